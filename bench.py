@@ -1,6 +1,6 @@
 """Headline benchmark: 96x96 HR crops/sec of the SRGAN GAN train step on MI355X.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python bench.py --gpus N ...          (N > 1 outside torchrun: starts its own N ranks as a child process, see self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -13,7 +13,11 @@ available offline).  Inputs are resident in HBM before the timed region.  One pr
 at N > 1 the gradient buckets are all-reduced over RCCL as the backward pass completes them
 (weak scaling); the line then carries the process group it actually ran on.
 
-Rank 0 prints ONE JSON line.  At N = 1 it also carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times ``--steps`` steps and prints it: ``value`` (crops/s) and
+``ms_per_step`` come from the host clock around the timed steps.  ``--dump-outputs DIR`` then writes what the last timed step
+computed as DIR/<name>.npy (see ``dump_outputs``; inputs and initial weights are seeded, so two builds compare output for output).
+With ``--full`` (side measurements outside the timed region; each ``--no-*`` option drops one) at N = 1 the line also carries
+  "step_ms_spread": p10 / median / p90 of up to 50 further steps (a HIP event pair around each);
   "parity":       the four losses of the FIRST step (seeded default-init weights) on the HIP path and on the
                   CPU oracle from the same weights and batch; ``rel`` is the generator-loss difference;
   "roofline":     the dominant kernel by device time, measured live with HIP events on the launch stream in an
@@ -598,6 +602,35 @@ def cpu_baseline(states, lr, hr, warmup=3, steps=10, budget_s=60.0):
                                     'sample': f'{n2} timed pre-training steps of batch 2, median {med2 * 1e3:.1f} ms/step'}}
 
 
+DUMP_SAMPLE = 1 << 22  # a state of more elements is dumped as a fixed, seeded sample of this many
+
+
+def flat_state(sd):
+    """The floating-point entries of a state dict (parameters, BatchNorm running statistics), flattened and concatenated in the
+    state dict's order, as float32 on the host."""
+    return torch.cat([v.detach().reshape(-1).float().cpu() for v in sd.values() if v.is_floating_point()])
+
+
+def dump_outputs(out_dir, losses, states):
+    """``--dump-outputs DIR``: what the timed path computed in its last step, as DIR/<name>.npy (float32) -- the losses
+    ``gan_step`` returns (``gan/train-loss`` -> ``gan_train_loss``) and, per network in ``states`` ({name: state dict}), its
+    state after the step (``flat_state``) as ``<name>_state``; a state of more than DUMP_SAMPLE elements keeps the elements at
+    DUMP_SAMPLE fixed positions (a seeded permutation's first DUMP_SAMPLE, in ascending order), 64 MB in all at the most.
+    Returns {name: shape}."""
+    import numpy as np
+    arrays = {k.replace('/', '_').replace('-', '_'): v.detach().float().cpu().numpy() for k, v in losses.items()}
+    for name, sd in states.items():
+        flat = flat_state(sd)
+        if flat.numel() > DUMP_SAMPLE:
+            pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(1234))[:DUMP_SAMPLE].sort().values
+            flat = flat[pick]
+        arrays[f'{name}_state'] = flat.numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), arr.astype(np.float32))
+    return {name: list(arr.shape) for name, arr in arrays.items()}
+
+
 def assert_fracs(obj, path='line'):
     """Every ``frac`` of the line is a share of a hardware peak: none may exceed 1."""
     if isinstance(obj, dict):
@@ -623,6 +656,10 @@ def main():
     ap.add_argument('--no-other-configs', action='store_true')
     ap.add_argument('--no-dp-rehearsal', action='store_true')
     ap.add_argument('--dp-contention', default='16', help='CUs held during the data-parallel rehearsal, comma separated (default 16)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: step spread, parity, roofline, CPU baseline, other configurations, data-parallel rehearsal')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's losses and network states as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -675,7 +712,7 @@ def main():
     trainer.discriminator.train()
     lr, hr = synth_batch(device, rank)
 
-    single = world == 1 and not forced  # the side measurements of the default one-GPU run
+    single = world == 1 and not forced and args.full  # the side measurements of the one-GPU run (--full)
     want_parity = single and not args.no_parity
     states0 = cpu_states(trainer) if (single and not (args.no_parity and args.no_cpu_baseline)) else None
     first = trainer.gan_step(lr, hr)  # set-up step 1 of 3 (eager); its losses feed the parity check
@@ -727,6 +764,10 @@ def main():
     gen_loss = float(losses['gan/train-loss'])
     if not (gen_loss == gen_loss):
         sys.exit('bench.py: generator loss is NaN')
+    if args.dump_outputs and rank == 0:  # before any further step changes the states
+        shapes = dump_outputs(args.dump_outputs, losses, {'generator': trainer.generator.state_dict(),
+                                                          'discriminator': trainer.discriminator.state_dict()})
+        print(f'bench.py: wrote {len(shapes)} arrays to {args.dump_outputs}: {shapes}', file=sys.stderr)
 
     # spread of the step time (outside the timed region): per-step HIP events on the step's stream
     spread = None

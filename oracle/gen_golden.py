@@ -35,6 +35,18 @@ os.makedirs(OUT, exist_ok=True)
 torch.set_num_threads(8)
 
 
+def savez_lzma(path, **arrays):
+    """``np.savez`` with LZMA-compressed members (``np.load`` reads them): keeps srgan_steps.npz, mostly float samples that
+    deflate barely shrinks, under the 1 MiB a committed file may have."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, 'w', zipfile.ZIP_LZMA) as z:
+        for name, value in arrays.items():
+            buf = io.BytesIO()
+            np.save(buf, np.asanyarray(value))
+            z.writestr(name + '.npy', buf.getvalue())
+
+
 def install_torchvision_stub():
     """torchvision is absent in this image (plain ModuleNotFoundError).  Provide just what
     torchsr/srgan/{loss,trainer}.py import: models.vgg19, utils.save_image, transforms.*."""
@@ -384,7 +396,7 @@ def gen_steps():
     out.update(b16_pre_loss=np.float64(loss),
                b16_pre_g_digest=np.stack([tensor_digest(v) for k, v in sorted(t.generator.state_dict().items())]),
                b16_pre_g_sample=sample_table(t.generator.state_dict()))
-    np.savez_compressed(os.path.join(OUT, 'srgan_steps.npz'), **out)
+    savez_lzma(os.path.join(OUT, 'srgan_steps.npz'), **out)
     os.chdir(ROOT)
 
 

@@ -590,3 +590,28 @@ def test_bench_fractions_are_shares_of_a_peak():
     for bad in ({'roofline': {'frac': 1.1218}}, {'x': [{'dominant_kernel': {'frac': 1.03}}]}, {'step_frac_of_fp32_mfma_peak': 1.2}):
         with pytest.raises(AssertionError):
             bench.assert_fracs(bad)
+
+
+def test_bench_dump_outputs_are_float32_fixed_and_within_64_mb(tmp_path):
+    """``bench.py --dump-outputs DIR``: the losses of the last step and the networks' states as float32 .npy files, at most 64 MB
+    in all (the 23.6 M-element discriminator as a fixed sample), the same positions on every call."""
+    import bench
+    from torchsr_amd.srgan.discriminator import Discriminator
+    from torchsr_amd.srgan.generator import Generator
+    torch.manual_seed(0)
+    states = {'generator': Generator().state_dict(), 'discriminator': Discriminator().state_dict()}
+    losses = {'gan/disc-loss': torch.tensor(1.25), 'gan/train-loss': torch.tensor(0.5)}
+    shapes = bench.dump_outputs(str(tmp_path / 'a'), losses, states)
+    bench.dump_outputs(str(tmp_path / 'b'), losses, states)
+    assert shapes == {'gan_disc_loss': [], 'gan_train_loss': [], 'generator_state': [1551574],
+                      'discriminator_state': [bench.DUMP_SAMPLE]}
+    total = 0
+    for name in shapes:
+        a, b = np.load(tmp_path / 'a' / f'{name}.npy'), np.load(tmp_path / 'b' / f'{name}.npy')
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+        total += os.path.getsize(tmp_path / 'a' / f'{name}.npy')
+    assert total <= 64 << 20
+    assert float(np.load(tmp_path / 'a' / 'gan_train_loss.npy')) == 0.5
+    assert np.array_equal(np.load(tmp_path / 'a' / 'generator_state.npy'), bench.flat_state(states['generator']).numpy())
+    flat_d = bench.flat_state(states['discriminator']).numpy()
+    assert np.isin(np.load(tmp_path / 'a' / 'discriminator_state.npy')[:1000], flat_d).all()
