@@ -131,6 +131,23 @@ int srx_conv2d_stat_rows(const srx_conv2d_t* d);
  * BM = 144 is the 128 + 16 row tile, BM = 36 the row-tile kernel of rowtile.hip. */
 int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out);
 
+/* Plan overrides for tests and tile experiments (no reference counterpart).  They hold for every later call of this process until
+ * reset with zeros (srx_wgrad_force: (-1, 0)); the environment seeds them at load (SRX_FORCE_PLAN="BM,BN,split,ks", SRX_S2_MODE bit 0,
+ * SRX_NO_WGRAD_LIN, SRX_WGRAD_NSPLIT).  srx_conv2d_plan and the workspace queries report what a forced call runs.  A forced form a
+ * layer has no kernel for (tile not instantiated at the layer's arithmetic, BN not dividing the padded columns, 144 rows with bf16
+ * products, the fused kernel on a layer it cannot run, more row splits than the rows allow) is refused with SRX_E_UNSUPPORTED and
+ * a message when that layer is planned or called, before anything is launched.
+ * srx_conv2d_force_plan: every gconv_kernel / gconv_multi_kernel plan (not the whole-frame calls above 2^24 pixels) is BM x BN
+ *   (BM = 144: the 128 + 16 row tile), every tile K-split `split` ways where the output is linear (strided / shuffled outputs run
+ *   unsplit), KS = 2: two wave groups on the 64 x 64 tile (64 x 32 always has 2, or 4 with bf16 products).
+ * srx_conv2d_force_s2: strided data gradients -- mode 0 the cost model, 1 always gconv_multi_kernel (tile from the model or
+ *   srx_conv2d_force_plan), 2 always gconv_s2f_kernel on tile BM x BN ((2, 0, 0): the model's fused tile).
+ * srx_wgrad_force: fp32 weight gradients -- lin 0: never the LIN form of wgrad_dma_kernel, 1 / -1: wherever it is eligible (the
+ *   default); nsplit > 0: that many row splits (whole 32-row chunks of at least 128 rows), 0: the model's. */
+int srx_conv2d_force_plan(int bm, int bn, int split, int ks);
+int srx_conv2d_force_s2(int mode, int bm, int bn);
+int srx_wgrad_force(int lin, int nsplit);
+
 /* OIHW master weights -> packed forward ([Cout_p][K_p], K=(kh,kw,ci)) and, when
  * wpk_bwd != NULL, packed data-gradient operands (per stride-parity class,
  * taps flipped, [Cin_p][K'_p], K'=(tap,co)). */

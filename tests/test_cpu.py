@@ -615,3 +615,90 @@ def test_bench_dump_outputs_are_float32_fixed_and_within_64_mb(tmp_path):
     assert np.array_equal(np.load(tmp_path / 'a' / 'generator_state.npy'), bench.flat_state(states['generator']).numpy())
     flat_d = bench.flat_state(states['discriminator']).numpy()
     assert np.isin(np.load(tmp_path / 'a' / 'discriminator_state.npy')[:1000], flat_d).all()
+
+
+def test_forced_plans_change_the_reported_plan_and_reset_restores_the_model_without_a_gpu():
+    """``srx_conv2d_force_plan`` / ``srx_conv2d_force_s2`` / ``srx_wgrad_force`` (plan arithmetic only, host code): each changes
+    what ``srx_conv2d_plan`` and the workspace queries report as specified, a forced form a layer has no kernel for is refused
+    with a message, and zeros hand the choice back to the cost model exactly.  The default plans of the discriminators'
+    strided layers are pinned, so that a cost-model change shows up as a deliberate edit here."""
+    import ctypes as C
+    from torchsr_amd import _lib
+    lib = _lib.lib()
+    if lib.srx_plan_cus() != 256:
+        pytest.skip('the pinned plans are those of a 256-CU part')
+    out = (C.c_int * 6)()
+
+    def desc(n, h, w, cin, cout, stride=2, prec=0, k=3):
+        return _lib.Conv2dDesc(n, h, w, cin, (cin + 3) // 4 * 4, cout, (cout + 3) // 4 * 4, k, k, stride, k // 2, 0, 0, 0.0, 0, prec)
+
+    def plan(d, which=1):
+        rc = lib.srx_conv2d_plan(C.byref(d), which, out)
+        return list(out) if rc == 0 else (rc, _lib.last_error())
+
+    d96, d128, d12 = desc(16, 96, 96, 64, 64), desc(16, 128, 128, 64, 64), desc(16, 12, 12, 512, 512)
+    d96b, d128b = desc(16, 96, 96, 64, 64, prec=1), desc(16, 128, 128, 64, 64, prec=1)
+    small, s1 = desc(3, 26, 30, 64, 64), desc(2, 24, 24, 128, 128, stride=1)
+    pinned = {  # {BM, BN, split, workgroups, KS, multi (1 gconv_multi_kernel, 2 gconv_s2f_kernel)}
+        'd96': [144, 64, 1, 256, 1, 2], 'd128': [128, 64, 1, 512, 1, 2], 'd12': [64, 64, 1, 288, 2, 1],
+        'd96b': [128, 64, 1, 1152, 1, 1], 'd128b': [128, 64, 1, 512, 1, 2], 'small': [64, 64, 1, 40, 1, 1],
+        's1': [64, 64, 6, 216, 2, 0]}
+    layers = {'d96': d96, 'd128': d128, 'd12': d12, 'd96b': d96b, 'd128b': d128b, 'small': small, 's1': s1}
+
+    def defaults():
+        return {k: plan(d, 0 if k == 's1' else 1) for k, d in layers.items()}
+
+    wl = desc(2, 12, 20, 64, 64, stride=1)   # 480 rows: at most 4 row splits of >= 128 rows
+    ws_default = lib.srx_conv2d_bwd_weight_multi_ws_floats(C.byref(wl), 1)
+    try:
+        assert defaults() == pinned
+        # the fused kernel on a forced tile (also one the model never picks), and back on gconv_multi_kernel at the model's tile
+        assert lib.srx_conv2d_force_s2(2, 128, 128) == 0 and plan(desc(2, 22, 18, 128, 128)) == [128, 128, 1, 2, 1, 2]
+        assert lib.srx_conv2d_force_s2(2, 64, 64) == 0
+        assert plan(small) == [64, 64, 1, 10, 1, 2] and plan(d96) == [64, 64, 1, 576, 1, 2]
+        assert lib.srx_conv2d_force_s2(2, 0, 0) == 0 and plan(d96b) == [128, 64, 1, 288, 1, 2]   # (the model's fused tile)
+        assert lib.srx_conv2d_force_s2(1, 0, 0) == 0
+        assert plan(d96) == [144, 64, 1, 1024, 1, 1] and plan(d12) == pinned['d12']
+        # ... and on a forced tile: KS = 2 where asked, the 144-row tile fp32 only, tiles gconv_multi_kernel lacks refused
+        assert lib.srx_conv2d_force_plan(64, 64, 1, 2) == 0 and plan(d96) == [64, 64, 1, 2304, 2, 1]
+        assert lib.srx_conv2d_force_plan(144, 64, 1, 1) == 0 and plan(small) == [144, 64, 1, 20, 1, 1]
+        rc, msg = plan(desc(3, 26, 30, 64, 64, prec=1))
+        assert rc == 2 and 'no 144-row tile' in msg
+        assert lib.srx_conv2d_force_plan(64, 32, 1, 1) == 0
+        rc, msg = plan(small)
+        assert rc == 2 and 'gconv_multi_kernel' in msg and 'no instantiation' in msg
+        # the forward and stride-1 data gradient: the forced tile with its K split, KS implied by 64 x 32
+        assert plan(s1, 0) == [64, 32, 1, 72, 2, 0] and plan(s1, 1)[:5] == [64, 32, 1, 72, 2]
+        assert lib.srx_conv2d_force_plan(144, 128, 3, 1) == 0 and plan(s1, 0) == [144, 128, 3, 24, 1, 0]
+        assert lib.srx_conv2d_fwd_ws_floats(C.byref(s1)) == 8 * 3 * 144 * 128   # (every tile K-split: one partial per split)
+        rc, msg = plan(desc(2, 24, 24, 128, 128, stride=1, prec=1), 0)
+        assert rc == 2 and 'no 144-row tile' in msg
+        rc, msg = plan(desc(2, 24, 24, 64, 64, stride=1, k=5), 1)   # (64 padded columns)
+        assert rc == 2 and 'do not divide' in msg
+        assert lib.srx_conv2d_fwd_ws_floats(C.byref(desc(2, 24, 24, 64, 64, stride=1, k=5))) == 0
+        # the fused kernel where it cannot run: odd extent, Cin = 32, Cout = 48, a tile without a bf16 instantiation
+        assert lib.srx_conv2d_force_plan(0, 0, 0, 0) == 0 and lib.srx_conv2d_force_s2(2, 64, 64) == 0
+        for bad in (desc(2, 13, 18, 64, 64), desc(2, 14, 18, 32, 64), desc(2, 14, 18, 64, 48)):
+            rc, msg = plan(bad)
+            assert rc == 2 and 'gconv_s2f_kernel refused' in msg
+        assert lib.srx_conv2d_force_s2(2, 144, 64) == 0
+        rc, msg = plan(d96b)
+        assert rc == 2 and 'no instantiation' in msg
+        # the weight gradient's row splits (its workspace holds one slab per split)
+        assert lib.srx_wgrad_force(-1, 2) == 0
+        assert lib.srx_conv2d_bwd_weight_multi_ws_floats(C.byref(wl), 1) == 64 * 577 * 2
+        assert lib.srx_wgrad_force(0, 5) == 0
+        assert lib.srx_conv2d_bwd_weight_multi_ws_floats(C.byref(wl), 1) == 0 and 'row splits refused' in _lib.last_error()
+        # arguments out of range are refused by the setters themselves
+        for fn, args in (('srx_conv2d_force_plan', (144, 64, 0, 1)), ('srx_conv2d_force_plan', (96, 64, 1, 1)),
+                         ('srx_conv2d_force_plan', (64, 64, 1, 3)), ('srx_conv2d_force_s2', (3, 0, 0)),
+                         ('srx_conv2d_force_s2', (2, 144, 32)), ('srx_conv2d_force_s2', (1, 64, 64)),
+                         ('srx_wgrad_force', (2, 0)), ('srx_wgrad_force', (-1, 65))):
+            with pytest.raises(RuntimeError, match=fn[4:]):
+                _lib.call(fn, *args)
+    finally:
+        lib.srx_conv2d_force_plan(0, 0, 0, 0)
+        lib.srx_conv2d_force_s2(0, 0, 0)
+        lib.srx_wgrad_force(-1, 0)
+    assert defaults() == pinned
+    assert lib.srx_conv2d_bwd_weight_multi_ws_floats(C.byref(wl), 1) == ws_default

@@ -129,17 +129,130 @@ def test_conv2d_fwd_bwd(dev, case):
         assert rel_err(conv.bias.grad, bc.grad) < 2e-4
 
 
-@pytest.mark.parametrize('plan', ['144,64,1,1', '144,128,1,1', '144,64,4,1', '144,128,3,1'])
+def _prof_names(fn):
+    """Run fn with the library's per-launch records on; the names of the conv kernels it launched."""
+    from torchsr_amd import _lib
+    _lib.call('srx_prof_start', 16)
+    try:
+        fn()
+    finally:
+        n = _lib.lib().srx_prof_stop()
+    buf, ms, fl = C.create_string_buffer(128), C.c_float(), C.c_double()
+    names = []
+    for i in range(n):
+        _lib.call('srx_prof_get', i, buf, 128, C.byref(ms), C.byref(fl))
+        names.append(buf.value.decode().split(' MxNxK')[0])
+    return names
+
+
+@pytest.mark.parametrize('plan', ['144,64,1,1', '144,128,1,1', '144,64,4,1', '144,128,3,1', '64,64,1,2', '64,32,1,1'])
 @pytest.mark.parametrize('case', [(2, 24, 24, 128, 128, 3, 1, 1, False, 0, 0),    # BN statistics, whole 144-row tiles
                                   (3, 13, 11, 64, 256, 3, 1, 1, True, 2, 0),     # ragged M, bias + LeakyReLU
                                   (2, 12, 12, 64, 256, 3, 1, 1, True, 0, 2),     # PixelShuffle store
                                   (2, 16, 16, 128, 128, 3, 2, 1, False, 0, 0)],  # stride 2 forward
                          ids=lambda c: 'x'.join(map(str, c)))
-def test_conv2d_144_row_tiles(dev, case, plan, monkeypatch):
-    """The 128 + 16 row tile (16 extra rows on 16x16x4 MFMAs) forced on several layers, whole and K-split
-    (fix-up kernel); the data gradient of a stride-1 layer takes the same plan."""
-    monkeypatch.setenv('SRX_FORCE_PLAN', plan)
-    test_conv2d_fwd_bwd(dev, case)
+def test_conv2d_144_row_tiles(dev, case, plan):
+    """A tile forced in-process (srx_conv2d_force_plan) on several layers, called through the C ABI (the layer class would send
+    the wide stride-1 ones to Winograd): the 128 + 16 row tile (16 extra rows on 16x16x4 MFMAs, XR = 16) whole and K-split
+    (fix-up kernel), the two-wave-group 64 x 64 tile and the 64 x 32 tile.  The forward and the data gradient take the forced
+    plan -- the stride-2 layer's on gconv_multi_kernel -- or, where that path has no kernel for the tile, refuse it and leave
+    the output untouched; the weight gradient has planners of its own."""
+    from torchsr_amd import _lib
+    n, h, w, cin, cout, k, s, p, bias, act, shuffle = case
+    bm, bn, split, ks = map(int, plan.split(','))
+    seed = hash(case) % 1000
+    L = _lib.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    cs_in = (cin + 3) // 4 * 4
+    cout_l = cout // 4 if shuffle else cout
+    cs_out = (cout_l + 3) // 4 * 4
+    d = _lib.Conv2dDesc(n, h, w, cin, cs_in, cout, cs_out, k, k, s, p, shuffle, act, 0.2, 0, 0)
+    x = rnd((n, cin, h, w), seed)
+    wt = rnd((cout, cin, k, k), seed + 1) * (2.0 / (cin * k * k)) ** 0.5 * 1.7
+    b = rnd((cout,), seed + 2) * 0.3 if bias else None
+    pre = TF.conv2d(x.double(), wt.double(), None if b is None else b.double(), s, p)
+    yc = TF.relu(pre) if act == 1 else TF.leaky_relu(pre, 0.2) if act == 2 else pre
+    if shuffle:
+        yc = TF.pixel_shuffle(yc, 2)
+    gy = rnd(yc.shape, seed + 3)
+    g_pre = TF.pixel_unshuffle(gy, 2) if shuffle else gy   # the gradient at the conv's own output
+    want_dx = torch.nn.grad.conv2d_input(x.shape, wt.double(), g_pre.double(), s, p)
+    want_dw = torch.nn.grad.conv2d_weight(x.double(), wt.shape, g_pre.double(), s, p)
+
+    wf = torch.empty(L.srx_conv2d_packed_fwd_floats(C.byref(d)), device=dev)
+    wb = torch.empty(max(L.srx_conv2d_packed_bwd_floats(C.byref(d)), 4), device=dev)
+    _lib.call('srx_conv2d_pack', C.byref(d), wt.to(dev).data_ptr(), wf.data_ptr(), wb.data_ptr(), st)
+    xg, gyg = nhwc(x, cs_in).to(dev), nhwc(gy, cs_out).to(dev)
+    kchunks = -(-k * k * cs_in // 32)
+    kind = lambda m, n: 'gconv_kernel<%d, %d, %d, 32, %d, %d, 0>' % (  # noqa: E731
+        128 if m == 144 else m, n, 64 if n == 128 else 32, 2 if (m, n) == (64, 32) else ks, 16 if m == 144 else 0)
+    want_stats = not bias and act == 0 and not shuffle
+    try:
+        _lib.call('srx_conv2d_force_plan', bm, bn, split, ks)
+        # forward: the forced tile, K-split where the output is linear (not through the PixelShuffle store)
+        out = (C.c_int * 6)()
+        _lib.call('srx_conv2d_plan', C.byref(d), 0, out)
+        sp = -(-kchunks // -(-kchunks // split)) if not shuffle else 1
+        assert list(out)[:3] == [bm, bn, sp] and out[4] == (2 if (bm, bn) == (64, 32) else ks), list(out)
+        y = torch.full((n, yc.shape[2], yc.shape[3], cs_out), float('nan'), device=dev)
+        part = torch.empty((L.srx_conv2d_stat_rows(C.byref(d)), cout, 2), device=dev) if want_stats else None
+        assert not want_stats or part.shape[0] == -(-pre[:, 0].numel() // bm)   # (one statistics row per row tile)
+        nws = L.srx_conv2d_fwd_ws_floats(C.byref(d))
+        ws = torch.empty(max(nws, 4), device=dev)
+        bg = b.to(dev) if bias else None
+        names = _prof_names(lambda: _lib.call('srx_conv2d_fwd', C.byref(d), xg.data_ptr(), wf.data_ptr(),
+                                              None if bg is None else bg.data_ptr(), y.data_ptr(),
+                                              None if part is None else part.data_ptr(), ws.data_ptr(), nws, st))
+        assert names == [kind(bm, bn)], names
+        assert rel_err(nchw(y.cpu(), cout_l), yc) < 2e-4
+        if cout_l % 4:
+            assert float(y[..., cout_l:].abs().max()) == 0.0
+        if want_stats:
+            s1 = part[:, :, 0].sum(0).cpu().double()
+            s2 = part[:, :, 1].sum(0).cpu().double()
+            ref1, ref2 = pre.sum((0, 2, 3)), pre.square().sum((0, 2, 3))
+            assert ((s1 - ref1).abs().max() / ref2.sqrt().max()).item() < 1e-4
+            assert rel_err(s2, ref2) < 2e-4
+        # data gradient: stride 1 on gconv_kernel (K-split), stride 2 on gconv_multi_kernel (no 64 x 32 form, no K split)
+        cnp = (cin + 63) // 64 * 64
+        refused = cnp % bn != 0 or (s == 2 and (bm, bn) == (64, 32))
+        dx = torch.full((n, h, w, cs_in), 7.0, device=dev)
+        nws = L.srx_conv2d_bwd_data_ws_floats(C.byref(d))
+        ws = torch.empty(max(nws, 4), device=dev)
+        run_dx = lambda: _lib.call('srx_conv2d_bwd_data', C.byref(d), gyg.data_ptr(), wb.data_ptr(), dx.data_ptr(), 0,  # noqa: E731
+                                   ws.data_ptr(), nws, st)
+        if refused:
+            assert L.srx_conv2d_plan(C.byref(d), 1, out) == 2 and 'refused' in _lib.last_error()
+            with pytest.raises(RuntimeError, match='refused'):
+                run_dx()
+            torch.cuda.synchronize()
+            assert bool((dx == 7.0).all())
+        else:
+            _lib.call('srx_conv2d_plan', C.byref(d), 1, out)
+            if s == 1:
+                dchunks = -(-k * k * ((cout + 3) // 4 * 4) // 32)
+                dsp = -(-dchunks // -(-dchunks // split))
+                assert list(out)[:3] == [bm, bn, dsp] and out[4] in (ks, 2) and out[5] == 0, list(out)
+                assert _prof_names(run_dx) == [kind(bm, bn)]
+            else:
+                assert list(out)[:3] == [bm, bn, 1] and out[4] == ks and out[5] == 1, list(out)
+                assert _prof_names(run_dx) == ['gconv_multi_kernel<%d, %d, %d, 32, %d, 0, %d>' % (
+                    128 if bm == 144 else bm, bn, 64 if bn == 128 else 32, 16 if bm == 144 else 0, ks)]
+            assert rel_err(nchw(dx.cpu(), cin), want_dx) < 2e-4
+            if cin % 4:
+                assert float(dx[..., cin:].abs().max()) == 0.0
+        # weight gradient (+ bias), which the forced plan does not touch
+        dw = torch.empty(cout, cin, k, k, device=dev)
+        db = torch.empty(cout, device=dev) if bias else None
+        nws = L.srx_conv2d_bwd_weight_ws_floats(C.byref(d))
+        ws = torch.empty(max(nws, 4), device=dev)
+        _lib.call('srx_conv2d_bwd_weight', C.byref(d), xg.data_ptr(), gyg.data_ptr(), dw.data_ptr(), 0,
+                  None if db is None else db.data_ptr(), ws.data_ptr(), nws, st)
+        assert rel_err(dw, want_dw) < 2e-4
+        if bias:
+            assert rel_err(db, g_pre.double().sum((0, 2, 3))) < 2e-4
+    finally:
+        _lib.call('srx_conv2d_force_plan', 0, 0, 0, 0)
 
 
 @pytest.mark.parametrize('case', [(2, 24, 24, 64, 64, 3, 1, 1, True), (2, 16, 16, 128, 256, 3, 1, 1, False),

@@ -153,6 +153,9 @@ _SIGS = {
     'srx_conv2d_bwd_weight_ws_floats': (_Z, [_D]),
     'srx_conv2d_stat_rows': (_I, [_D]),
     'srx_conv2d_plan': (_I, [_D, _I, C.POINTER(C.c_int)]),
+    'srx_conv2d_force_plan': (_I, [_I, _I, _I, _I]),
+    'srx_conv2d_force_s2': (_I, [_I, _I, _I]),
+    'srx_wgrad_force': (_I, [_I, _I]),
     'srx_pack_table_bytes': (_Z, [_I]),
     'srx_pack_table_build': (_I, [_P, _I, _P, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     'srx_pack_table_add_wino': (_I, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong), _D, _P, _P, _I]),

@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -1483,7 +1484,8 @@ __global__ __launch_bounds__(256) void wgrad_dma_kernel(const WMulti mp) {
 
   __shared__ unsigned okmask[LIN ? WG_MASKW : 1];
   if constexpr (LIN) {  // bit r of word c: tap (dh, dw) of row mbeg + 32 c + r is inside the image (and the row inside the split)
-    const int nrows = (((mend - mbeg + 31) / 32 + 2) * 32 + 63) & ~63;
+    // (chunks + 3 words: request() reads the word after the last look-ahead's too; the host keeps chunks + 3 <= WG_MASKW)
+    const int nrows = (((mend - mbeg + 31) / 32 + 3) * 32 + 63) & ~63;
     for (int base = wave * 64; base < nrows; base += 256) {
       const int m = mbeg + base + lane;
       int n, rem, mh, mw;
@@ -2129,9 +2131,46 @@ int bwd_classes(const srx_conv2d_t* d, BwdClass* cls, size_t& total_floats) {
 // only those r tiles take the partial-sum round trip through HBM.  Larger tiles are preferred
 // (fewer L2->LDS bytes per MFMA: the 64x64 tile moves 16 B/clk/workgroup and stalls on L1/L2)
 // unless they leave the chip under-filled.
-struct Plan { int BM, BN, mtiles, ntiles, tiles, full, tail, split, kc_per_split, ks; float cost; };
+struct Plan { int BM, BN, mtiles, ntiles, tiles, full, tail, split, kc_per_split, ks; float cost; bool refused; };
 
 int device_cus() { return srx_plan_cus(); }  // the device's CUs less the reserved ones (api.cpp)
+
+// In-process overrides of the planners (srx_conv2d_force_plan / srx_conv2d_force_s2 / srx_wgrad_force): tests switch kernel paths
+// inside one process with them.  Seeded from SRX_FORCE_PLAN, SRX_S2_MODE (bit 0), SRX_NO_WGRAD_LIN and SRX_WGRAD_NSPLIT at first use.
+struct ConvForce {
+  std::atomic<int> plan[4];  // BM, BN, split, KS of every gconv plan; BN = 0: off
+  std::atomic<int> s2[3];    // strided data gradients: mode (0 model, 1 gconv_multi_kernel, 2 gconv_s2f_kernel), BM, BN (mode 2)
+  std::atomic<int> wg[2];    // weight gradient: LIN (-1 default, 0 never, 1 where eligible), row splits (0: the model's)
+};
+ConvForce& conv_force() {
+  static ConvForce* f = [] {
+    ConvForce* s = new ConvForce;
+    const SrxDevSwitches& e = srx_dev();
+    for (int i = 0; i < 4; ++i) s->plan[i].store(e.force_plan ? e.plan[i] : 0);
+    s->s2[0].store((e.s2_mode & 1) ? 1 : 0); s->s2[1].store(0); s->s2[2].store(0);
+    s->wg[0].store(e.no_wgrad_lin ? 0 : -1); s->wg[1].store(e.wgrad_nsplit > 0 && e.wgrad_nsplit <= 64 ? e.wgrad_nsplit : 0);
+    return s;
+  }();
+  return *f;
+}
+bool forced_plan(int& bm, int& bn, int& sp, int& ks) {
+  ConvForce& f = conv_force();
+  bn = f.plan[1].load(std::memory_order_relaxed);
+  bm = f.plan[0].load(std::memory_order_relaxed); sp = f.plan[2].load(std::memory_order_relaxed); ks = f.plan[3].load(std::memory_order_relaxed);
+  return bn > 0;
+}
+
+// nullptr: gconv_kernel (multi = false) / gconv_multi_kernel (multi = true) has an instantiation for tile bm x bn with ks wave
+// groups at this arithmetic and the tile's columns divide the layer's padded ones; otherwise why not
+const char* forced_tile_refusal(int bm, int bn, int ks, int Cnp, bool bf16, bool multi) {
+  if (Cnp % bn != 0) return "the tile's columns do not divide the layer's padded output columns";
+  if (ks == 2 && !(bm == 64 && (bn == 64 || bn == 32))) return "two wave groups (KS = 2) on a tile other than 64 x 64 / 64 x 32";
+  if (bf16 && bm == 144) return "no 144-row tile with bf16 products";
+  if (!bf16 && bm == 256) return "no 256-row tile with fp32 products";
+  const bool known = (bm == 144 && (bn == 128 || bn == 64)) || (bm == 128 && (bn == 128 || bn == 64 || bn == 32)) ||
+                     (bm == 64 && bn == 64) || (!multi && bm == 64 && bn == 32) || (!multi && bm == 256 && bn == 128);
+  return known ? nullptr : "no instantiation of this tile";
+}
 
 Plan make_plan(int M, int Cnp, int kchunks, bool can_split, bool bf16 = false, bool big = false) {
   const int P = device_cus();
@@ -2179,18 +2218,23 @@ Plan make_plan(int M, int Cnp, int kchunks, bool can_split, bool bf16 = false, b
     p.cost = rounds * t_tile + tail_cost;
     if (p.cost < best.cost) best = p;
   }
-  // developer override for tile experiments: SRX_FORCE_PLAN="BM,BN,split,ks" (split: K-split of ALL tiles)
-  if (srx_dev().force_plan && !big) {
-    const int bm = srx_dev().plan[0], bn = srx_dev().plan[1], sp = srx_dev().plan[2], ks = srx_dev().plan[3];
-    if (bn > 0 && Cnp % bn == 0) {
-      Plan p{};
-      p.BM = bm; p.BN = bn; p.mtiles = (int)srx_cdiv(M, bm); p.ntiles = Cnp / bn; p.tiles = p.mtiles * p.ntiles;
-      if (sp > 1 && can_split) { p.full = 0; p.tail = p.tiles; p.kc_per_split = (int)srx_cdiv(kchunks, sp); p.split = (int)srx_cdiv(kchunks, p.kc_per_split); }
-      else { p.full = p.tiles; p.tail = 0; p.split = 1; p.kc_per_split = kchunks; }
-      p.ks = (bm == 64 && bn == 64 && ks == 2) ? 2 : 1;
-      if (bm == 64 && bn == 32) p.ks = bf16 ? 4 : 2;
+  // forced plan (srx_conv2d_force_plan, SRX_FORCE_PLAN="BM,BN,split,ks"; split: K-split of ALL tiles where the output is linear,
+  // strided / shuffled outputs run unsplit).  A tile without a kernel is refused (`refused`, message set), never replaced.
+  int bm, bn, sp, ks;
+  if (!big && forced_plan(bm, bn, sp, ks)) {
+    Plan p{};
+    if (const char* why = forced_tile_refusal(bm, bn, ks, Cnp, bf16, false)) {
+      srx_set_error("conv2d: forced plan %d x %d (KS %d) refused: %s (%d padded columns, %s products)", bm, bn, ks, why, Cnp,
+                    bf16 ? "bf16" : "fp32");
+      p.refused = true;
       return p;
     }
+    p.BM = bm; p.BN = bn; p.mtiles = (int)srx_cdiv(M, bm); p.ntiles = Cnp / bn; p.tiles = p.mtiles * p.ntiles;
+    if (sp > 1 && can_split) { p.full = 0; p.tail = p.tiles; p.kc_per_split = (int)srx_cdiv(kchunks, sp); p.split = (int)srx_cdiv(kchunks, p.kc_per_split); }
+    else { p.full = p.tiles; p.tail = 0; p.split = 1; p.kc_per_split = kchunks; }
+    p.ks = (bm == 64 && bn == 64 && ks == 2) ? 2 : 1;
+    if (bm == 64 && bn == 32) p.ks = bf16 ? 4 : 2;
+    return p;
   }
   // fewer workgroups than CUs and a 4-wave tile: split its k-chunks over two wave groups (KS = 2)
   best.ks = (best.BM == 64 && best.BN == 64 && best.full + best.tail * best.split <= P && best.kc_per_split >= 4) ? 2 : 1;
@@ -2248,7 +2292,8 @@ int launch_gconv_multi(const GMulti& m, size_t lds, hipStream_t st) {
 // Tile for a multi-problem launch.  The stride-parity classes of a data gradient have the same M but
 // 1x..4x different K, and their strided outputs cannot take the split-K fix-up path, so balance comes
 // from the tile size alone: every candidate's workgroups are list-scheduled heavy-first (the order
-// run_gconv_multi launches them in) over the CUs and the shortest makespan wins.
+// run_gconv_multi launches them in) over the CUs and the shortest makespan wins.  A forced plan (srx_conv2d_force_plan) costs 0;
+// one without a gconv_multi_kernel instantiation returns -1 with the message set.
 float multi_tile(const GMulti& m, int Cnp, int& BM, int& BN, int& KS, bool bf16 = false) {
   const int P = device_cus();
   constexpr int NC = 7;
@@ -2257,8 +2302,14 @@ float multi_tile(const GMulti& m, int Cnp, int& BM, int& BN, int& KS, bool bf16 
   const float eff[NC] = {0.91f, 0.82f, 0.95f, 0.85f, 0.60f, 0.50f, 0.80f};
   float best = 1e30f;
   BM = 128; BN = Cnp == 32 ? 32 : 64; KS = 1;
-  if (srx_dev().force_plan && srx_dev().plan[1] > 0 && Cnp % srx_dev().plan[1] == 0) {  // developer override (SRX_FORCE_PLAN)
-    BM = srx_dev().plan[0]; BN = srx_dev().plan[1]; KS = (BM == 64 && BN == 64 && srx_dev().plan[3] == 2) ? 2 : 1;
+  int fbm, fbn, fsp, fks;
+  if (forced_plan(fbm, fbn, fsp, fks)) {
+    if (const char* why = forced_tile_refusal(fbm, fbn, fks, Cnp, bf16, true)) {
+      srx_set_error("conv2d_bwd_data: forced plan %d x %d (KS %d) refused for gconv_multi_kernel: %s (%d padded columns, %s products)",
+                    fbm, fbn, fks, why, Cnp, bf16 ? "bf16" : "fp32");
+      return -1.f;
+    }
+    BM = fbm; BN = fbn; KS = (BM == 64 && BN == 64 && fks == 2) ? 2 : 1;
     return 0.f;
   }
   std::vector<float> heap;
@@ -2322,20 +2373,22 @@ int run_gconv_multi(GMulti& m, int BM, int BN, int KS, hipStream_t st, int preci
     if (BM == 128 && BN == 128) return launch_gconv_multi<128, 128, 64, 32, 0, 1>(m, lds, st);
     if (BM == 128 && BN == 64) return launch_gconv_multi<128, 64, 32, 32, 0, 1>(m, lds, st);
     if (BM == 64 && BN == 64) return launch_gconv_multi<64, 64, 32, 32, 0, 1>(m, lds, st);
-    return launch_gconv_multi<128, 32, 32, 32, 0, 1>(m, lds, st);
+    if (BM == 128 && BN == 32) return launch_gconv_multi<128, 32, 32, 32, 0, 1>(m, lds, st);
+    SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_bwd_data: no bf16 gconv_multi_kernel for tile %d x %d", BM, BN);
   }
   if (BM == 144 && BN == 128) return launch_gconv_multi<128, 128, 64, 32, 16>(m, lds, st);
   if (BM == 144 && BN == 64) return launch_gconv_multi<128, 64, 32, 32, 16>(m, lds, st);
   if (BM == 128 && BN == 128) return launch_gconv_multi<128, 128, 64, 32, 0>(m, lds, st);
   if (BM == 128 && BN == 64) return launch_gconv_multi<128, 64, 32, 32, 0>(m, lds, st);
   if (BM == 64 && BN == 64) return launch_gconv_multi<64, 64, 32, 32, 0>(m, lds, st);
-  return launch_gconv_multi<128, 32, 32, 32, 0>(m, lds, st);
+  if (BM == 128 && BN == 32) return launch_gconv_multi<128, 32, 32, 32, 0>(m, lds, st);
+  SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_bwd_data: no gconv_multi_kernel for tile %d x %d", BM, BN);
 }
 
 // ---- the fused-class strided data gradient (gconv_s2f_kernel) ----
 // Eligible: 2..4 non-empty classes on ONE M grid (extents multiples of the stride), whole chunks per tap, plain gather.
 bool s2f_eligible(const srx_conv2d_t* d, const BwdClass* cls, int nc) {
-  if ((srx_dev().s2_mode & 1) || nc < 2 || nc > 4 || d->shuffle || d->up || d->precision > 1) return false;
+  if (nc < 2 || nc > 4 || d->shuffle || d->up || d->precision > 1) return false;
   if (bwd_ck(d) % BK != 0 || pad_rows(d->Cin) % 64 != 0) return false;
   for (int i = 0; i < nc; ++i)
     if (cls[i].K == 0 || cls[i].Hm != cls[0].Hm || cls[i].Wm != cls[0].Wm || cls[i].Hm <= 0 || cls[i].Wm <= 0) return false;
@@ -2423,7 +2476,48 @@ int run_gconv_s2f(const srx_conv2d_t* d, const GArgs& shared, const BwdClass* cl
   SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_bwd_data: internal: no fused-class instantiation for tile %d x %d", BM, BN);
 }
 
+// The launch of a strided data gradient whose stride-parity classes are m's problems: one gconv_s2f_kernel launch (fused) or one
+// gconv_multi_kernel launch, on tile BM x BN with KS wave groups -- the cost model's choice, or the forced one
+// (srx_conv2d_force_s2 / srx_conv2d_force_plan).  A forced form the layer has no kernel for is refused here, before any launch;
+// srx_conv2d_plan reports what this returns.
+int strided_dgrad_plan(const srx_conv2d_t* d, const BwdClass* cls, int nc, const GMulti& m, int& BM, int& BN, int& KS, bool& fused) {
+  ConvForce& f = conv_force();
+  const int mode = f.s2[0].load(std::memory_order_relaxed);
+  const bool bf16 = d->precision != 0;
+  const int Cnp = pad_rows(d->Cin);
+  const bool eligible = m.n == nc && s2f_eligible(d, cls, nc);
+  fused = false;
+  if (mode == 2) {
+    if (!eligible)
+      SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_bwd_data: forced gconv_s2f_kernel refused: the layer needs 2..4 non-empty stride-parity "
+                                  "classes on one grid (extents multiples of the stride), Cout and Cin in whole chunks, no shuffle / upsample");
+    int bm = f.s2[1].load(std::memory_order_relaxed), bn = f.s2[2].load(std::memory_order_relaxed);
+    if (bm == 0) {
+      s2f_tile(d, cls, nc, bm, bn);
+    } else {
+      const bool known = bf16 ? ((bm == 128 && (bn == 128 || bn == 64)) || (bm == 64 && bn == 64))
+                              : (((bm == 144 || bm == 128) && (bn == 128 || bn == 64)) || (bm == 64 && bn == 64));
+      if (!known || Cnp % bn != 0)
+        SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_bwd_data: forced gconv_s2f_kernel tile %d x %d refused: %s (%d padded columns, %s products)",
+                 bm, bn, known ? "the tile's columns do not divide the layer's" : "no instantiation of this tile", Cnp, bf16 ? "bf16" : "fp32");
+    }
+    BM = bm; BN = bn; KS = 1; fused = true;
+    return SRX_OK;
+  }
+  const float t_multi = multi_tile(m, Cnp, BM, BN, KS, bf16);
+  if (t_multi < 0.f) return SRX_E_UNSUPPORTED;
+  if (mode == 0 && eligible) {  // all classes of a tile in one workgroup, when that is the shorter launch
+    int fbm, fbn;
+    const float t_fused = s2f_tile(d, cls, nc, fbm, fbn);
+    if (fbm > 0 && (0.97f * t_fused < t_multi || (srx_dev().s2_mode & 4))) {  // (a tie goes to the fused launch: measured)
+      BM = fbm; BN = fbn; KS = 1; fused = true;
+    }
+  }
+  return SRX_OK;
+}
+
 int run_gconv(GArgs& a, const Plan& p, float* ws, size_t ws_floats, hipStream_t st, int precision = 0) {
+  if (p.refused) return SRX_E_UNSUPPORTED;  // (a forced plan the layer has no kernel for: make_plan set the message)
   a.kchunks = a.Kp / BK;
   const size_t need = plan_ws_floats(p);
   if (need && (!ws || need > ws_floats))
@@ -2472,7 +2566,8 @@ int run_gconv(GArgs& a, const Plan& p, float* ws, size_t ws_floats, hipStream_t 
   if (p.BM == 64 && p.BN == 64)
     return p.ks == 2 ? launch_gconv<64, 64, 32, 32, 2, 0>(a, p, st) : launch_gconv<64, 64, 32, 32, 1, 0>(a, p, st);
   if (p.BM == 64 && p.BN == 32) return launch_gconv<64, 32, 32, 32, 2, 0>(a, p, st);
-  return launch_gconv<128, 32, 32, 32, 1, 0>(a, p, st);
+  if (p.BM == 128 && p.BN == 32) return launch_gconv<128, 32, 32, 32, 1, 0>(a, p, st);
+  SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: no fp32 kernel for tile %dx%d", p.BM, p.BN);
 }
 
 void set_mgrid(GArgs& a, int N, int Hm, int Wm) {
@@ -2569,7 +2664,15 @@ static int wgrad_nsplit(int M, int64_t tiles, int nprob, int Cnw, int Kw, int pr
     }
     if (cost < best_cost) { best_cost = cost; nsplit = ns; }
   }
-  if (const int v = srx_dev().wgrad_nsplit; v > 0 && v <= 64 && v <= max_by_rows) nsplit = v;
+  if (const int v = conv_force().wg[1].load(std::memory_order_relaxed); v > 0) {  // srx_wgrad_force / SRX_WGRAD_NSPLIT
+    const int rps = (int)srx_roundup(srx_cdiv(M, v), 32);
+    if (v > max_by_rows || (int)srx_cdiv(M, rps) != v) {
+      srx_set_error("conv2d_bwd_weight: forced %d row splits refused: %d rows split into whole 32-row chunks of at least 128 rows "
+                    "give %d splits", v, M, v > max_by_rows ? max_by_rows : (int)srx_cdiv(M, rps));
+      return -1;
+    }
+    nsplit = v;
+  }
   const int rps = (int)srx_roundup(srx_cdiv(M, nsplit), 32);
   return (int)srx_cdiv(M, rps);
 }
@@ -2607,6 +2710,7 @@ extern "C" size_t srx_conv2d_bwd_weight_multi_ws_floats(const srx_conv2d_t* d, i
   const size_t Cnw = (size_t)srx_roundup(d->Cout, 64), Kw = (size_t)srx_roundup(g.K, 64);
   const int ns = wgrad_rows_ok(d) ? wgrad_rows_nsplit(d, nprob)
                                   : wgrad_nsplit(d->N * g.Ho * g.Wo, (int64_t)(Kw / 64) * (Cnw / 64), nprob, (int)Cnw, (int)Kw, d->precision);
+  if (ns < 0) return 0;  // (a refused forced split: the call reports it)
   return Cnw * (Kw + 1) * (size_t)ns * nprob;  // one slab (+ one bias row) per problem and row split
 }
 
@@ -2631,6 +2735,7 @@ extern "C" int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out) {
   }
   if (which == 0) {
     p = fwd_plan(d, fwd_geo(d));
+    if (p.refused) return SRX_E_UNSUPPORTED;
   } else {
     SRX_REQUIRE(d->stride <= 4, "conv2d_plan: stride > 4 unsupported");
     BwdClass cls[16];
@@ -2645,14 +2750,11 @@ extern "C" int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out) {
         m.g[m.n++].Kp = cls[i].Kp;
       }
       p = Plan{};
-      const float t_multi = multi_tile(m, pad_rows(d->Cin), p.BM, p.BN, p.ks, d->precision != 0);
+      bool fused = false;
+      if (int rc = strided_dgrad_plan(d, cls, nc, m, p.BM, p.BN, p.ks, fused)) return rc;
       p.split = 1; p.tail = 0;
-      int fbm = 0, fbn = 0;
-      const bool fused = m.n == nc && s2f_eligible(d, cls, nc) &&
-                         (0.97f * s2f_tile(d, cls, nc, fbm, fbn) < t_multi || (srx_dev().s2_mode & 4)) && fbm > 0;
       if (fused) {  // (multi = 2: all classes of a tile in one workgroup, gconv_s2f_kernel)
-        p.BM = fbm; p.BN = fbn; p.ks = 1;
-        p.full = (int)srx_cdiv(m.g[0].M, fbm) * (pad_rows(d->Cin) / fbn);
+        p.full = (int)srx_cdiv(m.g[0].M, p.BM) * (pad_rows(d->Cin) / p.BN);
         multi = 2;
       } else {
         for (int i = 0; i < m.n; ++i) p.full += (int)srx_cdiv(m.g[i].M, p.BM) * (int)srx_cdiv(d->Cin, p.BN);
@@ -2660,9 +2762,38 @@ extern "C" int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out) {
       }
     } else {
       p = bwd_plan(d, cls[0]);
+      if (p.refused) return SRX_E_UNSUPPORTED;
     }
   }
   out[0] = p.BM; out[1] = p.BN; out[2] = p.split; out[3] = p.full + p.tail * p.split; out[4] = p.ks; out[5] = multi;
+  return SRX_OK;
+}
+
+extern "C" int srx_conv2d_force_plan(int bm, int bn, int split, int ks) {
+  SRX_REQUIRE((bm == 0 && bn == 0 && split == 0 && ks == 0) ||
+              ((bm == 64 || bm == 128 || bm == 144 || bm == 256) && (bn == 32 || bn == 64 || bn == 128) && split >= 1 && split <= 16 &&
+               (ks == 1 || ks == 2)),
+              "conv2d_force_plan: (0, 0, 0, 0) or BM 64 / 128 / 144 / 256, BN 32 / 64 / 128, split 1..16, KS 1 / 2");
+  ConvForce& f = conv_force();
+  f.plan[1].store(0);  // (off while the others change)
+  f.plan[0].store(bm); f.plan[2].store(split); f.plan[3].store(ks); f.plan[1].store(bn);
+  return SRX_OK;
+}
+
+extern "C" int srx_conv2d_force_s2(int mode, int bm, int bn) {
+  SRX_REQUIRE(((mode == 0 || mode == 1) && bm == 0 && bn == 0) ||
+              (mode == 2 && ((bm == 0 && bn == 0) || ((bm == 64 || bm == 128 || bm == 144) && (bn == 64 || bn == 128)))),
+              "conv2d_force_s2: (0, 0, 0), (1, 0, 0) or (2, BM 64 / 128 / 144, BN 64 / 128) -- (2, 0, 0): the model's fused tile");
+  ConvForce& f = conv_force();
+  f.s2[0].store(0);
+  f.s2[1].store(bm); f.s2[2].store(bn); f.s2[0].store(mode);
+  return SRX_OK;
+}
+
+extern "C" int srx_wgrad_force(int lin, int nsplit) {
+  SRX_REQUIRE(lin >= -1 && lin <= 1 && nsplit >= 0 && nsplit <= 64, "wgrad_force: LIN -1 / 0 / 1, 0..64 row splits");
+  ConvForce& f = conv_force();
+  f.wg[0].store(lin); f.wg[1].store(nsplit);
   return SRX_OK;
 }
 
@@ -2970,15 +3101,15 @@ static int conv_bwd_data_impl(const srx_conv2d_t* d, const float* dy, const floa
     return srx_rt36_run(d, dy, wpk_bwd + cls[0].woff, nullptr, addend, dx, nullptr, SRX_ACT_NONE, 0.f, st);
   bool any_empty = false;
   for (int i = 0; i < nc; ++i) any_empty |= (cls[i].K == 0);
-  if (any_empty) {
-    if (hipMemsetAsync(dx, 0, (size_t)d->N * d->H * d->W * d->Cin_s * sizeof(float), st) != hipSuccess)
-      SRX_FAIL(SRX_E_HIP, "conv2d_bwd_data: memset failed");
-  }
   const size_t dy_bytes = (size_t)d->N * g.Ho * g.Wo * (d->shuffle ? 4 : 1) * d->Cout_s * sizeof(float);
   SRX_REQUIRE(small_enough(d) && dy_bytes < 0xfffffff0ull,
               "conv2d_bwd_data: more than 2^24 pixels or 4 GiB per tensor (data gradients keep 32-bit offsets: training crops, not whole frames)");
 
+  // every launch is planned (and a refused forced plan reported) before dx is touched
   GMulti multi{};
+  GArgs single[16];
+  Plan single_plan[16];
+  int ns = 0;
   for (int i = 0; i < nc; ++i) {
     const BwdClass& c = cls[i];
     if (c.K == 0 || c.Hm <= 0 || c.Wm <= 0) continue;
@@ -3014,23 +3145,26 @@ static int conv_bwd_data_impl(const srx_conv2d_t* d, const float* dy, const floa
     a.add_ld = accumulate ? a.Co : addend_ld; a.add_hi = accumulate ? 0x7fffffff : addend_channels;
     a.ascale = accumulate ? 1.f : addend_scale;
     if (act_out) { a.mask = act_out; a.mask_slope = act_slope; a.mask_lo = c_lo; a.mask_hi = c_hi; }
-    if (d->stride == 1) {
-      if (int rc = run_gconv(a, bwd_plan(d, c), ws, ws_floats, st, d->precision)) return rc;
-    } else if (nc <= 4) {
+    if (d->stride != 1 && nc <= 4) {
       multi.g[multi.n++] = a;
-    } else {  // stride > 2: one launch per class (with the layer's arithmetic: bf16 products under precision = 1)
-      if (int rc = run_gconv(a, bwd_plan(d, c), ws, ws_floats, st, d->precision)) return rc;
+    } else {  // stride 1, or stride > 2: one launch per class (with the layer's arithmetic: bf16 products under precision = 1)
+      single_plan[ns] = bwd_plan(d, c);
+      if (single_plan[ns].refused) return SRX_E_UNSUPPORTED;
+      single[ns++] = a;
     }
   }
+  int bm = 0, bn = 0, ks = 1;
+  bool fused = false;
+  if (multi.n > 0)
+    if (int rc = strided_dgrad_plan(d, cls, nc, multi, bm, bn, ks, fused)) return rc;
+  if (any_empty) {
+    if (hipMemsetAsync(dx, 0, (size_t)d->N * d->H * d->W * d->Cin_s * sizeof(float), st) != hipSuccess)
+      SRX_FAIL(SRX_E_HIP, "conv2d_bwd_data: memset failed");
+  }
+  for (int i = 0; i < ns; ++i)
+    if (int rc = run_gconv(single[i], single_plan[i], ws, ws_floats, st, d->precision)) return rc;
   if (multi.n > 0) {
-    int bm, bn, ks;
-    const float t_multi = multi_tile(multi, pad_rows(d->Cin), bm, bn, ks, d->precision != 0);
-    if (multi.n == nc && s2f_eligible(d, cls, nc)) {  // all classes of a tile in one workgroup, when that is the shorter launch
-      int fbm, fbn;
-      const float t_fused = s2f_tile(d, cls, nc, fbm, fbn);
-      if (fbm > 0 && (0.97f * t_fused < t_multi || (srx_dev().s2_mode & 4)))  // (a tie goes to the fused launch: measured)
-        return run_gconv_s2f(d, multi.g[0], cls, nc, wpk_bwd, total, fbm, fbn, st);
-    }
+    if (fused) return run_gconv_s2f(d, multi.g[0], cls, nc, wpk_bwd, total, bm, bn, st);
     if (int rc = run_gconv_multi(multi, bm, bn, ks, st, d->precision)) return rc;
   }
   return SRX_OK;
@@ -3259,6 +3393,7 @@ static int wgrad_multi_impl(const srx_conv2d_t* d, int nprob, int per_out, const
   const int64_t tiles = (int64_t)a.ktiles * ntiles;
   const bool rows_kernel = wgrad_rows_ok(d);
   const int nsplit = rows_kernel ? wgrad_rows_nsplit(d, nprob) : wgrad_nsplit(a.M, tiles, nprob, a.Cnw, a.Kw, d->precision);
+  if (nsplit < 0) return SRX_E_UNSUPPORTED;  // (wgrad_nsplit set the message)
   a.rows_per_split = rows_kernel ? (int)srx_cdiv(d->N * d->H, nsplit) * d->W : (int)srx_roundup(srx_cdiv(a.M, nsplit), 32);
   a.nsplit = nsplit;
   a.nprob = nprob;
@@ -3286,19 +3421,28 @@ static int wgrad_multi_impl(const srx_conv2d_t* d, int nprob, int per_out, const
     else SRX_LAUNCH_PROF(nm, wfl, wgrad_rows_bf16_kernel<16>, grid, dim3(256), 0, st, mp);
     SRX_CHECK_LAUNCH("wgrad_rows_bf16_kernel");
   } else {
-  if (srx_prof_on())
-    snprintf(nm, sizeof(nm), "wgrad_kernel<%d> MxNxK=%dx%dx%d x%d", d->precision ? 1 : 0, a.M, d->Cout, a.K, nprob);
-  if (d->precision) SRX_LAUNCH_PROF(nm, wfl, wgrad_kernel<1>, grid, dim3(256), 0, st, mp);
-  else if (srx_dev().no_wgrad_dma) SRX_LAUNCH_PROF(nm, wfl, wgrad_kernel<0>, grid, dim3(256), 0, st, mp);
-  else if (g.Ck % 64 == 0 && a.Cdv % 64 == 0 && (!a.dy_shuffle || a.dy_shuffle % 64 == 0)) {
-    // LIN: offsets linear in the row, validity from a per-workgroup bit table (see wgrad_dma_kernel)
-    const bool lin = !srx_dev().no_wgrad_lin && a.in_stride == 1 && a.Hi == a.Hm && a.Wi == a.Wm && !a.dy_shuffle && a.K % 64 == 0 &&
-                     a.rows_per_split / 32 + 3 <= WG_MASKW && a.in_bytes < 0xfff00000u && a.dy_bytes < 0xfff00000u;
-    if (lin) SRX_LAUNCH_PROF(nm, wfl, (wgrad_dma_kernel<true, true>), grid, dim3(256), 0, st, mp);
-    else SRX_LAUNCH_PROF(nm, wfl, wgrad_dma_kernel<true>, grid, dim3(256), 0, st, mp);
-  }
-  else SRX_LAUNCH_PROF(nm, wfl, wgrad_dma_kernel<false>, grid, dim3(256), 0, st, mp);
-  SRX_CHECK_LAUNCH("wgrad_kernel");
+    // form: 0 wgrad_kernel<PR>, 1 wgrad_dma_kernel<0, 0>, 2 wgrad_dma_kernel<1, 0> (WIDE), 3 wgrad_dma_kernel<1, 1> (WIDE + LIN:
+    // offsets linear in the row, validity from a per-workgroup bit table, see wgrad_dma_kernel; srx_wgrad_force(0, .) turns it off)
+    int form = 0;
+    if (!d->precision && !srx_dev().no_wgrad_dma) {
+      form = 1;
+      if (g.Ck % 64 == 0 && a.Cdv % 64 == 0 && (!a.dy_shuffle || a.dy_shuffle % 64 == 0)) {
+        const bool lin = conv_force().wg[0].load(std::memory_order_relaxed) != 0 && a.in_stride == 1 && a.Hi == a.Hm && a.Wi == a.Wm &&
+                         !a.dy_shuffle && a.K % 64 == 0 && a.rows_per_split / 32 + 3 <= WG_MASKW && a.in_bytes < 0xfff00000u &&
+                         a.dy_bytes < 0xfff00000u;
+        form = lin ? 3 : 2;
+      }
+    }
+    if (srx_prof_on()) {
+      if (form == 0) snprintf(nm, sizeof(nm), "wgrad_kernel<%d> MxNxK=%dx%dx%d x%d", d->precision ? 1 : 0, a.M, d->Cout, a.K, nprob);
+      else snprintf(nm, sizeof(nm), "wgrad_dma_kernel<%d, %d> MxNxK=%dx%dx%d x%d", form >= 2 ? 1 : 0, form == 3 ? 1 : 0, a.M, d->Cout, a.K, nprob);
+    }
+    if (d->precision) SRX_LAUNCH_PROF(nm, wfl, wgrad_kernel<1>, grid, dim3(256), 0, st, mp);
+    else if (form == 0) SRX_LAUNCH_PROF(nm, wfl, wgrad_kernel<0>, grid, dim3(256), 0, st, mp);
+    else if (form == 3) SRX_LAUNCH_PROF(nm, wfl, (wgrad_dma_kernel<true, true>), grid, dim3(256), 0, st, mp);
+    else if (form == 2) SRX_LAUNCH_PROF(nm, wfl, wgrad_dma_kernel<true>, grid, dim3(256), 0, st, mp);
+    else SRX_LAUNCH_PROF(nm, wfl, wgrad_dma_kernel<false>, grid, dim3(256), 0, st, mp);
+    SRX_CHECK_LAUNCH("wgrad_kernel");
   }
   if (srx_dev().old_wgrad_reduce || (size_t)g.K * sizeof(float) > 48 * 1024) {
     const int64_t n = (int64_t)d->Cout * g.K;
