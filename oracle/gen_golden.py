@@ -1,6 +1,6 @@
 """ORACLE pinning script -- run ONLY in the build container (needs /root/reference).
 
-    python oracle/gen_golden.py
+    python oracle/gen_golden.py [generator | steps | checkpoint]
 
 1. imports the reference's own modules (``torchsr.srgan.{generator,discriminator}``) and,
    under a minimal ``torchvision`` stub (torchvision is not installed here; the stub only
@@ -219,6 +219,29 @@ def gen_generator():
                     f'{tag}_y_eval': ye.numpy(), f'{tag}_dx': x.grad.numpy(), f'{tag}_grad_keys': gk,
                     f'{tag}_grad_digest': gd, f'{tag}_running_keys': rk, f'{tag}_running_digest': rd,
                     f'{tag}_loss': np.float64(loss.item())})
+    # Forward-only cases at larger sizes: LR 24x24 (the residual blocks on the row-tile kernel) and LR 20x28 (non-square).  No kink screen: no input of these sizes keeps every activation 5e-6 rms from its kink (best
+    # margins over 20 seeds: 2x3x24x24 2.1e-6, 1x3x20x28 2.9e-6, 1x3x24x24 2.8e-6), so their GRADIENTS are not comparable
+    # between two fp32 implementations.  Forward outputs are: PReLU is continuous, an activation near its kink does not
+    # move them.  Stored: train / eval outputs, the loss and the running-statistics digests -- no gradients.
+    for tag, shape, seed in [('c', (2, 3, 24, 24), 300), ('d', (1, 3, 20, 28), 400)]:
+        ref.load_state_dict(sd0)
+        x = seeded_input(shape, seed)
+        ref.train()
+        with torch.no_grad():
+            y = ref(x)
+        loss = y.square().mean()
+        sd = {k: v.clone() for k, v in sd0.items()}
+        check(f'G[{tag}] train output', O.generator_forward(sd, x, True), y)
+        post = ref.state_dict()
+        for k in ('blocks.5.bn2.running_mean', 'conv2.1.running_var'):
+            check(f'G[{tag}] {k}', sd[k], post[k])
+        ref.eval()
+        with torch.no_grad():
+            ye = ref(x)
+        check(f'G[{tag}] eval output', O.generator_forward({k: v.clone() for k, v in post.items()}, x, False), ye)
+        rk, rd = digest_table({k: v for k, v in post.items() if 'running_' in k})
+        out.update({f'{tag}_x': x.numpy(), f'{tag}_y_train': y.numpy(), f'{tag}_y_eval': ye.numpy(),
+                    f'{tag}_running_keys': rk, f'{tag}_running_digest': rd, f'{tag}_loss': np.float64(loss.item())})
     np.savez_compressed(os.path.join(OUT, 'srgan_generator.npz'), **out)
 
 
@@ -555,6 +578,9 @@ if __name__ == '__main__':
     install_torchvision_stub()
     if sys.argv[1:] == ['checkpoint']:
         gen_checkpoint()
+        sys.exit(0)
+    if sys.argv[1:] == ['generator']:
+        gen_generator()
         sys.exit(0)
     if sys.argv[1:] == ['steps']:
         gen_steps()

@@ -55,6 +55,35 @@ def test_generator_vs_golden(dev, tag):
     assert rel(ye, gold[f'{tag}_y_eval']) < TOL
 
 
+@pytest.mark.parametrize('tag', ['c', 'd'])
+def test_generator_forward_vs_golden(dev, tag):
+    """Forward only, at sizes the gradient fixtures cannot have (no input keeps every activation clear of its kink there,
+    oracle/gen_golden.py): LR 2x3x24x24, where the residual blocks' 64 -> 64 convs run on the row-tile kernel (12-pixel tiles at
+    1152 pixels; the step's 36-pixel tiles and BatchNorm folds are pinned by test_step_layers_gpu.py's tower case), and LR
+    1x3x20x28 (non-square).  Train- and eval-mode outputs, the loss and the running statistics."""
+    from step_layers import prof_launches
+    from torchsr_amd.srgan.generator import Generator
+    gold = np.load(os.path.join(GOLDEN, 'srgan_generator.npz'))
+    gen = Generator()
+    gen.load_state_dict(closed_form_state(gen.state_dict()))
+    gen = gen.to(dev).train()
+    x = torch.from_numpy(gold[f'{tag}_x']).to(dev)
+    out = []
+    names = prof_launches(lambda: out.append(gen(x)))  # (autograd recording, as in training)
+    y = out[0]
+    assert tag != 'c' or any(k.startswith('rt36_conv3x3_c64_kernel') for k in names), sorted(set(names))
+    assert rel(y, gold[f'{tag}_y_train']) < TOL
+    loss = y.square().mean()
+    assert abs(loss.item() - float(gold[f'{tag}_loss'])) < TOL * float(gold[f'{tag}_loss'])
+    sd = gen.state_dict()
+    for k, dg in zip(gold[f'{tag}_running_keys'], gold[f'{tag}_running_digest']):
+        assert digest_rel(sd[str(k)], dg) < TOL, k
+    gen.eval()
+    with torch.no_grad():
+        ye = gen(x)
+    assert rel(ye, gold[f'{tag}_y_eval']) < TOL
+
+
 @pytest.mark.parametrize('tag,size', [('s32', 32), ('s96', 96)])
 def test_discriminator_vs_golden(dev, tag, size):
     from torchsr_amd import functional as F

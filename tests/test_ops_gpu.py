@@ -130,19 +130,9 @@ def test_conv2d_fwd_bwd(dev, case):
 
 
 def _prof_names(fn):
-    """Run fn with the library's per-launch records on; the names of the conv kernels it launched."""
-    from torchsr_amd import _lib
-    _lib.call('srx_prof_start', 16)
-    try:
-        fn()
-    finally:
-        n = _lib.lib().srx_prof_stop()
-    buf, ms, fl = C.create_string_buffer(128), C.c_float(), C.c_double()
-    names = []
-    for i in range(n):
-        _lib.call('srx_prof_get', i, buf, 128, C.byref(ms), C.byref(fl))
-        names.append(buf.value.decode().split(' MxNxK')[0])
-    return names
+    """Run fn with the library's per-launch records on; the names of the conv kernels it launched (without MxNxK)."""
+    from step_layers import prof_launches
+    return [k.split(' MxNxK')[0] for k in prof_launches(fn)]
 
 
 @pytest.mark.parametrize('plan', ['144,64,1,1', '144,128,1,1', '144,64,4,1', '144,128,3,1', '64,64,1,2', '64,32,1,1'])
@@ -873,15 +863,7 @@ def test_bicubic_down_vs_pil_fixture(dev):
     assert (diff != 0).mean() < 0.15, (diff != 0).mean()
 
 
-FULL_SIZE_LAYERS = [
-    # every distinct conv shape of the batch-16 SRGAN GAN step (BASELINE configs[1]): N, H, W, Cin, Cout, k, s, p, shuffle
-    (16, 24, 24, 64, 64, 3, 1, 1, 0), (16, 24, 24, 3, 64, 9, 1, 4, 0), (16, 24, 24, 64, 256, 3, 1, 1, 2),
-    (16, 48, 48, 64, 256, 3, 1, 1, 2), (16, 96, 96, 64, 3, 9, 1, 4, 0), (16, 96, 96, 3, 64, 3, 1, 1, 0),
-    (16, 96, 96, 64, 64, 3, 2, 1, 0), (16, 48, 48, 64, 128, 3, 1, 1, 0), (16, 48, 48, 128, 128, 3, 2, 1, 0),
-    (16, 24, 24, 128, 256, 3, 1, 1, 0), (16, 24, 24, 256, 256, 3, 2, 1, 0), (16, 12, 12, 256, 512, 3, 1, 1, 0),
-    (16, 12, 12, 512, 512, 3, 2, 1, 0), (32, 96, 96, 64, 64, 3, 1, 1, 0), (32, 48, 48, 128, 128, 3, 1, 1, 0),
-    (32, 24, 24, 256, 256, 3, 1, 1, 0), (32, 12, 12, 512, 512, 3, 1, 1, 0), (32, 6, 6, 512, 512, 3, 1, 1, 0),
-]
+from step_layers import FULL_SIZE_LAYERS  # noqa: E402  (shared with test_step_layers_gpu.py)
 
 
 @pytest.mark.parametrize('case', FULL_SIZE_LAYERS, ids=lambda c: 'x'.join(map(str, c)))

@@ -46,15 +46,19 @@ def oracle_for(t, dtype=torch.float32):
 
 
 # How many "fp32-vs-fp64 distances of the oracle" this package's parameters may sit from the reference's after the SECOND and third
-# step.  Not derived: two fp32 evaluations can sit on opposite sides of the exact value (x 2), this package's convs carry up to 3 x
-# the rounding error of the oracle's direct convs (Winograd F(2x2,3x3): tools/experiments/wino_error.py) and every rounding
-# difference that flips an activation decision in one of ~50 layers moves whole elements; measured 5.2 on the deepest layer
-# (blocks.0.conv1.weight after two steps, round 6), the first failure of this assertion at the factor 2 it was written with.
-# Applied to the network's sampled tensors together (per tensor a 512-element sample may hold no flipped element at all).
+# step: 8, in both runs (measured 5.2 on the deepest layer, blocks.0.conv1.weight after two steps, round 6).  With Winograd off the
+# hypothesis is 2 -- two independent fp32 evaluations sit about sqrt(2) as far apart as each sits from fp64 -- checked after
+# every other assertion of the run (StepFactorExceeded).  Applied to the network's sampled tensors together (per tensor a
+# 512-element sample may hold no flipped element at all).
 YARD_FACTOR = 8.0
+YARD_HYPOTHESIS_OFF = 2.0
 
 
-def assert_digests(keys, sd, digests, what, samples=None, steps=1, yard=None):
+class StepFactorExceeded(AssertionError):
+    """A step-level factor hypothesis (Winograd off) does not hold; raised only after every other check of the run passed."""
+
+
+def assert_digests(keys, sd, digests, what, samples=None, steps=1, yard=None, hypothesis=None):
     """Post-step state against the fixture captured from the unmodified reference trainer.  SMALL tensors (< 4096 elements):
     their digest -- sums over the tensor -- with a slack for at most two elements per Adam step moving the other way (an
     element whose gradient sits at the fp32 noise floor moves by +-lr in a direction that differs between any two fp32
@@ -65,7 +69,8 @@ def assert_digests(keys, sd, digests, what, samples=None, steps=1, yard=None):
     sampling noise of that count, lie within 2e-6 absolute.  After LATER steps Adam's update depends on gradient ratios and the
     elements near the noise floor part ways for good: the sample's L2 distance from the fixture is then measured in units of
     ``yard`` = {key: L2 distance over the same sample between the oracle evaluated in fp32 and in fp64 after the same steps} --
-    what fp32 arithmetic itself costs on this batch -- and may be at most ``YARD_FACTOR`` of them; no element is further off than
+    what fp32 arithmetic itself costs on this batch -- and may be at most ``YARD_FACTOR`` of them (``hypothesis``: a list that
+    collects (what, yards) where the count exceeds YARD_HYPOTHESIS_OFF); no element is further off than
     one Adam step per step taken, ever."""
     big = sample_keys(sd) if samples is not None else []
     for k, dg in zip(keys, digests):
@@ -96,7 +101,11 @@ def assert_digests(keys, sd, digests, what, samples=None, steps=1, yard=None):
         if steps > 1:
             # (over all sampled tensors of the network together: whether a 512-element sample of ONE tensor holds a flipped
             # element at all is a draw, for the yardstick as for the product -- per tensor the ratio of two such draws says nothing)
+            yards = sq_mine ** 0.5 / max(sq_yard ** 0.5, 1e-300)
+            print(f'  {what}: {yards:.2f} yards')
             assert sq_mine ** 0.5 <= YARD_FACTOR * sq_yard ** 0.5 + 1e-6, (what, sq_mine ** 0.5, sq_yard ** 0.5)
+            if hypothesis is not None and sq_mine ** 0.5 > YARD_HYPOTHESIS_OFF * sq_yard ** 0.5 + 1e-6:
+                hypothesis.append((what, round(yards, 2)))
             return
         # ... and over ALL sampled tensors together the flipped share is held to the 0.2 % the elementwise oracle checks allow
         mean = 2e-3 * tot
@@ -133,15 +142,39 @@ def assert_elementwise(mod, ref, name):
             assert diff.max().item() <= 2.1e-4, (name, k, diff.max().item())
 
 
-def test_gan_steps_vs_golden(dev):
+def conv_launches(fn):
+    """Run fn with the library's per-launch records on; (its result, the names of the conv kernels it launched)."""
+    from step_layers import prof_launches
+    out = []
+    names = prof_launches(lambda: out.append(fn()))
+    return out[0], names
+
+
+def winograd(monkeypatch, on):
+    """Winograd F(2x2,3x3) on or off for the trainers built after this call (every Winograd routing decision reads
+    ``_dev.NO_WINO`` in Python: functional.wino_layer_ok, wino_forward_only_ok)."""
+    from torchsr_amd import _dev
+    monkeypatch.setattr(_dev, 'NO_WINO', not on)
+
+
+YARD_OFF_XFAIL = pytest.mark.xfail(strict=True, raises=StepFactorExceeded,
+                                   reason='Winograd off: G measured 2.57 yards after the second step (MI355X), not 2')
+_SR_AFTER3 = {}  # the generator's eval-mode output after test_gan_steps_vs_golden's three steps, by Winograd on / off
+
+
+@pytest.mark.parametrize('wino', [True, pytest.param(False, marks=YARD_OFF_XFAIL)], ids=['wino', 'direct'])
+def test_gan_steps_vs_golden(dev, wino, monkeypatch):
+    winograd(monkeypatch, wino)
     gold = np.load(os.path.join(GOLDEN, 'srgan_steps.npz'))
     lr, hr = torch.from_numpy(gold['low_res']), torch.from_numpy(gold['high_res'])
     t = make_trainer(dev, use_graphs=False)
     g_keys = [str(k) for k in gold['g_keys']]
     d_keys = [str(k) for k in gold['d_keys']]
     o32, o64 = oracle_for(t), oracle_for(t, torch.float64)  # (the yardstick of the later steps: assert_digests)
+    hypothesis = None if wino else []
     for step in range(3):
-        losses = t.gan_step(lr.to(dev), hr.to(dev))
+        losses, names = conv_launches(lambda: t.gan_step(lr.to(dev), hr.to(dev)))
+        assert wino or not any(k.startswith('wino_kernel') for k in names), names
         o32.gan_step(lr, hr)
         o64.gan_step(lr.double(), hr.double())
         got = [losses[k].item() for k in LOSS_KEYS]
@@ -150,12 +183,36 @@ def test_gan_steps_vs_golden(dev):
             assert abs(g - w) <= 1e-3 * max(abs(w), 1e-3), (step, got, want)
         assert abs(got[3] - gold['gan_ref_gen_losses'][step]) <= 1e-3 * gold['gan_ref_gen_losses'][step]
         # post-step parameters and BN running statistics of the reference trainer, after every step
-        assert_digests(g_keys, t.generator.state_dict(), gold['gan_g_digest'][step], f'G step {step}', gold['gan_g_sample'][step], step + 1, yardstick(o32, o64, 'g'))
-        assert_digests(d_keys, t.discriminator.state_dict(), gold['gan_d_digest'][step], f'D step {step}', gold['gan_d_sample'][step], step + 1, yardstick(o32, o64, 'd'))
+        assert_digests(g_keys, t.generator.state_dict(), gold['gan_g_digest'][step], f'G step {step}', gold['gan_g_sample'][step], step + 1, yardstick(o32, o64, 'g'), hypothesis)
+        assert_digests(d_keys, t.discriminator.state_dict(), gold['gan_d_digest'][step], f'D step {step}', gold['gan_d_sample'][step], step + 1, yardstick(o32, o64, 'd'), hypothesis)
     t.generator.eval()
     with torch.no_grad():
         sr = t.generator(lr.to(dev))
     assert abs(O.psnr(sr.cpu(), hr) - float(gold['gan_psnr_after3'])) < 0.01  # PSNR parity (0.01 dB) after 3 steps
+    _SR_AFTER3[wino] = sr.cpu()
+    if hypothesis:
+        raise StepFactorExceeded(hypothesis)
+
+
+@pytest.mark.xfail(strict=True, reason='measured max |sr - ref| = 4.79e-3 max |ref| after 3 steps (MI355X), not 1e-3')
+def test_gan_sr_after3_elementwise(dev):
+    """The super-resolved image after three GAN steps, element by element, against the unmodified reference's
+    (north_star's 1e-3 of the largest element).  A test of its own, not an assertion inside test_gan_steps_vs_golden[wino]: that
+    one passes and must keep telling so.  It reads the image test_gan_steps_vs_golden[wino] made when that ran first."""
+    gold = np.load(os.path.join(GOLDEN, 'srgan_steps.npz'))
+    lr = torch.from_numpy(gold['low_res'])
+    sr = _SR_AFTER3.get(True)
+    if sr is None:
+        t = make_trainer(dev, use_graphs=False)
+        for _ in range(3):
+            t.gan_step(lr.to(dev), torch.from_numpy(gold['high_res']).to(dev))
+        t.generator.eval()
+        with torch.no_grad():
+            sr = t.generator(lr.to(dev)).cpu()
+    ref_sr = torch.from_numpy(gold['gan_sr_after3']).double()
+    err = ((sr.cpu().double() - ref_sr).abs().max() / ref_sr.abs().max()).item()
+    print(f'  SR after 3 steps: max |sr - ref| / max |ref| = {err:.2e}')
+    assert err <= 1e-3, err
 
 
 def test_baseline_size_gan_step_vs_reference_and_oracle(dev):
@@ -180,14 +237,32 @@ def test_baseline_size_gan_step_vs_reference_and_oracle(dev):
     assert_elementwise(t.discriminator, orc.d, 'D')
 
 
-def test_baseline_size_gradients_vs_oracle(dev):
+# With Winograd off the step-level hypothesis is "1.5 x the fp32 oracle's distance"; measured (MI355X) 1.71 (D) and 1.73 (G).  The
+# per-layer table (test_step_layers_gpu.py) holds 5 outputs above their budget (2.0-3.8 x torch's fp32 distance, open:
+# OVER_F there), but those are rounding-sized; the per-tensor figures here show where most of the step-level excess comes from -- D features.14 / 15 / 17 / 18 sit ~270 x the oracle's distance (6e-4 against
+# 2e-6) in BOTH runs, with features.18.bias at ~1100 x and features.18.weight at ~11 x: one LeakyReLU input within rounding of
+# zero behind features.18's BatchNorm (xhat ~ 0 there: the bias sum moves, the weight sum hardly) taken the other way.
+RMS_OFF_XFAIL = pytest.mark.xfail(strict=True, raises=StepFactorExceeded, reason='Winograd off: network RMS measured 1.71 x (D) / 1.73 x (G) the fp32 oracle\'s '
+                                  'distance from fp64, not 1.5 x: single activation decisions (D features.18), not Winograd; and G '
+                                  'blocks.11.prelu.weight (one element) at 2.66e-2 from fp64, over the 2e-2 ceiling (oracle fp32: 1.07e-2)')
+
+
+@pytest.mark.parametrize('wino', [True, pytest.param(False, marks=RMS_OFF_XFAIL)], ids=['wino', 'direct'])
+def test_baseline_size_gradients_vs_oracle(dev, wino, monkeypatch):
     """Adam's first step is ~lr * sign(g): the post-step comparisons above pin every gradient's direction but not its
     size.  This one compares the batch-16 GAN step's gradients themselves -- the flat .grad buffers right before each
     optimiser step -- with the oracle's, and the yardstick is COMPUTED (round 6; rounds 3-5 held hand-set budgets of
     cosine 0.9995 / max 2e-2 / median 2e-3): the oracle evaluated in fp64 is the reference point, the fp32 oracle's own
     distance from it is what fp32 arithmetic with a few LeakyReLU / PReLU / ReLU / max-pool decisions falling the other way costs
-    on THIS batch, and this package's gradients may be at most 3 x that far from the fp64 value (Winograd's rounding is 2-3 x the
-    direct form's), tensor by tensor (relative L2); the classifier's gradients to 1e-4 and the generator tail's to 1e-3 outright (north_star's figure)."""
+    on THIS batch, and this package's gradients may be at most 3 x that far from the fp64 value (with Winograd on), tensor by tensor (relative L2); the classifier's gradients to 1e-4 and the generator tail's to 1e-3 outright (north_star's figure).
+
+    Run with Winograd on and off; the network RMS is held to 3 x in both, and with Winograd off the hypothesis 1.5 x (two
+    independent fp32 evaluations) is checked after every other assertion of the run -- see RMS_OFF_XFAIL.
+    Both runs keep rounds 3-5's per-tensor checks against the fp32 oracle (max-abs relative < 2e-2 on every tensor, median over
+    the tensors < 2e-3) and hold every tensor of >= 4096 elements to 1.5 x (3 x with Winograd) the oracle's distance + 2e-3: the
+    floor is what ONE activation decision taken the other way costs a layer with a few thousand rows (~1 / sqrt(rows) of the
+    BatchNorm sums; measured 6e-4 on D features.14 / 17), so a layer wrong by 1e-2 cannot hide in the network's RMS."""
+    winograd(monkeypatch, wino)
     gold = np.load(os.path.join(GOLDEN, 'srgan_steps.npz'))
     s_lr, s_hr = (int(v) for v in gold['b16_seeds'])
     lr, hr = seeded_input((16, 3, 24, 24), s_lr), seeded_input((16, 3, 96, 96), s_hr)
@@ -231,7 +306,10 @@ def test_baseline_size_gradients_vs_oracle(dev):
     tap_oracle64(orc64.gen_optimizer, orc64.g, 'G')
     orc.gan_step(lr, hr)
     orc64.gan_step(lr.double(), hr.double())
-    t.gan_step(lr.to(dev), hr.to(dev))
+    _, names = conv_launches(lambda: t.gan_step(lr.to(dev), hr.to(dev)))
+    assert wino or not any(k.startswith('wino_kernel') for k in names), names
+    factor = 3.0 if wino else 1.5  # (per tensor, >= 4096 elements)
+    hypothesis = []
     report = {}
     for tag in ('D', 'G'):
         assert set(got[tag]) == set(want[tag]) == set(want64[tag])
@@ -243,20 +321,35 @@ def test_baseline_size_gradients_vs_oracle(dev):
             report[(tag, k)] = (mine, theirs)
             if ref.numel() > 1:
                 assert (a @ ref / (a.norm() * ref.norm()).clamp_min(1e-300)).item() > 0.9995, (tag, k)
-            assert mine <= 2e-2, (tag, k, mine, theirs)  # (the ceiling rounds 3-5 held on the max-norm: nothing is broken)
+            if mine > 2e-2 and not wino:  # (measured with Winograd off only: reported with the hypothesis, after every check)
+                hypothesis.append((tag, k, 'over the 2e-2 ceiling', round(mine, 4), round(theirs, 4)))
+            else:
+                assert mine <= 2e-2, (tag, k, mine, theirs)  # (the ceiling rounds 3-5 held on the max-norm: nothing is broken)
+            if g.numel() >= 4096:
+                assert mine <= factor * theirs + 2e-3, (tag, k, mine, theirs)
+        # rounds 3-5's per-tensor checks against the fp32 oracle: max-abs relative error, worst tensor and median tensor
+        maxrel = [((g.double() - want[tag][k].double()).abs().max() / want[tag][k].double().abs().max().clamp_min(1e-30)).item()
+                  for k, g in got[tag].items()]
+        print(f'  {tag}: max-abs relative vs the fp32 oracle: worst {max(maxrel):.2e}, median {float(np.median(maxrel)):.2e}')
+        assert max(maxrel) < 2e-2 and float(np.median(maxrel)) < 2e-3, (tag, max(maxrel), float(np.median(maxrel)))
         # Relative L2 distance from the fp64 gradient, over the network's tensors together (root mean square): no more than 3 x the
         # fp32 oracle's own.  Per tensor the ratio says little -- a 64-element BatchNorm gradient is a different number after ONE
         # LeakyReLU decision falls the other way, in the oracle's fp32 evaluation as in this package's, and which of the two
         # draws that card on a given tensor is chance (first failures of the per-tensor form: D features.0.weight at 1.74 x,
-        # features.3.weight at 4.4 x).  3, not the 1.5 the review suggested: the wide layers here are Winograd F(2x2,3x3) in
-        # fp32, whose rounding error is 2-3 x that of the direct fp32 convolution the oracle runs (against fp64:
-        # tools/experiments/wino_error.py), so that is how much further from the exact value this arithmetic may sit
+        # features.3.weight at 4.4 x).  3 in both runs; 1.5 with Winograd off is the hypothesis (RMS_OFF_XFAIL).  Measured (MI355X) 1.95 x / 0.63 x
+        # (D / G) with Winograd on and 1.71 x / 1.73 x with it off: the excess over 1.5 is not Winograd's rounding; the per-tensor
+        # signature below points at single activation decisions (D features.18)
         rms = lambda i: (sum(v[i] ** 2 for (tg, _k), v in report.items() if tg == tag) / len(got[tag])) ** 0.5  # noqa: E731
+        print(f'  {tag}: network RMS {rms(0):.3e} vs the fp32 oracle {rms(1):.3e}: {rms(0) / max(rms(1), 1e-300):.2f} x')
         assert rms(0) <= 3.0 * rms(1) + 2e-6, (tag, rms(0), rms(1))
+        if not wino and rms(0) > 1.5 * rms(1) + 2e-6:  # the hypothesis of the Winograd-off run: reported after every other check
+            hypothesis.append((tag, round(rms(0) / rms(1), 2)))
         # north_star's figure on what it can be asked of: nothing but two Linear layers lies between the loss and the classifier's
         # gradients, and the generator's last layers sit behind VGG19's and the discriminator's activations only
         tight = [k for k in got[tag] if k.startswith(('classifier', 'conv3', 'conv_layers.1'))]
         assert tight and all(report[(tag, k)][0] < (1e-4 if tag == 'D' else 1e-3) for k in tight), (tag, {k: report[(tag, k)] for k in tight})
+    if hypothesis:
+        raise StepFactorExceeded(hypothesis)
 
 
 def test_baseline_size_pretrain_step_vs_reference_and_oracle(dev):
