@@ -112,7 +112,13 @@ typedef struct srx_conv2d {
                          fp32 in memory, operands are rounded when staged into LDS; strided data
                          gradients and the 3-channel (thin) layers remain fp32.  2: only on the forward
                          of a 64 -> <= 4 channel layer (the generators' output conv): bf16 products there
-                         as well -- inference with every conv in bf16 (test.upscale(precision='bf16')) */
+                         as well -- inference with every conv in bf16 (test.upscale(precision='bf16')).
+                         3: fp16 inference (test.upscale(precision='fp16')), forward only and only for a
+                         <= 4-channel INPUT layer (Cin_s = 4, no shuffle / up): fp16 products with fp32
+                         accumulation, tensors fp32 in memory (operands rounded to nearest even when
+                         staged into LDS, like 1); the generator's 64-channel layers run on the _f16
+                         entry points below.  The host refuses 3 with autograd enabled or outside eval
+                         mode, the library on every backward entry point */
 } srx_conv2d_t;
 
 /* sizes (in floats) of the packed weight copies and of scratch buffers */
@@ -207,6 +213,27 @@ int srx_conv2d_fwd_bf16in(const srx_conv2d_t* d, const void* x_bf16, const float
 size_t srx_conv9x9_c64_thin_bf16_packed_bytes(void);
 int srx_conv9x9_c64_thin_bf16_pack(const float* w, const float* bias, int Cout, void* wpk, void* stream);
 int srx_conv9x9_c64_thin_bf16_fwd(int N, int H, int W, const void* x, const void* wpk, float* y, void* stream);
+
+/* ---------------------------------------------------------------- fp16-native inference chain */
+/* `torchsr test --precision fp16` (test.upscale(precision='fp16'), srx_conv2d_t::precision = 3): the same chain with the
+ * activations STORED as fp16 -- 11 significant bits instead of bf16's 8 at the same bytes per pixel, range +-65504 (the host
+ * checks the output for overflow).  Every entry point mirrors its bf16 namesake above: same arguments, same validation, same
+ * layouts and launch geometry, `void*` tensors hold fp16; packed weights are fp16 (BatchNorm scale applied in fp32 first),
+ * products are fp16 x fp16 on v_mfma_f32_32x32x16_f16, sums fp32, every rounding to fp16 is to nearest even.
+ * srx_conv3x3_c64_bf16_plan describes the fp16 launches too (same geometry). */
+size_t srx_conv3x3_c64_f16_packed_bytes(int Cout);
+int srx_conv3x3_c64_f16_pack(const float* w, const float* bias, const float* out_scale, int Cout, int shuffle, void* wpk,
+                             void* stream);
+/* y (fp16) = act(conv(x) + bias) [+ residual (fp16)], rounded once */
+int srx_conv3x3_c64_f16_fwd(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk, float slope,
+                            const void* residual, void* y, int y_cs, void* stream);
+/* fp32 -> fp16 rounds to nearest even (beyond 65519.99..: +-inf); fp16 -> fp32 is exact; n a positive multiple of 4 */
+int srx_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
+int srx_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
+/* the 9x9 64 -> <= 3 output conv on an fp16 input: fp16 products, fp32 accumulation, y fp32 [N][H][W][4] */
+size_t srx_conv9x9_c64_thin_f16_packed_bytes(void);
+int srx_conv9x9_c64_thin_f16_pack(const float* w, const float* bias, int Cout, void* wpk, void* stream);
+int srx_conv9x9_c64_thin_f16_fwd(int N, int H, int W, const void* x, const void* wpk, float* y, void* stream);
 
 /* y = act(conv(x, W) + bias) * out_scale + residual, residual laid out like y (not for shuffle layers).
  * With the eval-mode BatchNorm folded into W and bias by the host this is a whole `x + BN(conv(.))` of the

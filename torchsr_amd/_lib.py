@@ -172,6 +172,14 @@ _SIGS = {
     'srx_conv9x9_c64_thin_bf16_pack': (_I, [_P, _P, _I, _P, _P]),
     'srx_conv9x9_c64_thin_bf16_fwd': (_I, [_I, _I, _I, _P, _P, _P, _P]),
     'srx_conv2d_fwd_bf16in': (_I, [_D, _P, _P, _P, _P, _P]),
+    'srx_conv3x3_c64_f16_packed_bytes': (_Z, [_I]),
+    'srx_conv3x3_c64_f16_pack': (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    'srx_conv3x3_c64_f16_fwd': (_I, [_I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _I, _P]),
+    'srx_f32_to_f16': (_I, [_P, _P, _L, _P]),
+    'srx_f16_to_f32': (_I, [_P, _P, _L, _P]),
+    'srx_conv9x9_c64_thin_f16_packed_bytes': (_Z, []),
+    'srx_conv9x9_c64_thin_f16_pack': (_I, [_P, _P, _I, _P, _P]),
+    'srx_conv9x9_c64_thin_f16_fwd': (_I, [_I, _I, _I, _P, _P, _P, _P]),
     'srx_conv2d_fwd_residual': (_I, [_D, _P, _P, _P, _P, _F, _P, _P, _Z, _P]),
     'srx_conv2d_bwd_data': (_I, [_D, _P, _P, _P, _I, _P, _Z, _P]),
     'srx_conv2d_bwd_data_add': (_I, [_D, _P, _P, _P, _P, _P, _Z, _P]),

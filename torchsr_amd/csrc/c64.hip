@@ -42,7 +42,20 @@
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// The chain's 16-bit storage type: bf16 (precision 1 / 2) or fp16 (precision 3: 11 significant bits, range +-65504).  Only the
+// fragment type and the MFMA differ; both 32x32x16 forms take the same cycles on gfx950, and (T)float rounds to nearest even.
+template <typename T> struct E16;
+template <> struct E16<__bf16> {
+  typedef bf16x8 v8;
+  static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <> struct E16<_Float16> {
+  typedef f16x8 v8;
+  static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
 
 constexpr int KSTEPS = 36;       // 9 taps x 4 channel groups of 16
 
@@ -84,8 +97,12 @@ struct C64Args {
 //   bias, activation, addend, rounding, stores: ~130 vector instructions per 8 pixels x 8 channels that a single wave per
 //   SIMD had to run between its MFMAs (1.5 of 3.2 us per step), and that now issue in the shadow of the other wave's MFMAs.
 // One barrier per step orders both hand-overs (window rows: helper -> matrix waves; accumulators: matrix -> helper).
-template <int RW, int CW>
-__global__ __launch_bounds__(512) void c64_bf16_kernel(const C64Args a) {
+// T: the 16-bit type of activations, weights and addend -- __bf16 (profile name c64_bf16_kernel<RW, CW>) or _Float16
+// (c64_f16_kernel<RW, CW>: precision 3, v_mfma_f32_32x32x16_f16).  (A template parameter of the kernel itself, not a __device__
+// body behind two wrappers: inlined into a wrapper, the bf16 body came out with other registers and another schedule.)
+template <typename T, int RW, int CW>
+__global__ __launch_bounds__(512) void c64_kernel(const C64Args a) {
+  typedef typename E16<T>::v8 v8;
   static_assert(RW * CW == 4, "128 pixels per step");
   constexpr int TW = 32 * CW;                    // tile columns
   constexpr int PX = TW + 2;                     // window pixels per row (one halo pixel each side)
@@ -126,11 +143,11 @@ __global__ __launch_bounds__(512) void c64_bf16_kernel(const C64Args a) {
   if (!helper) {
     __builtin_amdgcn_s_setprio(3);  // the matrix pipe is what the step waits for: its wave wins every issue arbitration
     // ---- matrix waves: the weights of 32 output channels, 36 fragments of 8 bf16 per lane, resident for the life of the workgroup
-    bf16x8 wf[KSTEPS];
+    v8 wf[KSTEPS];
     {
       const u32x4* wp = reinterpret_cast<const u32x4*>(a.w + (size_t)g * (KSTEPS * 2 * 1024)) + nh * 64 + lane;
 #pragma unroll
-      for (int ks = 0; ks < KSTEPS; ++ks) wf[ks] = __builtin_bit_cast(bf16x8, wp[ks * 128]);
+      for (int ks = 0; ks < KSTEPS; ++ks) wf[ks] = __builtin_bit_cast(v8, wp[ks * 128]);
     }
     // the bias in accumulator layout (register r of lane l holds channel (r & 3) + 8 (r >> 2) + 4 (l >> 5) of the 32): it is the
     // C operand of each tile's first MFMA, so adding it costs no instruction anywhere
@@ -175,20 +192,20 @@ __global__ __launch_bounds__(512) void c64_bf16_kernel(const C64Args a) {
       // B fragments run PD k-steps ahead of the MFMAs that consume them (a read issued right in front of its MFMA
       // exposes the whole LDS latency every second instruction)
       constexpr int PD = 4;
-      bf16x8 b0[PD], b1[PD];
+      v8 b0[PD], b1[PD];
       auto fetch = [&](int ks, int slot) {
         const int tap = ks >> 2, th = tap / 3, tw = tap - 3 * th, cs = ks & 3;
-        b0[slot] = *reinterpret_cast<const bf16x8*>(win + foff[tw][cs] + sb0[th]);
-        b1[slot] = *reinterpret_cast<const bf16x8*>(win + foff[tw][cs] + sb1[th]);
+        b0[slot] = *reinterpret_cast<const v8*>(win + foff[tw][cs] + sb0[th]);
+        b1[slot] = *reinterpret_cast<const v8*>(win + foff[tw][cs] + sb1[th]);
       };
 #pragma unroll
       for (int ks = 0; ks < PD; ++ks) fetch(ks, ks);
 #pragma unroll
       for (int ks = 0; ks < KSTEPS; ++ks) {
-        const bf16x8 x0 = b0[ks % PD], x1 = b1[ks % PD];
+        const v8 x0 = b0[ks % PD], x1 = b1[ks % PD];
         if (ks + PD < KSTEPS) fetch(ks + PD, ks % PD);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], x0, ks == 0 ? biasv : acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], x1, ks == 0 ? biasv : acc1, 0, 0, 0);
+        acc0 = E16<T>::mfma(wf[ks], x0, ks == 0 ? biasv : acc0);
+        acc1 = E16<T>::mfma(wf[ks], x1, ks == 0 ? biasv : acc1);
       }
       // pin the issue order the loop above spells out: 2 PD reads up front, then per k-step the two reads of step
       // ks + PD in front of the two MFMAs of step ks (left alone the scheduler sinks every read to just before its MFMA)
@@ -360,7 +377,7 @@ __global__ __launch_bounds__(512) void c64_bf16_kernel(const C64Args a) {
       for (int t4 = 0; t4 < 4; ++t4) {
         const unsigned char* sp = src + (epx + 16 * t4) * EPI_PITCH + ech * 32;
         const f32x4 lo = *reinterpret_cast<const f32x4*>(sp), hi = *reinterpret_cast<const f32x4*>(sp + 16);
-        const bf16x8 radd = __builtin_bit_cast(bf16x8, rreg[t4]);
+        const v8 radd = __builtin_bit_cast(v8, rreg[t4]);
         float v[8];  // (the bias is already in: the matrix waves start their accumulators from it)
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = e < 4 ? lo[e] : hi[e - 4];
@@ -375,7 +392,7 @@ __global__ __launch_bounds__(512) void c64_bf16_kernel(const C64Args a) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] += (float)radd[e];
         }
-        const bf16x8 o = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3], (__bf16)v[4], (__bf16)v[5], (__bf16)v[6], (__bf16)v[7]};
+        const v8 o = {(T)v[0], (T)v[1], (T)v[2], (T)v[3], (T)v[4], (T)v[5], (T)v[6], (T)v[7]};
         const u32x4 od = __builtin_bit_cast(u32x4, o);
         // (an asm store: the descriptor is built by hand as four scalars, like the DMA's)
         asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen" :: "v"(od), "v"(toff[t4]), "s"((t4 >> 1) ? o1 : o0) : "memory");
@@ -437,11 +454,12 @@ __global__ __launch_bounds__(512) void c64_bf16_kernel(const C64Args a) {
   }
 }
 
-// OIHW fp32 [Cout][64][3][3] -> [group][kstep][half][lane][8] bf16: lane l of fragment (ks, nh) holds output channel
+// OIHW fp32 [Cout][64][3][3] -> [group][kstep][half][lane][8] bf16 (or fp16): lane l of fragment (ks, nh) holds output channel
 // 32 nh + (l & 31) of its group, input channels 16 (ks & 3) + 8 (l >> 5) .. + 7 of tap ks >> 2.  With PixelShuffle the group
 // g = 2 i + j collects the channels c * 4 + g (c = 0 .. 63), the ones PixelShuffle(2) moves to sub-pixel (i, j).
-__global__ void c64_pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, unsigned short* __restrict__ dst,
-                                int Cout, int shuffle) {
+template <typename T>
+__device__ __forceinline__ void c64_pack_body(const float* __restrict__ w, const float* __restrict__ scale, unsigned short* __restrict__ dst,
+                                              int Cout, int shuffle) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;  // one 8-channel fragment lane
   const int total = (Cout / 64) * KSTEPS * 2 * 64;
   if (idx >= total) return;
@@ -452,8 +470,16 @@ __global__ void c64_pack_kernel(const float* __restrict__ w, const float* __rest
   const float s = scale ? scale[co] : 1.f;
   for (int e = 0; e < 8; ++e) {
     const float v = w[((size_t)co * 64 + ci0 + e) * 9 + tap] * s;
-    dst[(size_t)idx * 8 + e] = __builtin_bit_cast(unsigned short, (__bf16)v);
+    dst[(size_t)idx * 8 + e] = __builtin_bit_cast(unsigned short, (T)v);
   }
+}
+__global__ void c64_pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, unsigned short* __restrict__ dst,
+                                int Cout, int shuffle) {
+  c64_pack_body<__bf16>(w, scale, dst, Cout, shuffle);
+}
+__global__ void c64_pack_f16_kernel(const float* __restrict__ w, const float* __restrict__ scale, unsigned short* __restrict__ dst,
+                                    int Cout, int shuffle) {
+  c64_pack_body<_Float16>(w, scale, dst, Cout, shuffle);
 }
 
 __global__ void c64_pack_bias_kernel(const float* __restrict__ b, float* __restrict__ dst, int Cout, int shuffle) {
@@ -480,10 +506,29 @@ __global__ void bf16_to_f32_kernel(const uint2* __restrict__ x, f32x4* __restric
   }
 }
 
+// fp32 <-> fp16 (the ends of the precision-3 chain): (_Float16)float rounds to nearest even (v_cvt_pk_f16_f32; NOT the
+// round-toward-zero v_cvt_pkrtz_f16_f32), beyond 65519.99.. to +-inf; fp16 -> fp32 is exact
+__global__ void f32_to_f16_kernel(const f32x4* __restrict__ x, uint2* __restrict__ y, int64_t nquads) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nquads; i += (int64_t)gridDim.x * blockDim.x) {
+    const f32x4 v = x[i];
+    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+    const f16x4 o = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+    y[i] = __builtin_bit_cast(uint2, o);
+  }
+}
+
+__global__ void f16_to_f32_kernel(const uint2* __restrict__ x, f32x4* __restrict__ y, int64_t nquads) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nquads; i += (int64_t)gridDim.x * blockDim.x) {
+    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+    const f16x4 v = __builtin_bit_cast(f16x4, x[i]);
+    y[i] = f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+  }
+}
+
 // One workgroup per CU (a wave owns its SIMD's whole register file), persistent over work items = (image, column strip,
 // row chunk).  The chunk height is chosen so that the busiest workgroup's rows -- its items x (chunk rows + the 2 halo rows
 // a chunk loads without computing) -- are fewest.
-int c64_plan(int N, int H, int W, int groups, int RW, int TW, int* rows_per_chunk, int* nchunks, int* nstrips) {
+int c64_plan(int N, int H, int W, int groups, int RW, int TW, int* rows_per_chunk, int* nchunks, int* nstrips, const char* fn) {
   const int cus = srx_plan_cus();
   const int gx_max = std::max(1, cus / groups);
   const int strips = (int)srx_cdiv(W, TW);
@@ -503,7 +548,7 @@ int c64_plan(int N, int H, int W, int groups, int RW, int TW, int* rows_per_chun
   // groups of RW rows ahead, plus the row above / below): the whole span must stay below 4 GiB, or offsets wrap silently
   // and rows above the image stop failing the descriptor's range check.  Shorter chunks cost time only.
   const int64_t span_rows = (int64_t)(1LL << 32) / ((int64_t)W * 128) - (2 + 3 * RW + 1);
-  if (span_rows < RW) SRX_FAIL(SRX_E_UNSUPPORTED, "conv3x3_c64_bf16_fwd: image rows of %d pixels are too long for 32-bit offsets inside a chunk", W);
+  if (span_rows < RW) SRX_FAIL(SRX_E_UNSUPPORTED, "%s: image rows of %d pixels are too long for 32-bit offsets inside a chunk", fn, W);
   if (best_rpc > span_rows) best_rpc = (int)(span_rows / RW) * RW;
   *rows_per_chunk = best_rpc;
   *nchunks = (int)srx_cdiv(H, best_rpc);
@@ -511,23 +556,26 @@ int c64_plan(int N, int H, int W, int groups, int RW, int TW, int* rows_per_chun
   return SRX_OK;
 }
 
-template <int RW, int CW>
+template <typename T, int RW, int CW>
 int launch_c64(C64Args& a, int groups, hipStream_t st) {
   constexpr int TW = 32 * CW, NR = RW == 1 ? 4 : 3 * RW;
+  constexpr bool F16 = std::is_same<T, _Float16>::value;
+  constexpr auto kernel = &c64_kernel<T, RW, CW>;
+  const char* kname = F16 ? "c64_f16_kernel" : "c64_bf16_kernel";
   const size_t lds = (size_t)NR * (TW + 2) * 128 + 4 * 2 * 64 * EPI_PITCH + 4 * 4096;
   static std::once_flag once;
   std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&c64_bf16_kernel<RW, CW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   });
   const int gx_max = std::max(1, srx_plan_cus() / groups);
-  if (int rc = c64_plan(a.N, a.H, a.W, groups, RW, TW, &a.rows_per_chunk, &a.chunks, &a.strips)) return rc;
+  if (int rc = c64_plan(a.N, a.H, a.W, groups, RW, TW, &a.rows_per_chunk, &a.chunks, &a.strips,
+                       F16 ? "conv3x3_c64_f16_fwd" : "conv3x3_c64_bf16_fwd")) return rc;
   a.nwork = (int)((int64_t)a.N * a.strips * a.chunks);
   const int gx = std::min(a.nwork, gx_max);
   char nm[112];
-  if (srx_prof_on()) snprintf(nm, sizeof(nm), "c64_bf16_kernel<%d, %d> MxNxK=%lldx%dx576", RW, CW, (long long)a.N * a.H * a.W, 64 * groups);
-  SRX_LAUNCH_PROF(nm, 2.0 * a.N * a.H * a.W * 64.0 * groups * 576.0, (c64_bf16_kernel<RW, CW>), dim3((unsigned)gx, (unsigned)groups),
-                  dim3(512), lds, st, a);
-  SRX_CHECK_LAUNCH("c64_bf16_kernel");
+  if (srx_prof_on()) snprintf(nm, sizeof(nm), "%s<%d, %d> MxNxK=%lldx%dx576", kname, RW, CW, (long long)a.N * a.H * a.W, 64 * groups);
+  SRX_LAUNCH_PROF(nm, 2.0 * a.N * a.H * a.W * 64.0 * groups * 576.0, kernel, dim3((unsigned)gx, (unsigned)groups), dim3(512), lds, st, a);
+  SRX_CHECK_LAUNCH(kname);
   return SRX_OK;
 }
 
@@ -537,35 +585,49 @@ extern "C" size_t srx_conv3x3_c64_bf16_packed_bytes(int Cout) {
   return Cout > 0 && Cout % 64 == 0 ? (size_t)(Cout / 64) * KSTEPS * 2 * 1024 + (size_t)Cout * sizeof(float) : 0;
 }
 
-extern "C" int srx_conv3x3_c64_bf16_pack(const float* w, const float* bias, const float* out_scale, int Cout, int shuffle,
-                                         void* wpk, void* stream) {
+static int c64_pack_impl(const float* w, const float* bias, const float* out_scale, int Cout, int shuffle, void* wpk, void* stream,
+                         bool f16) {
+  const char* fn = f16 ? "conv3x3_c64_f16_pack" : "conv3x3_c64_bf16_pack";
   SRX_REQUIRE(w && wpk && Cout > 0 && Cout % 64 == 0 && (shuffle == 0 || (shuffle == 2 && Cout == 256)),
-              "conv3x3_c64_bf16_pack: Cout must be a multiple of 64 (256 with PixelShuffle 2)");
+              "%s: Cout must be a multiple of 64 (256 with PixelShuffle 2)", fn);
   hipStream_t st = srx_stream(stream);
   const int total = (Cout / 64) * KSTEPS * 2 * 64;
-  hipLaunchKernelGGL(c64_pack_kernel, dim3((unsigned)srx_cdiv(total, 256)), dim3(256), 0, st, w, out_scale,
+  hipLaunchKernelGGL(f16 ? c64_pack_f16_kernel : c64_pack_kernel, dim3((unsigned)srx_cdiv(total, 256)), dim3(256), 0, st, w, out_scale,
                      static_cast<unsigned short*>(wpk), Cout, shuffle);
-  SRX_CHECK_LAUNCH("c64_pack_kernel");
+  SRX_CHECK_LAUNCH(f16 ? "c64_pack_f16_kernel" : "c64_pack_kernel");
   float* bdst = reinterpret_cast<float*>(static_cast<unsigned char*>(wpk) + (size_t)(Cout / 64) * KSTEPS * 2 * 1024);
   if (bias) {
     hipLaunchKernelGGL(c64_pack_bias_kernel, dim3((unsigned)srx_cdiv(Cout, 256)), dim3(256), 0, st, bias, bdst, Cout, shuffle);
     SRX_CHECK_LAUNCH("c64_pack_bias_kernel");
   } else if (hipMemsetAsync(bdst, 0, (size_t)Cout * sizeof(float), st) != hipSuccess) {
-    SRX_FAIL(SRX_E_HIP, "conv3x3_c64_bf16_pack: memset failed");
+    SRX_FAIL(SRX_E_HIP, "%s: memset failed", fn);
   }
   return SRX_OK;
 }
 
+extern "C" int srx_conv3x3_c64_bf16_pack(const float* w, const float* bias, const float* out_scale, int Cout, int shuffle,
+                                         void* wpk, void* stream) {
+  return c64_pack_impl(w, bias, out_scale, Cout, shuffle, wpk, stream, false);
+}
+
+extern "C" size_t srx_conv3x3_c64_f16_packed_bytes(int Cout) { return srx_conv3x3_c64_bf16_packed_bytes(Cout); }
+
+extern "C" int srx_conv3x3_c64_f16_pack(const float* w, const float* bias, const float* out_scale, int Cout, int shuffle,
+                                        void* wpk, void* stream) {
+  return c64_pack_impl(w, bias, out_scale, Cout, shuffle, wpk, stream, true);
+}
+
 static int c64_fwd_impl(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk, float slope,
-                        const void* residual, void* y, int y_cs, void* stream, unsigned* dbg) {
-  SRX_REQUIRE(x && wpk && y, "conv3x3_c64_bf16_fwd: null pointer");
-  SRX_REQUIRE(N > 0 && H > 0 && W > 0 && Cout > 0 && Cout % 64 == 0 && Cout <= 1024, "conv3x3_c64_bf16_fwd: bad size (Cout a multiple of 64)");
-  SRX_REQUIRE(shuffle == 0 || (shuffle == 2 && Cout == 256), "conv3x3_c64_bf16_fwd: PixelShuffle(2) needs Cout = 256");
-  SRX_REQUIRE(y_cs % 8 == 0 && y_cs >= (shuffle ? 64 : Cout), "conv3x3_c64_bf16_fwd: the output's channel stride must hold its channels in whole 16-byte chunks");
-  SRX_REQUIRE(!residual || (!shuffle && residual != y), "conv3x3_c64_bf16_fwd: the addend is a tensor of its own, without PixelShuffle");
-  SRX_REQUIRE(x != y, "conv3x3_c64_bf16_fwd: in place is not possible (neighbouring tiles read their halo)");
+                        const void* residual, void* y, int y_cs, void* stream, unsigned* dbg, bool f16 = false) {
+  const char* fn = f16 ? "conv3x3_c64_f16_fwd" : "conv3x3_c64_bf16_fwd";
+  SRX_REQUIRE(x && wpk && y, "%s: null pointer", fn);
+  SRX_REQUIRE(N > 0 && H > 0 && W > 0 && Cout > 0 && Cout % 64 == 0 && Cout <= 1024, "%s: bad size (Cout a multiple of 64)", fn);
+  SRX_REQUIRE(shuffle == 0 || (shuffle == 2 && Cout == 256), "%s: PixelShuffle(2) needs Cout = 256", fn);
+  SRX_REQUIRE(y_cs % 8 == 0 && y_cs >= (shuffle ? 64 : Cout), "%s: the output's channel stride must hold its channels in whole 16-byte chunks", fn);
+  SRX_REQUIRE(!residual || (!shuffle && residual != y), "%s: the addend is a tensor of its own, without PixelShuffle", fn);
+  SRX_REQUIRE(x != y, "%s: in place is not possible (neighbouring tiles read their halo)", fn);
   SRX_REQUIRE((int64_t)W * 128 * 130 < (1LL << 32) && (int64_t)(shuffle ? 2 : 1) * W * y_cs * 2 < (1LL << 32) && (int64_t)N * H * W < (1LL << 31),
-              "conv3x3_c64_bf16_fwd: image rows too long for 32-bit offsets inside a chunk");
+              "%s: image rows too long for 32-bit offsets inside a chunk", fn);
   C64Args a{};
   a.x = static_cast<const unsigned char*>(x);
   a.w = static_cast<const unsigned char*>(wpk);
@@ -578,9 +640,14 @@ static int c64_fwd_impl(int N, int H, int W, int Cout, int shuffle, const void* 
   hipStream_t st = srx_stream(stream);
   const int groups = Cout / 64;
   // narrow images: waves take rows instead of column segments
-  if (W <= 32) return launch_c64<4, 1>(a, groups, st);
-  if (W <= 64) return launch_c64<2, 2>(a, groups, st);
-  return launch_c64<1, 4>(a, groups, st);
+  if (f16) {
+    if (W <= 32) return launch_c64<_Float16, 4, 1>(a, groups, st);
+    if (W <= 64) return launch_c64<_Float16, 2, 2>(a, groups, st);
+    return launch_c64<_Float16, 1, 4>(a, groups, st);
+  }
+  if (W <= 32) return launch_c64<__bf16, 4, 1>(a, groups, st);
+  if (W <= 64) return launch_c64<__bf16, 2, 2>(a, groups, st);
+  return launch_c64<__bf16, 1, 4>(a, groups, st);
 }
 
 // out[3] = {rows per chunk, chunks per column strip, column strips} of the launch srx_conv3x3_c64_bf16_fwd would make (host only)
@@ -588,12 +655,17 @@ extern "C" int srx_conv3x3_c64_bf16_plan(int N, int H, int W, int Cout, int* out
   SRX_REQUIRE(out && N > 0 && H > 0 && W > 0 && Cout > 0 && Cout % 64 == 0, "conv3x3_c64_bf16_plan: bad argument");
   SRX_REQUIRE((int64_t)W * 128 * 130 < (1LL << 32) && (int64_t)N * H * W < (1LL << 31), "conv3x3_c64_bf16_plan: image rows too long for 32-bit offsets inside a chunk");
   const int RW = W <= 32 ? 4 : (W <= 64 ? 2 : 1), CW = W <= 32 ? 1 : (W <= 64 ? 2 : 4);
-  return c64_plan(N, H, W, Cout / 64, RW, 32 * CW, out, out + 1, out + 2);
+  return c64_plan(N, H, W, Cout / 64, RW, 32 * CW, out, out + 1, out + 2, "conv3x3_c64_bf16_plan");
 }
 
 extern "C" int srx_conv3x3_c64_bf16_fwd(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk, float slope,
                                         const void* residual, void* y, int y_cs, void* stream) {
   return c64_fwd_impl(N, H, W, Cout, shuffle, x, wpk, slope, residual, y, y_cs, stream, nullptr);
+}
+
+extern "C" int srx_conv3x3_c64_f16_fwd(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk, float slope,
+                                       const void* residual, void* y, int y_cs, void* stream) {
+  return c64_fwd_impl(N, H, W, Cout, shuffle, x, wpk, slope, residual, y, y_cs, stream, nullptr, true);
 }
 
 // Developer aid (tools/bench_c64.py stamps): the same launch with in-kernel cycle stamps; dbg: 256 x 4 (workgroups) x 8 (waves) x 8
@@ -620,5 +692,23 @@ extern "C" int srx_bf16_to_f32(const void* x, float* y, int64_t n, void* stream)
   hipLaunchKernelGGL(bf16_to_f32_kernel, dim3((unsigned)std::min<int64_t>(srx_cdiv(q, 256), 8192)), dim3(256), 0, srx_stream(stream),
                      static_cast<const uint2*>(x), reinterpret_cast<f32x4*>(y), q);
   SRX_CHECK_LAUNCH("bf16_to_f32_kernel");
+  return SRX_OK;
+}
+
+extern "C" int srx_f32_to_f16(const float* x, void* y, int64_t n, void* stream) {
+  SRX_REQUIRE(x && y && n > 0 && n % 4 == 0, "f32_to_f16: a positive multiple of 4 elements");
+  const int64_t q = n / 4;
+  hipLaunchKernelGGL(f32_to_f16_kernel, dim3((unsigned)std::min<int64_t>(srx_cdiv(q, 256), 8192)), dim3(256), 0, srx_stream(stream),
+                     reinterpret_cast<const f32x4*>(x), static_cast<uint2*>(y), q);
+  SRX_CHECK_LAUNCH("f32_to_f16_kernel");
+  return SRX_OK;
+}
+
+extern "C" int srx_f16_to_f32(const void* x, float* y, int64_t n, void* stream) {
+  SRX_REQUIRE(x && y && n > 0 && n % 4 == 0, "f16_to_f32: a positive multiple of 4 elements");
+  const int64_t q = n / 4;
+  hipLaunchKernelGGL(f16_to_f32_kernel, dim3((unsigned)std::min<int64_t>(srx_cdiv(q, 256), 8192)), dim3(256), 0, srx_stream(stream),
+                     static_cast<const uint2*>(x), reinterpret_cast<f32x4*>(y), q);
+  SRX_CHECK_LAUNCH("f16_to_f32_kernel");
   return SRX_OK;
 }

@@ -110,8 +110,9 @@ template <int BM, int BN, int WM, int WN, int KS, int XR, int PR, int UP = 0, in
 __device__ __forceinline__ void gconv_body(const GArgs& a, const int bid) {
   static_assert(XR == 0 || (XR == 16 && KS == 1), "extra rows: 16, without the in-workgroup K split");
   static_assert(PR == 0 || XR == 0, "the 16-row extension is fp32 only");
-  constexpr int BKL = PR == 1 ? BK / 2 : BK;  // floats per LDS row
-  constexpr int NS = PR == 1 ? 2 : 4;         // MFMA sub-steps per chunk
+  constexpr bool H16 = PR == 1 || PR == 3;  // 16-bit products of fp32-stored tensors: bf16 (PR = 1) or fp16 (PR = 3)
+  constexpr int BKL = H16 ? BK / 2 : BK;  // floats per LDS row
+  constexpr int NS = H16 ? 2 : 4;         // MFMA sub-steps per chunk
   constexpr int BMT = BM + XR;  // rows of the tile
   constexpr int TM = WM / 32, TN = WN / 32;
   constexpr int WAVES_N = BN / WN;
@@ -280,9 +281,13 @@ __device__ __forceinline__ void gconv_body(const GArgs& a, const int bid) {
   };
   // fp32: 16-byte quad q of the row at quad q ^ ((row>>1)&7).  bf16: the quad shrinks to 8 bytes; quads 2g, 2g+1
   // form the 16-byte group g (k = 8g..8g+7, one MFMA operand), stored at group g ^ ((row>>2)&3).
-  const int wchunk = PR == 1 ? (((q >> 1) ^ ((r0 >> 2) & 3)) * 4 + (q & 1) * 2) : (q ^ ((r0 >> 1) & 7)) * 4;
+  const int wchunk = H16 ? (((q >> 1) ^ ((r0 >> 2) & 3)) * 4 + (q & 1) * 2) : (q ^ ((r0 >> 1) & 7)) * 4;
   auto put = [&](float* dst, const f32x4& v) {
-    if (PR == 1) {
+    if (PR == 3) {  // fp16 products (inference, the 3-channel input conv): the same layout, rounded to fp16
+      typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+      const f16x2 lo = {(_Float16)v[0], (_Float16)v[1]}, hi = {(_Float16)v[2], (_Float16)v[3]};
+      *reinterpret_cast<uint2*>(dst) = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
+    } else if (PR == 1) {
       typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
       const bf16x2 lo = {(__bf16)v[0], (__bf16)v[1]}, hi = {(__bf16)v[2], (__bf16)v[3]};
       *reinterpret_cast<uint2*>(dst) = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
@@ -302,7 +307,7 @@ __device__ __forceinline__ void gconv_body(const GArgs& a, const int bid) {
   };
 
   const int h = lane >> 5, l31 = lane & 31;
-  const int xr = PR == 1 ? (l31 >> 2) & 3 : (l31 >> 1) & 7;
+  const int xr = H16 ? (l31 >> 2) & 3 : (l31 >> 1) & 7;
   const int arow = (wm * WM + l31) * BKL, brow = (wn * WN + l31) * BKL;
   // extra 16 rows: wave w < BN/16 owns the 16x16 block of columns 16w..16w+15
   //   v_mfma_f32_16x16x4_f32: A[i = l&15][k = l>>4], B[k = l>>4][j = l&15], D: col = l&15, row = 4(l>>4) + reg
@@ -334,6 +339,17 @@ __device__ __forceinline__ void gconv_body(const GArgs& a, const int bid) {
   };
   auto mma = [&](int set) {
     __builtin_amdgcn_s_setprio(1);
+    if (PR == 3) {
+      typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, af[set][i]),
+                                                             __builtin_bit_cast(f16x8, bf[set][j]), acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+      return;
+    }
     if (PR) {  // (PR = 2: a 16-byte quad of the stored tensor IS eight bf16 k-values, one MFMA operand)
       typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #pragma unroll
@@ -2045,8 +2061,10 @@ int check_desc(const srx_conv2d_t* d) {
     SRX_REQUIRE(d->Cout_s >= d->Cout && d->Cout_s % 4 == 0, "conv2d: Cout_s must be a multiple of 4 and >= Cout");
   }
   SRX_REQUIRE(d->act == SRX_ACT_NONE || d->act == SRX_ACT_RELU || d->act == SRX_ACT_LRELU, "conv2d: bad act");
-  SRX_REQUIRE(d->precision == 0 || d->precision == 1 || (d->precision == 2 && srx_thin_fwd_applicable(d)),
-              "conv2d: precision must be 0 (fp32), 1 (bf16 products) or, for the forward of a 64 -> <= 4 channel layer, 2 (bf16 products there too)");
+  SRX_REQUIRE(d->precision == 0 || d->precision == 1 || (d->precision == 2 && srx_thin_fwd_applicable(d)) ||
+                  (d->precision == 3 && d->Cin_s == 4 && !d->shuffle && d->up != 2),
+              "conv2d: precision must be 0 (fp32), 1 (bf16 products) or, for the forward of a 64 -> <= 4 channel layer, 2 (bf16 products there too), "
+              "or, for the forward of a <= 4-channel input layer, 3 (fp16 products)");
   const int uf = d->up == 2 ? 2 : 1;
   const int Ho = (uf * d->H + 2 * d->pad - d->KH) / d->stride + 1, Wo = (uf * d->W + 2 * d->pad - d->KW) / d->stride + 1;
   SRX_REQUIRE(Ho > 0 && Wo > 0, "conv2d: empty output");
@@ -2248,7 +2266,7 @@ size_t plan_ws_floats(const Plan& p) { return p.split > 1 ? (size_t)p.tail * p.s
 template <int BM, int BN, int WM, int WN, int KS, int XR, int PR = 0, int BIG = 0>
 int launch_gconv(const GArgs& a, const Plan& p, hipStream_t st) {
   const int ktab_chunks = p.full > 0 || p.split == 1 ? a.kchunks : p.kc_per_split;
-  const size_t lds = (size_t)(KS * 3 * (BM + XR + BN) * BK) * (PR == 1 ? 2 : 4) + (size_t)ktab_chunks * 8 * sizeof(int2);
+  const size_t lds = (size_t)(KS * 3 * (BM + XR + BN) * BK) * (PR == 1 || PR == 3 ? 2 : 4) + (size_t)ktab_chunks * 8 * sizeof(int2);
   if (lds > 160 * 1024) SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: K range needs %zu bytes of LDS", lds);
   static std::once_flag once;
   std::call_once(once, [] {
@@ -2530,7 +2548,11 @@ int run_gconv(GArgs& a, const Plan& p, float* ws, size_t ws_floats, hipStream_t 
   a.ws = ws;
   if (a.big) {  // whole-frame calls: three tiles, no K split (plans made with `big` ask for nothing else)
     if (p.split > 1) SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: internal: split plan on a call above 2^24 pixels");
-    if (precision) {
+    if (precision == 3) {
+      if (p.BM == 128 && p.BN == 128) return launch_gconv<128, 128, 64, 32, 1, 0, 3, 1>(a, p, st);
+      if (p.BM == 128 && p.BN == 64) return launch_gconv<128, 64, 32, 32, 1, 0, 3, 1>(a, p, st);
+      if (p.BM == 128 && p.BN == 32) return launch_gconv<128, 32, 32, 32, 1, 0, 3, 1>(a, p, st);
+    } else if (precision) {
       if (p.BM == 128 && p.BN == 128) return launch_gconv<128, 128, 64, 32, 1, 0, 1, 1>(a, p, st);
       if (p.BM == 128 && p.BN == 64) return launch_gconv<128, 64, 32, 32, 1, 0, 1, 1>(a, p, st);
       if (p.BM == 128 && p.BN == 32) return launch_gconv<128, 32, 32, 32, 1, 0, 1, 1>(a, p, st);
@@ -2548,6 +2570,16 @@ int run_gconv(GArgs& a, const Plan& p, float* ws, size_t ws_floats, hipStream_t 
     if (p.BM == 64 && p.BN == 64)
       return p.ks == 2 ? launch_gconv<64, 64, 32, 32, 2, 0, 2>(a, p, st) : launch_gconv<64, 64, 32, 32, 1, 0, 2>(a, p, st);
     SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: no bf16-storage kernel for tile %dx%d", p.BM, p.BN);
+  }
+  if (precision == 3) {  // fp16 products (the input conv of fp16 inference; plans made with `bf16 = true`: same tiles as below)
+    if (p.BM == 256 && p.BN == 128) return launch_gconv<256, 128, 64, 64, 1, 0, 3>(a, p, st);
+    if (p.BM == 128 && p.BN == 128) return launch_gconv<128, 128, 64, 32, 1, 0, 3>(a, p, st);
+    if (p.BM == 128 && p.BN == 64) return launch_gconv<128, 64, 32, 32, 1, 0, 3>(a, p, st);
+    if (p.BM == 64 && p.BN == 64)
+      return p.ks == 2 ? launch_gconv<64, 64, 32, 32, 2, 0, 3>(a, p, st) : launch_gconv<64, 64, 32, 32, 1, 0, 3>(a, p, st);
+    if (p.BM == 128 && p.BN == 32) return launch_gconv<128, 32, 32, 32, 1, 0, 3>(a, p, st);
+    if (p.BM == 64 && p.BN == 32) return launch_gconv<64, 32, 32, 32, 4, 0, 3>(a, p, st);
+    SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: no fp16 kernel for tile %dx%d", p.BM, p.BN);
   }
   if (precision) {  // bf16 products (plans made with `bf16 = true` never ask for the 144-row tiles)
     if (p.BM == 256 && p.BN == 128) return launch_gconv<256, 128, 64, 64, 1, 0, 1>(a, p, st);
@@ -2991,7 +3023,7 @@ static int conv_fwd_impl(const srx_conv2d_t* d, const float* x, const float* wpk
   if (residual && d->shuffle) SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_fwd: residual with PixelShuffle is not implemented");
   hipStream_t st = srx_stream(stream);
   if (srx_thin_fwd_applicable(d) && !bn_partials && !residual && d->up != 2) return srx_thin_fwd(d, x, wpk, bias, y, d->Cout, st);
-  if (srx_first3_fwd_applicable(d) && !bn_partials && !residual && d->act != SRX_ACT_PRELU)
+  if (srx_first3_fwd_applicable(d) && d->precision != 3 && !bn_partials && !residual && d->act != SRX_ACT_PRELU)
     return srx_first3_fwd(d, x, wpk, fwd_geo(d).Kp, bias, y, st);
   if (srx_rt36_applicable(d) && out_scale == 1.f)
     return srx_rt36_run(d, x, wpk, bias, residual, y, bn_partials, d->act, d->slope, st);
@@ -3056,6 +3088,7 @@ static int conv_bwd_data_impl(const srx_conv2d_t* d, const float* dy, const floa
                               void* stream, const float* addend = nullptr, int addend_ld = 0, int addend_channels = 0,
                               float addend_scale = 1.f, float out_scale = 1.f) {
   if (int rc = check_desc(d)) return rc;
+  SRX_REQUIRE(d->precision != 3, "conv2d: precision 3 (fp16 products) is forward-only");
   SRX_REQUIRE(dy && wpk_bwd && dx, "conv2d_bwd_data: null pointer");
   SRX_REQUIRE(d->stride <= 4, "conv2d_bwd_data: stride > 4 unsupported");
   if (addend_ld == 0) addend_ld = d->Cin_s;
@@ -3199,6 +3232,7 @@ extern "C" int srx_conv2d_bwd_data_bn(const srx_conv2d_t* d, const float* dy, co
                                       const float* bn_y, const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
                                       const float* bn_beta, const float* bn_prelu, float* table, void* stream) {
   if (int rc = check_desc(d)) return rc;
+  SRX_REQUIRE(d->precision != 3, "conv2d: precision 3 (fp16 products) is forward-only");
   SRX_REQUIRE(dy && wpk_bwd && dx && bn_y && bn_mean && bn_invstd && bn_gamma && bn_beta && table, "conv2d_bwd_data_bn: null pointer");
   SRX_REQUIRE(!addend || addend != dx, "conv2d_bwd_data_bn: the addend must be a tensor of its own");
   if (srx_conv2d_bwd_data_bn_rows(d) == 0)
@@ -3224,6 +3258,7 @@ extern "C" int srx_conv2d_bwd_data_bn_in(const srx_conv2d_t* d, const float* dou
                                          const float* bn_y, const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
                                          const float* bn_beta, const float* bn_prelu, float* table, void* stream) {
   if (int rc = check_desc(d)) return rc;
+  SRX_REQUIRE(d->precision != 3, "conv2d: precision 3 (fp16 products) is forward-only");
   SRX_REQUIRE(dout && in_y && in_mean && in_invstd && in_gamma && in_beta && in_sums && dy_out && wpk_bwd && dx,
               "conv2d_bwd_data_bn_in: null pointer");
   SRX_REQUIRE(dy_out != dout && dy_out != dx && dx != dout && (!addend || addend != dx), "conv2d_bwd_data_bn_in: dout, dy_out, dx and the addend must be tensors of their own");
@@ -3315,6 +3350,7 @@ static int wgrad_multi_impl(const srx_conv2d_t* d, int nprob, int per_out, const
                             float* const* dws_hi, float* const* dbs_hi, int cin_lo, float* ws, size_t ws_floats,
                             void* stream) {
   if (int rc = check_desc(d)) return rc;
+  SRX_REQUIRE(d->precision != 3, "conv2d: precision 3 (fp16 products) is forward-only");
   SRX_REQUIRE(nprob >= 1 && nprob <= WG_MAXP && per_out >= 1 && nprob % per_out == 0,
               "conv2d_bwd_weight_multi: 1..%d problems, a whole number of outputs", WG_MAXP);
   SRX_REQUIRE(xs && dys && dws && ws, "conv2d_bwd_weight: null pointer");

@@ -24,7 +24,19 @@
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// the input's (and the packed weights') 16-bit type: bf16, or fp16 (precision 3); both 32x32x16 MFMAs take the same cycles
+template <typename T> struct E16;
+template <> struct E16<__bf16> {
+  typedef bf16x8 v8;
+  static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <> struct E16<_Float16> {
+  typedef f16x8 v8;
+  static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
 
 constexpr int KSTEPS = 36;          // 9 column taps x 4 channel groups of 16
 constexpr int TW = 128, PX = TW + 8;  // output columns per strip; window pixels per row (4 halo pixels each side)
@@ -44,14 +56,17 @@ __device__ __forceinline__ void dma16(const u32x4& rsrc, unsigned voff, unsigned
 }
 
 struct T9Args {
-  const unsigned char* x;   // bf16 NHWC [N][H][W][64]
-  const unsigned char* w;   // packed: [kstep 36][lane 64][8 bf16], then 4 floats of bias
+  const unsigned char* x;   // bf16 (fp16) NHWC [N][H][W][64]
+  const unsigned char* w;   // packed: [kstep 36][lane 64][8 bf16 (fp16)], then 4 floats of bias
   float* out;               // fp32 [N][H][W][4]
   int N, H, W;
   int strips, chunks, rows_per_chunk, nwork;
 };
 
-__global__ __launch_bounds__(512) void t9_bf16_kernel(const T9Args a) {
+// T = __bf16 (profile name t9_bf16_kernel) or _Float16 (t9_f16_kernel: precision 3, fp16 products, fp32 sums and output)
+template <typename T>
+__global__ __launch_bounds__(512) void t9_kernel(const T9Args a) {
+  typedef typename E16<T>::v8 v8;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x & 255, lane = tid & 63;
   const int wave = srx_uniform((int)threadIdx.x >> 6);
@@ -68,11 +83,11 @@ __global__ __launch_bounds__(512) void t9_bf16_kernel(const T9Args a) {
   // add the partial rows of step k - 1 into the output ring.  Both roles run the same barriers: A per item, B_k per step.
   if (!helper) {
     __builtin_amdgcn_s_setprio(3);
-    bf16x8 wf[KSTEPS];
+    v8 wf[KSTEPS];
     {
       const u32x4* wp = reinterpret_cast<const u32x4*>(a.w) + lane;
 #pragma unroll
-      for (int ks = 0; ks < KSTEPS; ++ks) wf[ks] = __builtin_bit_cast(bf16x8, wp[ks * 64]);
+      for (int ks = 0; ks < KSTEPS; ++ks) wf[ks] = __builtin_bit_cast(v8, wp[ks * 64]);
     }
     // window offsets of the B fragments: pixel 32 w4 + l31 + kw (column c0 - 4 + pixel), chunk (2 cs + h) ^ swizzle(pixel);
     // the channel group flips bits 5..6 of the offset: one register per column tap, one v_xor per fragment
@@ -96,21 +111,21 @@ __global__ __launch_bounds__(512) void t9_bf16_kernel(const T9Args a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
         constexpr int PD = 3;
-        bf16x8 b0[PD], b1[PD];
+        v8 b0[PD], b1[PD];
         auto fetch = [&](int ks, int slot) {
           const int kw = ks >> 2, cs = ks & 3;
           const unsigned off = fbase[kw] ^ (unsigned)(cs << 5);
-          b0[slot] = *reinterpret_cast<const bf16x8*>(win + sb0 + off);
-          b1[slot] = *reinterpret_cast<const bf16x8*>(win + sb1 + off);
+          b0[slot] = *reinterpret_cast<const v8*>(win + sb0 + off);
+          b1[slot] = *reinterpret_cast<const v8*>(win + sb1 + off);
         };
 #pragma unroll
         for (int ks = 0; ks < PD; ++ks) fetch(ks, ks);
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ++ks) {
-          const bf16x8 x0 = b0[ks % PD], x1 = b1[ks % PD];
+          const v8 x0 = b0[ks % PD], x1 = b1[ks % PD];
           if (ks + PD < KSTEPS) fetch(ks + PD, ks % PD);
-          acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], x0, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], x1, acc1, 0, 0, 0);
+          acc0 = E16<T>::mfma(wf[ks], x0, acc0);
+          acc1 = E16<T>::mfma(wf[ks], x1, acc1);
         }
         __builtin_amdgcn_sched_group_barrier(0x100, 2 * PD, 0);
 #pragma unroll
@@ -250,6 +265,8 @@ __global__ __launch_bounds__(512) void t9_bf16_kernel(const T9Args a) {
 
 // OIHW fp32 [Cout <= 3][64][9][9] (+ bias) -> [kstep = kw * 4 + cs][lane][8 bf16]: lane l holds MFMA row (l & 31) = kh * 3 + c
 // (rows >= 27 and channels >= Cout: zero), input channels 16 cs + 8 (l >> 5) .. + 7 of column tap kw; then the bias as 4 floats.
+// (T = _Float16: the same layout in fp16.)
+template <typename T>
 __global__ void t9_pack_kernel(const float* __restrict__ w, const float* __restrict__ bias, unsigned char* __restrict__ dst, int Cout) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx < 4) reinterpret_cast<float*>(dst + KSTEPS * 1024)[idx] = (bias && idx < Cout) ? bias[idx] : 0.f;
@@ -261,7 +278,7 @@ __global__ void t9_pack_kernel(const float* __restrict__ w, const float* __restr
   for (int e = 0; e < 8; ++e) {
     float v = 0.f;
     if (row < 27 && c < Cout) v = w[(((size_t)c * 64 + ci0 + e) * 9 + kh) * 9 + kw];
-    d[e] = __builtin_bit_cast(unsigned short, (__bf16)v);
+    d[e] = __builtin_bit_cast(unsigned short, (T)v);
   }
 }
 
@@ -269,23 +286,36 @@ __global__ void t9_pack_kernel(const float* __restrict__ w, const float* __restr
 
 extern "C" size_t srx_conv9x9_c64_thin_bf16_packed_bytes(void) { return (size_t)KSTEPS * 1024 + 16; }
 
-extern "C" int srx_conv9x9_c64_thin_bf16_pack(const float* w, const float* bias, int Cout, void* wpk, void* stream) {
-  SRX_REQUIRE(w && wpk && Cout >= 1 && Cout <= 3, "conv9x9_c64_thin_bf16_pack: 1..3 output channels");
-  hipLaunchKernelGGL(t9_pack_kernel, dim3((unsigned)srx_cdiv(KSTEPS * 64, 256)), dim3(256), 0, srx_stream(stream), w, bias,
-                     static_cast<unsigned char*>(wpk), Cout);
+static int t9_pack_impl(const float* w, const float* bias, int Cout, void* wpk, void* stream, bool f16) {
+  SRX_REQUIRE(w && wpk && Cout >= 1 && Cout <= 3, "%s: 1..3 output channels", f16 ? "conv9x9_c64_thin_f16_pack" : "conv9x9_c64_thin_bf16_pack");
+  hipLaunchKernelGGL(f16 ? t9_pack_kernel<_Float16> : t9_pack_kernel<__bf16>, dim3((unsigned)srx_cdiv(KSTEPS * 64, 256)), dim3(256), 0, srx_stream(stream), w,
+                     bias, static_cast<unsigned char*>(wpk), Cout);
   SRX_CHECK_LAUNCH("t9_pack_kernel");
   return SRX_OK;
 }
 
-extern "C" int srx_conv9x9_c64_thin_bf16_fwd(int N, int H, int W, const void* x, const void* wpk, float* y, void* stream) {
-  SRX_REQUIRE(x && wpk && y && N > 0 && H > 0 && W > 0, "conv9x9_c64_thin_bf16_fwd: bad argument");
-  SRX_REQUIRE((int64_t)W * 128 * 140 < (1LL << 32) && (int64_t)N * H < (1LL << 31), "conv9x9_c64_thin_bf16_fwd: image rows too long for 32-bit offsets inside a chunk");
+extern "C" int srx_conv9x9_c64_thin_bf16_pack(const float* w, const float* bias, int Cout, void* wpk, void* stream) {
+  return t9_pack_impl(w, bias, Cout, wpk, stream, false);
+}
+
+extern "C" size_t srx_conv9x9_c64_thin_f16_packed_bytes(void) { return srx_conv9x9_c64_thin_bf16_packed_bytes(); }
+
+extern "C" int srx_conv9x9_c64_thin_f16_pack(const float* w, const float* bias, int Cout, void* wpk, void* stream) {
+  return t9_pack_impl(w, bias, Cout, wpk, stream, true);
+}
+
+template <typename T>
+static int t9_fwd_impl(int N, int H, int W, const void* x, const void* wpk, float* y, void* stream) {
+  constexpr bool F16 = std::is_same<T, _Float16>::value;
+  const char* fn = F16 ? "conv9x9_c64_thin_f16_fwd" : "conv9x9_c64_thin_bf16_fwd";
+  SRX_REQUIRE(x && wpk && y && N > 0 && H > 0 && W > 0, "%s: bad argument", fn);
+  SRX_REQUIRE((int64_t)W * 128 * 140 < (1LL << 32) && (int64_t)N * H < (1LL << 31), "%s: image rows too long for 32-bit offsets inside a chunk", fn);
   T9Args a{};
   a.x = static_cast<const unsigned char*>(x); a.w = static_cast<const unsigned char*>(wpk); a.out = y;
   a.N = N; a.H = H; a.W = W;
   static std::once_flag once;
   std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&t9_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&t9_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   });
   // one workgroup per CU, persistent; a chunk re-reads 8 input rows: keep chunks long, and as many items as CUs (x k)
   const int cus = srx_plan_cus();
@@ -302,7 +332,7 @@ extern "C" int srx_conv9x9_c64_thin_bf16_fwd(int N, int H, int W, const void* x,
   }
   {  // 32-bit byte offsets inside a chunk (rows_per_chunk + the 8-row window + the rows in flight): see c64.hip
     const int64_t span_rows = (int64_t)(1LL << 32) / ((int64_t)W * 128) - (8 + 4);
-    if (span_rows < RW) SRX_FAIL(SRX_E_UNSUPPORTED, "conv9x9_c64_thin_bf16_fwd: image rows of %d pixels are too long for 32-bit offsets inside a chunk", W);
+    if (span_rows < RW) SRX_FAIL(SRX_E_UNSUPPORTED, "%s: image rows of %d pixels are too long for 32-bit offsets inside a chunk", fn, W);
     if (best_rpc > span_rows) best_rpc = (int)(span_rows / RW) * RW;
   }
   a.rows_per_chunk = best_rpc;
@@ -310,8 +340,17 @@ extern "C" int srx_conv9x9_c64_thin_bf16_fwd(int N, int H, int W, const void* x,
   a.nwork = (int)(cols * a.chunks);
   const int gx = std::min(a.nwork, cus);
   char nm[112];
-  if (srx_prof_on()) snprintf(nm, sizeof(nm), "t9_bf16_kernel MxNxK=%lldx3x5184", (long long)N * H * W);
-  SRX_LAUNCH_PROF(nm, 2.0 * N * H * W * 3.0 * 5184.0, t9_bf16_kernel, dim3((unsigned)gx), dim3(512), LDS_BYTES, srx_stream(stream), a);
-  SRX_CHECK_LAUNCH("t9_bf16_kernel");
+  const char* kname = F16 ? "t9_f16_kernel" : "t9_bf16_kernel";
+  if (srx_prof_on()) snprintf(nm, sizeof(nm), "%s MxNxK=%lldx3x5184", kname, (long long)N * H * W);
+  SRX_LAUNCH_PROF(nm, 2.0 * N * H * W * 3.0 * 5184.0, t9_kernel<T>, dim3((unsigned)gx), dim3(512), LDS_BYTES, srx_stream(stream), a);
+  SRX_CHECK_LAUNCH(kname);
   return SRX_OK;
+}
+
+extern "C" int srx_conv9x9_c64_thin_bf16_fwd(int N, int H, int W, const void* x, const void* wpk, float* y, void* stream) {
+  return t9_fwd_impl<__bf16>(N, H, W, x, wpk, y, stream);
+}
+
+extern "C" int srx_conv9x9_c64_thin_f16_fwd(int N, int H, int W, const void* x, const void* wpk, float* y, void* stream) {
+  return t9_fwd_impl<_Float16>(N, H, W, x, wpk, y, stream);
 }

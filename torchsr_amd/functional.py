@@ -162,13 +162,25 @@ def _chk(t: Tensor, what: str) -> Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
-def _chk16(t: Tensor, what: str) -> Tensor:
-    """A bf16 NHWC activation of the bf16-native inference chain (csrc/c64.hip)."""
+def _chk16(t: Tensor, what: str, dtype: Optional[torch.dtype] = torch.bfloat16) -> Tensor:
+    """A 16-bit NHWC activation of the 16-bit-native inference chain (csrc/c64.hip): ``dtype`` (bf16 by default), or either
+    storage type with ``dtype=None``."""
     if t.device.type != 'cuda':
         raise RuntimeError(f'{what}: the MI355X path needs a CUDA/HIP tensor, got {t.device} (no CPU fallback)')
-    if t.dtype != torch.bfloat16:
-        raise RuntimeError(f'{what}: expected a bfloat16 tensor, got {t.dtype}')
+    if t.dtype != dtype and not (dtype is None and t.dtype in _STORE16):
+        raise RuntimeError(f'{what}: expected a {"bfloat16 or float16" if dtype is None else str(dtype)[6:]} tensor, got {t.dtype}')
     return t if t.is_contiguous() else t.contiguous()
+
+
+# the 16-bit storage types of the inference chain: bf16 (precision 1 / 2) and fp16 (precision 3, inference only)
+_STORE16 = (torch.bfloat16, torch.float16)
+PRECISION_F16 = 3
+
+
+def _chk_f16_inference(st, what: str) -> None:
+    """Precision 3 (fp16 storage and products) exists for inference only: no autograd."""
+    if st.precision == PRECISION_F16 and torch.is_grad_enabled():
+        raise RuntimeError(f'{what}: fp16 precision (3) is inference-only; run it under torch.no_grad() on an eval-mode model')
 
 
 def to_bf16(x: Tensor) -> Tensor:
@@ -179,35 +191,55 @@ def to_bf16(x: Tensor) -> Tensor:
     return y
 
 
+def to_f16(x: Tensor) -> Tensor:
+    """fp32 -> fp16 (round to nearest even; beyond 65519.99.. -> +-inf), same shape: the entry of the fp16 inference chain."""
+    x = _chk(x, 'to_f16.input')
+    y = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+    call('srx_f32_to_f16', _p(x), _p(y), x.numel(), _stream())
+    return y
+
+
 def to_f32(x: Tensor) -> Tensor:
-    x = _chk16(x, 'to_f32.input')
+    """bf16 or fp16 -> fp32 (exact), same shape."""
+    x = _chk16(x, 'to_f32.input', None)
     y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    call('srx_bf16_to_f32', _p(x), _p(y), x.numel(), _stream())
+    call('srx_bf16_to_f32' if x.dtype == torch.bfloat16 else 'srx_f16_to_f32', _p(x), _p(y), x.numel(), _stream())
     return y
 
 
 def conv2d_bf16in(conv, x: Tensor) -> Tensor:
-    """The generator's 64 -> 3 output conv on a bf16 input (``srx_conv2d_fwd_bf16in``; inference, precision 2); fp32 out."""
+    """The generator's 64 -> 3 output conv on a 16-bit input; fp32 out.  bf16: ``srx_conv2d_fwd_bf16in`` / the thin9 kernel
+    (inference, precision 2).  fp16: the thin9 kernel's fp16 form only (precision 3: no other kernel multiplies fp16)."""
     st = conv._st
-    x = _chk16(x, 'conv2d_bf16in.input')
+    x = _chk16(x, 'conv2d_bf16in.input', None)
     n, h, w, cs = x.shape
-    if st.precision != 2 or torch.is_grad_enabled():
+    f16 = x.dtype == torch.float16
+    t9 = st.k == 9 and st.pad == 4 and st.stride == 1 and st.cin == 64 and st.cout <= 3 and not _dev.NO_T9
+    if f16:
+        _chk_f16_inference(st, 'conv2d_bf16in')
+        if st.precision != PRECISION_F16 or not t9:
+            raise RuntimeError('conv2d_bf16in: an fp16 input needs precision 3 and a 9x9 64 -> <= 3 channel layer on the thin9 '
+                               'kernel (SRX_NO_T9 unset)')
+    elif st.precision != 2 or torch.is_grad_enabled():
         return conv(to_f32(x))
-    d = st.desc(n, h, w)
     y = torch.empty(st.out_shape(n, h, w), dtype=torch.float32, device=x.device)
     b = None if conv.bias is None else _chk(conv.bias.detach(), 'conv2d.bias')
-    if st.k == 9 and st.pad == 4 and st.stride == 1 and st.cin == 64 and st.cout <= 3 and not _dev.NO_T9:
-        # the taps as the GEMM's N (csrc/thin9.hip): 32x32x16 bf16 MFMAs instead of 4x4x4
-        key = st.pack_key(conv.weight) + (None if b is None else (b.data_ptr(), conv.bias._version),)
+    if t9:
+        # the taps as the GEMM's N (csrc/thin9.hip): 32x32x16 bf16 / fp16 MFMAs instead of 4x4x4.  The pack is keyed by the
+        # storage type too: a bf16 call after an fp16 one must not read fp16 weights
+        sfx = 'f16' if f16 else 'bf16'
+        key = st.pack_key(conv.weight) + (None if b is None else (b.data_ptr(), conv.bias._version), x.dtype)
         if conv.__dict__.get('_t9_key') != key:
             wpk = conv.__dict__.get('_t9_wpk')
             if wpk is None or wpk.device != x.device:
                 wpk = conv.__dict__['_t9_wpk'] = torch.empty(_lib.lib().srx_conv9x9_c64_thin_bf16_packed_bytes(), dtype=torch.uint8,
                                                              device=x.device)
-            call('srx_conv9x9_c64_thin_bf16_pack', _p(_chk(conv.weight.detach(), 'conv2d.weight')), _p(b), st.cout, _p(wpk), _stream())
+            call(f'srx_conv9x9_c64_thin_{sfx}_pack', _p(_chk(conv.weight.detach(), 'conv2d.weight')), _p(b), st.cout, _p(wpk),
+                 _stream())
             conv.__dict__['_t9_key'] = key
-        call('srx_conv9x9_c64_thin_bf16_fwd', n, h, w, _p(x), _p(conv.__dict__['_t9_wpk']), _p(y), _stream())
+        call(f'srx_conv9x9_c64_thin_{sfx}_fwd', n, h, w, _p(x), _p(conv.__dict__['_t9_wpk']), _p(y), _stream())
         return y
+    d = st.desc(n, h, w)
     st.pack(conv.weight, d)
     call('srx_conv2d_fwd_bf16in', C.byref(d), _p(x), _p(st.wpk_fwd), _p(b), _p(y), _stream())
     return y
@@ -289,13 +321,15 @@ class ConvState:
         self.cout_s = round4(cout // 4) if shuffle else round4(cout)
         self._descs = {}
         self.model_epoch = [0]  # replaced by the owning FlatParams' counter
-        self.precision = 0  # 1: bf16 products in the forward / stride-1 data gradient (srx_conv2d_t::precision)
+        self.precision = 0  # 1: bf16 products in the forward / stride-1 data gradient; 3: fp16 inference (srx_conv2d_t::precision)
+        # (3 reaches srx_conv2d_* only for the <= 4-channel input conv; the 64-channel layers run the _f16 chain entry points)
         self.wpk_fwd = None
         self.wpk_bwd = None
         self._key = None
         self.fused_only = False  # set while the layer runs inside a fused multi-conv kernel that has its own weight stream
 
     def desc(self, n, h, w) -> Conv2dDesc:
+        _chk_f16_inference(self, 'conv2d')
         d = self._descs.get((n, h, w, self.precision))
         if d is None:
             d = Conv2dDesc(n, h, w, self.cin, self.cin_s, self.cout, self.cout_s, self.k, self.k, self.stride,
@@ -1809,37 +1843,43 @@ class FoldedConv:
                 and (st.shuffle == 0 or (st.shuffle == 2 and st.cout == 256)))
 
     def _call_bf16(self, x: Tensor, residual: Optional[Tensor]) -> Tensor:
-        """bf16 in, bf16 out: the bf16-native chain (activations stored as bf16, weights resident in registers)."""
+        """16 bits in, the same 16 bits out: the 16-bit-native chain (activations stored as bf16 or fp16 -- the input's dtype
+        picks ``srx_conv3x3_c64_bf16_*`` or ``srx_conv3x3_c64_f16_*`` --, weights resident in registers)."""
         st = self.st
         if not self.bf16_native_ok():
-            raise RuntimeError('folded_conv: a bf16 input needs a 3x3 / 64-input-channel layer')
-        x = _chk16(x, 'folded_conv.input')
+            raise RuntimeError('folded_conv: a 16-bit input needs a 3x3 / 64-input-channel layer')
+        _chk_f16_inference(st, 'folded_conv')
+        x = _chk16(x, 'folded_conv.input', None)
+        dt = x.dtype
+        sfx = 'f16' if dt == torch.float16 else 'bf16'
         n, h, w, cs = x.shape
         if cs != 64:
-            raise RuntimeError(f'folded_conv: bf16 input has {cs} channels, the layer expects 64')
-        if self.__dict__.get('_key16') != self._key:
+            raise RuntimeError(f'folded_conv: {sfx} input has {cs} channels, the layer expects 64')
+        if self.__dict__.get('_key16') != (self._key, dt):  # (keyed by the storage type: fp16 and bf16 packs differ)
             nbytes = _lib.lib().srx_conv3x3_c64_bf16_packed_bytes(st.cout)
             wpk = self.__dict__.get('_wpk16')
             if wpk is None or wpk.numel() != nbytes or wpk.device != x.device:
                 wpk = self._wpk16 = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            call('srx_conv3x3_c64_bf16_pack', _p(self.w), _p(self.b), None, st.cout, st.shuffle, _p(wpk), _stream())
-            self._key16 = self._key
-        y = torch.empty(st.out_shape(n, h, w), dtype=torch.bfloat16, device=x.device)
+            call(f'srx_conv3x3_c64_{sfx}_pack', _p(self.w), _p(self.b), None, st.cout, st.shuffle, _p(wpk), _stream())
+            self._key16 = (self._key, dt)
+        y = torch.empty(st.out_shape(n, h, w), dtype=dt, device=x.device)
         slope = 1.0 if st.act == ACT_NONE else (0.0 if st.act == ACT_RELU else st.slope)
         r = None
         if residual is not None:
-            r = _chk16(residual, 'folded_conv.residual')
+            r = _chk16(residual, 'folded_conv.residual', dt)
             if r.shape != y.shape:
                 raise RuntimeError('folded_conv: residual must have the output shape')
-        call('srx_conv3x3_c64_bf16_fwd', n, h, w, st.cout, st.shuffle, _p(x), _p(self._wpk16), float(slope), _p(r), _p(y),
+        call(f'srx_conv3x3_c64_{sfx}_fwd', n, h, w, st.cout, st.shuffle, _p(x), _p(self._wpk16), float(slope), _p(r), _p(y),
              y.shape[3], _stream())
         return y
 
     def __call__(self, x: Tensor, residual: Optional[Tensor] = None) -> Tensor:
         self._refresh()
-        if x.dtype == torch.bfloat16:
+        if x.dtype in _STORE16:
             return self._call_bf16(x, residual)
         st = self.st
+        if st.precision == PRECISION_F16 and self.bf16_native_ok():
+            raise RuntimeError('folded_conv: with fp16 precision (3) a 64-channel layer takes an fp16 input (no fp32 fallback)')
         x = _chk(x, 'folded_conv.input')
         n, h, w, cs = x.shape
         if cs != st.cin_s:

@@ -57,6 +57,9 @@ class Conv2d(nn.Conv2d):
     def forward(self, x: Tensor, want_stats: bool = False, in_act=None, act_bwd_folded=None):
         """``in_act`` / ``act_bwd_folded``: a consumer / producer pair of flags that moves the backward of the producer's
         fused activation into the consumer's data gradient (``functional._Conv2d.forward``)."""
+        if self._st.precision == F.PRECISION_F16 and not F.inference_mode(self):
+            raise RuntimeError('Conv2d: fp16 precision (3) is inference-only (eval mode, no autograd); '
+                               "train with 'fp32' or 'bf16'")
         y, part = F.conv2d(x, _w(self.weight), _w(self.bias), self._st, want_stats, self.weight, in_act, act_bwd_folded)
         return (y, part) if want_stats else y
 

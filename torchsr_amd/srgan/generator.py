@@ -45,8 +45,9 @@ class Generator(nn.Module):
             f = self.__dict__.setdefault('_folded', (F.FoldedConv(self.conv1[0], None, self.conv1[1]),
                                                      F.FoldedConv(self.conv2[0], self.conv2[1], None)))
         conv1 = f[0](x4)
-        if self.bf16_native():  # from here to the output conv the activations are STORED as bf16 (csrc/c64.hip)
-            conv1 = F.to_bf16(conv1)
+        dt = self.native16()
+        if dt is not None:  # from here to the output conv the activations are STORED as bf16 / fp16 (csrc/c64.hip)
+            conv1 = F.to_bf16(conv1) if dt == torch.bfloat16 else F.to_f16(conv1)
         out = f[1](self.blocks(conv1), residual=conv1)
         for layer in list(self.conv_layers)[:-1]:
             out = layer(out)
@@ -55,14 +56,18 @@ class Generator(nn.Module):
     def infer_head_nhwc(self, feat: Tensor) -> Tensor:
         """Inference, second stage: feature map (or a tile of it with ``head_halo`` pixels around) -> NHWC image."""
         out = self.conv_layers[-1](feat)
-        if out.dtype == torch.bfloat16:
+        if out.dtype in (torch.bfloat16, torch.float16):
             return F.conv2d_bf16in(self.conv3, out)
         return self.conv3(out)
 
-    def bf16_native(self) -> bool:
-        """Inference with bf16 products (``test.upscale(precision='bf16')``): the 64-channel layers keep their activations
-        in bf16 between kernels (``srx_conv3x3_c64_bf16_fwd``) -- half the HBM traffic, no conversion on the way into LDS."""
-        return self.conv2[0]._st.precision == 1 and not _dev.NO_C64 and F.inference_mode(self)
+    def native16(self):
+        """The storage dtype of the 16-bit-native inference chain, or None.  Inference with bf16 products
+        (``test.upscale(precision='bf16')``, conv precision 1): ``torch.bfloat16``; with fp16 (``precision='fp16'``, conv
+        precision 3): ``torch.float16``.  The 64-channel layers then keep their activations in 16 bits between kernels
+        (``srx_conv3x3_c64_{bf16,f16}_fwd``) -- half the HBM traffic, no conversion on the way into LDS."""
+        if _dev.NO_C64 or not F.inference_mode(self):
+            return None
+        return {1: torch.bfloat16, F.PRECISION_F16: torch.float16}.get(self.conv2[0]._st.precision)
 
     def forward_nhwc(self, x4: Tensor) -> Tensor:
         """NHWC ``[N,h,w,4]`` -> NHWC ``[N,s*h,s*w,4]`` (4th channel zero)."""

@@ -38,23 +38,41 @@ def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
             max_tile_pixels: int = MAX_TILE_PIXELS, scale: int = 4, precision: str = None, staged: bool = True) -> Tensor:
     """``generator(low_res)`` in eval mode, tiled when the image is large.  ``low_res``: [N,3,h,w].
 
-    ``precision``: ``'fp32'`` (exact; the reference's ``test`` runs no autocast, test.py:57-62) or ``'bf16'`` (bf16
-    products with fp32 accumulation in every conv but the 3-channel INPUT conv); ``None`` keeps
-    whatever the generator's convs are set to.  The setting is restored afterwards.  ``staged=False`` forces the halo
-    tiling for a generator that offers the two-stage interface (``_upscale_staged``)."""
+    ``precision``: ``'fp32'`` (exact; the reference's ``test`` runs no autocast, test.py:57-62), ``'bf16'`` (bf16
+    products with fp32 accumulation in every conv but the 3-channel INPUT conv) or ``'fp16'``
+    (a generator with the 16-bit-native chain -- SRGAN's ``Generator.native16`` -- only: fp16 products with fp32
+    accumulation in every conv, the 64-channel activations stored as fp16; a non-finite output, i.e. an overflow of
+    fp16's +-65504, raises ``FloatingPointError``); ``None`` keeps whatever the generator's convs are set to.  The setting
+    is restored afterwards.  ``staged=False`` forces the halo tiling for a generator that offers the two-stage interface
+    (``_upscale_staged``)."""
+    from . import _dev
+    from .functional import PRECISION_F16
     from .layers import Conv2d, set_conv_precision
     generator.eval()
     if precision is not None:
-        if precision not in ('fp32', 'bf16'):
-            raise ValueError(f"upscale: precision must be 'fp32' or 'bf16', got {precision!r}")
+        if precision not in ('fp32', 'bf16', 'fp16'):
+            raise ValueError(f"upscale: precision must be 'fp32', 'bf16' or 'fp16', got {precision!r}")
+        if precision == 'fp16' and (not hasattr(generator, 'native16') or _dev.NO_C64 or _dev.NO_T9):
+            raise ValueError(f"upscale: precision 'fp16' needs a generator with the 16-bit-native chain (SRGAN; "
+                             f"{type(generator).__name__} has none) and its kernels enabled (SRX_NO_C64 / SRX_NO_T9 unset)")
         saved = [(m, m._st.precision) for m in generator.modules() if isinstance(m, Conv2d)]
-        set_conv_precision(generator, precision)
+        if precision == 'fp16':  # inference only: set here, never through set_conv_precision (training has no fp16)
+            for m, _ in saved:
+                m._st.precision = PRECISION_F16
+        else:
+            set_conv_precision(generator, precision)
         if precision == 'bf16':  # inference: the 64 -> 3 output conv multiplies bf16 operands too (srx_conv2d_t::precision = 2)
             for m, _ in saved:
                 if m.out_channels <= 4 and m.in_channels == 64:
                     m._st.precision = 2
         try:
-            return upscale(generator, low_res, halo, max_tile_pixels, scale, None, staged)
+            out = upscale(generator, low_res, halo, max_tile_pixels, scale, None, staged)
+            # fp32 and bf16 share fp32's range: a non-finite value here is an fp16 overflow.  (Every element is finite iff the
+            # minimum and the maximum are -- both propagate NaN --: one reduction, where isfinite(out).all() took 0.44 ms at 8K, this 0.17.)
+            if precision == 'fp16' and not bool(torch.isfinite(torch.stack(torch.aminmax(out))).all()):
+                raise FloatingPointError("upscale: the fp16 result is not finite -- an activation left fp16's range "
+                                         "(+-65504); use precision='bf16' or 'fp32' for this model / image")
+            return out
         finally:
             for m, p in saved:
                 m._st.precision = p

@@ -106,9 +106,10 @@ def parse_args(argv=None) -> Namespace:
     test = commands.add_parser('test', help='Generate a super resolution image from a trained model.')
     test.add_argument('image', type=str)
     test.add_argument('--model', type=str, default=MODEL, choices=MODELS.keys())
-    test.add_argument('--precision', type=str, default='fp32', choices=('fp32', 'bf16'),
-                      help='conv arithmetic of the generator forward: exact fp32 (the reference runs no autocast here) or '
-                           'bf16 products with fp32 accumulation')
+    test.add_argument('--precision', type=str, default='fp32', choices=('fp32', 'bf16', 'fp16'),
+                      help='conv arithmetic of the generator forward: exact fp32 (the reference runs no autocast here), '
+                           'bf16 products with fp32 accumulation, or fp16 products and fp16-stored activations with fp32 '
+                           'accumulation (SRGAN only; an fp16 overflow is reported, not written)')
     return parser.parse_args(argv)
 
 
