@@ -1,5 +1,6 @@
 """The conv problems of the batch-16 SRGAN GAN step (BASELINE configs[1], the bench.py headline), shared by the tests that
-exercise them at the step's own sizes (test_ops_gpu.py, test_step_layers_gpu.py)."""
+exercise them at the step's own sizes (test_ops_gpu.py, test_step_layers_gpu.py), and below them the non-convolution problems
+of the SRGAN and ESRGAN steps (STEP_OPS: test_step_ops_gpu.py, test_cpu.py)."""
 from torchsr_amd._lib import ACT_LRELU, ACT_RELU
 
 FULL_SIZE_LAYERS = [
@@ -77,3 +78,277 @@ def prof_launches(fn, buf_len=160):
         _lib.call('srx_prof_get', i, buf, buf_len, C.byref(ms), C.byref(fl))
         names.append(buf.value.decode())
     return names
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The non-convolution launches of the steps: BatchNorm, losses, pools, activations' backward, layout, Adam (norm.hip, loss.hip,
+# eltwise.hip, optim.hip).  OP_ARGS names the INTEGER arguments of each entry point in the order of the C signature
+# (include/srx.h); op_key folds them into (entry point, rows M or elements n, C, groups, act): what a STEP_OPS row is matched by.
+OP_ARGS = {
+    'srx_nchw_to_nhwc': ('N', 'Cin', 'H', 'W', 'C'), 'srx_nhwc_to_nchw': ('N', 'Cin', 'H', 'W', 'C'),
+    'srx_colsum': ('M', 'C', 'Cs', 'accumulate'), 'srx_act_bwd_from_out': ('n', 'act'),
+    'srx_act_bwd_from_out_strided': ('ldy', 'ly', 'ldx', 'M', 'C', 'act'), 'srx_prelu_fwd': ('n',),
+    'srx_prelu_bwd': ('accumulate', 'n'), 'srx_lrelu_fwd': ('n',), 'srx_axpby': ('n',),
+    'srx_axpby_channels': ('x_cs', 'x_off', 'z_cs', 'z_off', 'y_cs', 'y_off', 'C', 'M'),
+    'srx_copy_channels': ('src_cs', 'src_off', 'dst_cs', 'dst_off', 'C', 'M', 'accumulate'),
+    'srx_upsample_nearest2x_fwd': ('N', 'H', 'W', 'C'), 'srx_upsample_nearest2x_bwd': ('N', 'H', 'W', 'C'),
+    'srx_mean_fwd': ('n',), 'srx_mean_bwd': ('n',), 'srx_sigmoid_fwd': ('n',), 'srx_sigmoid_bwd': ('n',),
+    'srx_bn_partial_stats': ('M', 'C'), 'srx_bn_finalize': ('rows', 'M', 'C'), 'srx_bn_eval_stats': ('C',),
+    'srx_bn_act_fwd': ('M', 'C', 'act'), 'srx_bn_act_bwd_reduce': ('M', 'C', 'act'),
+    'srx_bn_act_bwd_apply': ('M', 'C', 'act', 'training'), 'srx_bn_train_fwd': ('rows', 'M', 'C', 'groups', 'act'),
+    'srx_bn_act_bwd': ('M', 'C', 'groups', 'act', 'training'), 'srx_bn_act_bwd_finish': ('rows', 'prelu_cols', 'M', 'C', 'act'),
+    'srx_maxpool2x2_fwd': ('N', 'H', 'W', 'C'), 'srx_maxpool2x2_bwd': ('N', 'H', 'W', 'C'),
+    'srx_maxpool2x2_relu_bwd': ('N', 'H', 'W', 'C'), 'srx_maxpool2x2_fwd_to_bf16': ('N', 'H', 'W', 'C'),
+    'srx_maxpool2x2_relu_bwd_bf16': ('N', 'H', 'W', 'C'), 'srx_act_bwd_from_out_to_bf16': ('n', 'act'),
+    'srx_mse_fwd': ('n',), 'srx_l1_fwd': ('n',), 'srx_mse_bwd': ('n',), 'srx_l1_bwd': ('n',), 'srx_l1_fwd_count': ('n', 'count'),
+    'srx_l1_bwd_count': ('n', 'count'), 'srx_bce_fwd': ('n',), 'srx_bce_bwd': ('n',), 'srx_bce_logits_fwd': ('n',),
+    'srx_bce_logits_bwd': ('n',), 'srx_adam_step': ('n',),
+}
+# srx_* launches that are neither convolutions nor in the four files above, and the op-level tests that hold them
+OPS_TESTED_ELSEWHERE = {
+    'srx_linear_fwd': 'test_ops_gpu.py::test_linear', 'srx_linear_bwd_data': 'test_ops_gpu.py::test_linear',
+    'srx_linear_bwd_weight': 'test_ops_gpu.py::test_linear', 'srx_gan_head_fwd': 'test_head_gpu.py', 'srx_gan_head_bwd': 'test_head_gpu.py',
+    'srx_ring_push': 'test_step_gpu.py (one thread, no shape)', 'srx_crop_flip_u8': 'test_ops_gpu.py', 'srx_bicubic_down': 'test_ops_gpu.py',
+}
+_CONV_PREFIXES = ('srx_conv', 'srx_wino', 'srx_pack_table', 'srx_rdb', 'srx_prof', 'srx_f32_to', 'srx_bf16_to', 'srx_f16_to',
+                  'srx_wgrad', 'srx_set_', 'srx_plan_', 'srx_occupy', 'srx_device', 'srx_version', 'srx_last', 'srx_build')
+
+
+def op_key(name, ints):
+    """(entry point, M or n, C, groups, act) of one recorded call; pools, layout and upsampling kernels: M = N * H * W pixels of
+    the tensor whose size the arguments give."""
+    a = dict(zip(OP_ARGS[name], ints))
+    size = a['M'] if 'M' in a else a['n'] if 'n' in a else a['N'] * a['H'] * a['W'] if 'N' in a else 0
+    return (name, int(size), int(a.get('C', 0)), int(a.get('groups', 1)), int(a.get('act', 0)))
+
+
+def record_op_calls(monkeypatch, fn):
+    """Run ``fn`` with ``torchsr_amd._lib.call`` -- and every module-level alias of it in the package (functional.py, optim.py
+    import the name) -- wrapped: the (entry point, integer arguments) of every srx_* call that is not a convolution, in call
+    order.  The integer arguments are those the ctypes signature declares as int / int64 (sizes and flags, never pointers)."""
+    import ctypes as C
+    import sys
+    import torch
+    from torchsr_amd import _lib
+    import torchsr_amd.esrgan.trainer  # noqa: F401  (every module that binds `call` must be loaded BEFORE the patch: one imported
+    import torchsr_amd.srgan.trainer  # noqa: F401   while it is in place would keep the spy as its alias for good)
+    import torchsr_amd.functional  # noqa: F401
+    import torchsr_amd.optim  # noqa: F401
+    real = _lib.call
+    calls = []
+
+    def spy(name, *args):
+        if not name.startswith(_CONV_PREFIXES):
+            types = _lib._SIGS[name][1]
+            calls.append((name, tuple(int(v) for v, t in zip(args, types) if t in (C.c_int, C.c_int64))))
+        return real(name, *args)
+
+    for mod_name, mod in list(sys.modules.items()):
+        if mod is None or not (mod_name == 'torchsr_amd' or mod_name.startswith('torchsr_amd.')):
+            continue
+        for attr, val in list(vars(mod).items()):
+            if val is real:
+                monkeypatch.setattr(mod, attr, spy)
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        monkeypatch.undo()
+    return calls
+
+
+# STEP_OPS: the non-convolution problems of the batch-16 SRGAN step and the batch-16 ESRGAN step (rows the recorder above finds
+# there: test_step_ops_are_covered) plus the edges of the kernels' launch geometry.  op: the family (one runner in
+# test_step_ops_gpu.py); the other fields are that family's sizes.  covers: op_key()s of the calls the case makes.
+ACT_NONE_, ACT_PRELU_ = 0, 3
+SLOPE = 0.25  # a power of two: integer data times the slope stays exact (counted in quarters)
+
+
+def _bn(m, c, groups=1, act=ACT_LRELU, training=True, residual=False, finish_rows=0):
+    tag = {0: 'none', 2: 'lrelu', 3: 'prelu'}[act]
+    id_ = f'bn.{m}x{c}.g{groups}.{tag}' + ('' if training else '.eval') + ('.res' if residual else '')
+    if training:
+        covers = [('srx_bn_partial_stats', m, c, 1, 0), ('srx_bn_train_fwd', m, c, groups, act), ('srx_bn_act_bwd', m, c, groups, act)]
+        if groups == 1:  # (the residual tower finalises its conv epilogue's table with the one-group call)
+            covers.append(('srx_bn_finalize', m, c, 1, 0))
+    else:
+        covers = [('srx_bn_eval_stats', 0, c, 1, 0), ('srx_bn_act_fwd', m, c, 1, act), ('srx_bn_act_bwd', m, c, 1, act)]
+    if groups == 1:  # the two-call form of the backward and, in training, its finish form WITH the apply pass
+        covers += [('srx_bn_act_bwd_reduce', m, c, 1, act), ('srx_bn_act_bwd_apply', m, c, 1, act)]
+        if training:
+            covers.append(('srx_bn_act_bwd_finish', m, c, 1, act))
+    return dict(id=id_, op='bn', M=m, C=c, groups=groups, act=act, training=training, residual=residual, covers=covers)
+
+
+STEP_OPS = [
+    # generator: the residual tower's BatchNorm + PReLU, its BatchNorm + skip, conv2's BatchNorm + skip (16 x 24 x 24 rows)
+    _bn(9216, 64, act=ACT_PRELU_), _bn(9216, 64, act=ACT_NONE_, residual=True), _bn(9216, 64, act=ACT_NONE_),
+    _bn(9216, 64, act=ACT_PRELU_, training=False), _bn(9216, 64, act=ACT_NONE_, training=False, residual=True),
+    # SRGAN discriminator on real + fake as one batch of 32 (two groups): 128-row blocks and, above 4 Mi elements, the
+    # grid-stride regime of the streaming kernels
+    _bn(73728, 64, 2), _bn(73728, 128, 2), _bn(18432, 128, 2), _bn(18432, 256, 2), _bn(4608, 256, 2), _bn(4608, 512, 2),
+    _bn(1152, 512, 2),
+    # ... and on the 16 generated images alone (the generator's adversarial term)
+    _bn(36864, 64), _bn(36864, 128), _bn(9216, 128), _bn(9216, 256), _bn(2304, 256), _bn(2304, 512), _bn(576, 512),
+    # ESRGAN discriminator, 32 images of 128 x 128: the first M on the 512-row plan
+    _bn(131072, 64, 2),
+    _bn(131072, 128, 2),
+    # ... its other layers, pair pass (two groups) and adversarial pass
+    _bn(65536, 64), _bn(65536, 128), _bn(32768, 128, 2), _bn(32768, 256, 2), _bn(16384, 128), _bn(16384, 256), _bn(8192, 256, 2),
+    _bn(8192, 512, 2), _bn(4096, 256), _bn(4096, 512), _bn(2048, 512, 2), _bn(1024, 512), _bn(512, 512, 2), _bn(256, 512),
+    # the row-block thresholds from both sides (one group: the last block is partial)
+    _bn(32767, 16), _bn(32768, 16), _bn(131071, 16), _bn(131072, 16),
+    # C = 256: 4 row lanes, 16 rows per trip; the last block holds 16 + 1 rows
+    _bn(36 * 32 + 17, 256, act=ACT_NONE_),
+    # cq = 10 does not divide 256 (6 idle threads), the narrowest and the widest channel count
+    _bn(4608, 40, act=ACT_PRELU_), _bn(4608, 8), _bn(1152, 1024, act=ACT_NONE_, residual=True),
+]
+STEP_OPS += [
+    # srx_bn_act_bwd_finish on a hand-built table: the PReLU partial in one and in two columns; 257 rows: one past a lane trip
+    dict(id='bn_finish.257x64.cols1', op='bn_finish', rows=257, C=64, M=9216, prelu_cols=1, act=3, covers=[('srx_bn_act_bwd_finish', 9216, 64, 1, 3)]),
+    dict(id='bn_finish.256x64.cols2', op='bn_finish', rows=256, C=64, M=9216, prelu_cols=2, act=3, covers=[('srx_bn_act_bwd_finish', 9216, 64, 1, 3)]),
+    dict(id='bn_finish.256x64.cols2.none', op='bn_finish', rows=256, C=64, M=9216, prelu_cols=2, act=0, covers=[('srx_bn_act_bwd_finish', 9216, 64, 1, 0)]),
+]
+
+
+def _colsum(m, c, cs, acc):
+    return dict(id=f'colsum.{m}x{c}.cs{cs}.acc{acc}', op='colsum', M=m, C=c, Cs=cs, accumulate=acc, covers=[('srx_colsum', m, c, 1, 0)])
+
+
+STEP_OPS += [_colsum(147456, 64, 64, 1), _colsum(9216, 3, 4, 0), _colsum(4099, 100, 104, 1), _colsum(32, 1, 1, 0), _colsum(32, 1, 1, 1),
+             _colsum(32, 1024, 1024, 1)]
+
+
+def _n(op, n, entries, **kw):
+    return dict(id=f'{op}.{n}' + ''.join(f'.{k}{v}' for k, v in kw.items()), op=op, n=n, covers=[(e, n, 0, 1, kw.get('act', 0)) for e in entries], **kw)
+
+
+LOSS_SIZES = (16 * 96 * 96 * 4, 16 * 6 * 6 * 512, 16 * 8 * 8 * 512, 1024 * 1024 - 1, 1024 * 1024, 1024 * 1024 + 1, 1, 16, 32)
+for _nn in LOSS_SIZES:
+    STEP_OPS.append(_n('mse', _nn, ('srx_mse_fwd', 'srx_mse_bwd')))
+    STEP_OPS.append(_n('l1', _nn, ('srx_l1_fwd', 'srx_l1_bwd')))
+    STEP_OPS.append(_n('mean', _nn, ('srx_mean_fwd', 'srx_mean_bwd')))
+    STEP_OPS.append(_n('bce', _nn, ('srx_bce_fwd', 'srx_bce_bwd')))
+    STEP_OPS.append(_n('bce_logits', _nn, ('srx_bce_logits_fwd', 'srx_bce_logits_bwd')))
+STEP_OPS.append(dict(id='l1_count.589824', op='l1', n=16 * 96 * 96 * 4, count=16 * 96 * 96 * 3,
+                     covers=[('srx_l1_fwd_count', 16 * 96 * 96 * 4, 0, 1, 0), ('srx_l1_bwd_count', 16 * 96 * 96 * 4, 0, 1, 0)]))
+STEP_OPS.append(dict(id='l1_count.1048576', op='l1', n=16 * 128 * 128 * 4, count=16 * 128 * 128 * 3,
+                     covers=[('srx_l1_fwd_count', 1024 * 1024, 0, 1, 0), ('srx_l1_bwd_count', 1024 * 1024, 0, 1, 0)]))
+STEP_OPS.append(dict(id='l1_count.1048577', op='l1', n=1024 * 1024 + 1, count=786433,
+                     covers=[('srx_l1_fwd_count', 1024 * 1024 + 1, 0, 1, 0), ('srx_l1_bwd_count', 1024 * 1024 + 1, 0, 1, 0)]))
+# activations' backward at the generator's sizes (16 x 96 x 96 x 64 is past the 4096-block cap), n & 3 tails included
+for _nn in (16 * 24 * 24 * 64, 16 * 48 * 48 * 64, 16 * 96 * 96 * 64, 4096 * 1024 + 1027):
+    STEP_OPS.append(_n('prelu_bwd', _nn, ('srx_prelu_fwd', 'srx_prelu_bwd')))
+    STEP_OPS.append(_n('act_bwd', _nn, ('srx_act_bwd_from_out',), act=2))
+for _nn, _a in ((16 * 96 * 96 * 64, 1), (16 * 6 * 6 * 512, 1), (16 * 8 * 8 * 512, 1), (16 * 64 * 64 * 64, 2), (16 * 128 * 128 * 64, 2)):
+    STEP_OPS.append(_n('act_bwd', _nn, ('srx_act_bwd_from_out',), act=_a))
+STEP_OPS.append(dict(id='act_bwd_strided.32768x32', op='act_bwd_strided', M=16 * 32 * 32 * 2, C=32, ld=192, act=2,
+                     covers=[('srx_act_bwd_from_out_strided', 16 * 32 * 32 * 2, 32, 1, 2)]))
+STEP_OPS.append(dict(id='act_bwd_strided.147456x64', op='act_bwd_strided', M=147456, C=64, ld=68, act=1,
+                     covers=[('srx_act_bwd_from_out_strided', 147456, 64, 1, 1)]))
+for _nn in (1, 16 * 24 * 24 * 64, 16 * 32 * 32 * 64, 16 * 96 * 96 * 64, 4096 * 1024 + 1026):
+    STEP_OPS.append(_n('axpby', _nn, ('srx_axpby',)))
+# VGG19's pools in the perceptual loss: source + target forward (N = 32), the source's backward (N = 16)
+for _hw, _c in ((96, 64), (48, 128), (24, 256), (12, 512), (128, 64), (64, 128), (32, 256), (16, 512)):
+    STEP_OPS.append(dict(id=f'pool.32x{_hw}x{_c}', op='pool', N=32, H=_hw, W=_hw, C=_c, covers=[('srx_maxpool2x2_fwd', 32 * _hw * _hw, _c, 1, 0)]))
+    STEP_OPS.append(dict(id=f'pool.16x{_hw}x{_c}', op='pool', N=16, H=_hw, W=_hw, C=_c, bwd=True,
+                         covers=[('srx_maxpool2x2_fwd', 16 * _hw * _hw, _c, 1, 0), ('srx_maxpool2x2_bwd', 16 * _hw * _hw, _c, 1, 0),
+                                 ('srx_maxpool2x2_relu_bwd', 16 * _hw * _hw, _c, 1, 0)]))
+# layout at the module boundary: images in (3 -> 4 channels), images out, the discriminator's flatten
+for _nn, _c, _hw, _cs in ((16, 3, 24, 4), (16, 3, 96, 4), (32, 3, 96, 4), (32, 512, 6, 512), (16, 512, 6, 512), (16, 3, 32, 4), (16, 3, 128, 4),
+                           (32, 512, 4, 512), (16, 512, 4, 512)):
+    STEP_OPS.append(dict(id=f'layout.{_nn}x{_c}x{_hw}', op='layout', N=_nn, Cin=_c, H=_hw, W=_hw, Cs=_cs,
+                         covers=[('srx_nchw_to_nhwc', _nn * _hw * _hw, _cs, 1, 0), ('srx_nhwc_to_nchw', _nn * _hw * _hw, _cs, 1, 0)]))
+# ESRGAN's trunk between dense-block buffers: 64-channel slices of 192-channel rows
+STEP_OPS.append(dict(id='channels.16384x64', op='channels', M=16 * 32 * 32, C=64, wide=192,
+                     covers=[('srx_axpby_channels', 16384, 64, 1, 0), ('srx_copy_channels', 16384, 64, 1, 0)]))
+STEP_OPS.append(dict(id='channels.147457x32', op='channels', M=147457, C=32, wide=192,
+                     covers=[('srx_axpby_channels', 147457, 32, 1, 0), ('srx_copy_channels', 147457, 32, 1, 0)]))
+# Adam on the flat buffers of the four models (lengths read from the built models) and on lengths with an n & 3 tail past the
+# 4096-block cap (4096 x 1024 floats)
+STEP_OPS += [dict(id=f'adam.{_k}.{_m}', op='adam', model=f'{_k}.{_m}', covers=[]) for _k in ('srgan', 'esrgan') for _m in 'GD']
+STEP_OPS += [dict(id=f'adam.tail{_r}', op='adam', n=4096 * 1024 + 1024 + _r, covers=[('srx_adam_step', 4096 * 1024 + 1024 + _r, 0, 1, 0)])
+             for _r in (1, 2, 3)]
+
+
+def _rng(case):
+    import zlib
+    import numpy as np
+    return np.random.default_rng(zlib.crc32(case['id'].encode()))
+
+
+def _sparse(rng, shape, hi, keep, pin=1):
+    """integers in [-hi, hi], a fraction ``keep`` of them kept, the rest zero -- except the last four elements and every 1024th,
+    which are ``pin``: every block of every launch geometry and every n & 3 tail holds non-zeros"""
+    import numpy as np
+    v = rng.integers(-hi, hi + 1, shape, dtype=np.int8)
+    if keep >= 1.0:
+        return v
+    v = np.where(rng.random(shape, dtype=np.float32) < keep, v, 0).astype(np.int8)
+    flat = v.reshape(-1)
+    flat[-4:] = pin
+    flat[::1024] = pin
+    return v
+
+
+def int_inputs(case):
+    """The integer-valued inputs of a case's exact check (int8 arrays; the tests cast them to fp32), or None when the family has
+    no exact check.  Every product of two of them, times SLOPE, is a whole number of quarters."""
+    rng, op = _rng(case), case['op']
+    if op == 'bn':
+        shape = (case['M'], case['C'])
+        d = dict(y=_sparse(rng, shape, 3, 1.0), dout=_sparse(rng, shape, 2, 1.0))
+        if case['act'] == ACT_PRELU_:  # the slope gradient is ONE sum over the whole tensor: sparser gradients
+            d['dout'] = _sparse(rng, shape, 2, 0.25)
+        return d
+    if op == 'bn_finish':
+        return dict(table=_sparse(rng, (case['rows'], 2 * case['C'] + 4), 100, 1.0).astype('int32'))
+    if op == 'colsum':
+        x = _sparse(rng, (case['M'], case['Cs']), 3, 1.0)
+        x[-1][x[-1] == 0] = 1  # the last row counts in every column
+        return dict(x=x)
+    if op in ('mse', 'l1', 'mean'):
+        n = case['n']
+        return dict(a=_sparse(rng, n, 2, 0.5), b=_sparse(rng, n, 1, 0.5, pin=-1))
+    if op == 'prelu_bwd':
+        n = case['n']
+        return dict(x=_sparse(rng, n, 2, 0.75, pin=-1), dy=_sparse(rng, n, 1, 0.5))
+    return None
+
+
+def int_abs_sums(case, d):
+    """{output: largest sum of ABSOLUTE values of the terms of any one output element}, in the smallest unit present (quarters
+    where SLOPE multiplies), computed in int64: below 2^24 every partial sum in every order is an fp32 number."""
+    import numpy as np
+    op = case['op']
+    i64 = lambda a: a.astype(np.int64)  # noqa: E731
+    if op == 'bn':
+        y, dout = i64(d['y']), i64(d['dout'])
+        per = case['M'] // case['groups']
+        out = {'sum y': np.abs(y).sum(0).max(), 'sum y^2': (y * y).sum(0).max()}
+        if case['act'] == ACT_NONE_:
+            dz4 = 4 * dout
+        else:
+            dz4 = np.where(y > 0, 4 * dout, dout)  # quarters
+        out['sum dz'] = np.abs(dz4).sum(0).max()          # (the parameter gradients total over the groups)
+        out['sum dz xhat'] = np.abs(dz4 * y).sum(0).max()
+        if case['act'] == ACT_PRELU_:
+            out['d prelu'] = np.abs(np.where(y > 0, 0, dout * y)).sum()
+        assert per * case['groups'] == case['M']
+        # + the non-zero .grad the sums are accumulated into (|grad| <= 8 units, see the runner)
+        return {k: int(v) + 4 * 8 for k, v in out.items()}
+    if op == 'bn_finish':
+        t = np.abs(i64(d['table']))
+        c = case['C']
+        cols = t[:, :2 * c].sum(0).max()
+        pre = t[:, 2 * c:2 * c + case['prelu_cols']].sum()
+        return {'columns': int(cols) + 8, 'prelu': int(pre) + 8}
+    if op == 'colsum':
+        return {'colsum': int(np.abs(i64(d['x'])).sum(0).max()) + 8}
+    if op in ('mse', 'l1', 'mean'):
+        a, b = i64(d['a']), i64(d['b'])
+        return {'mse': int(((a - b) ** 2).sum()), 'l1': int(np.abs(a - b).sum()), 'mean': int(np.abs(a).sum())}
+    if op == 'prelu_bwd':
+        x, dy = i64(d['x']), i64(d['dy'])
+        return {'dslope': int(np.abs(np.where(x > 0, 0, dy * x)).sum()) + 8}
+    raise KeyError(op)

@@ -702,3 +702,85 @@ def test_forced_plans_change_the_reported_plan_and_reset_restores_the_model_with
         lib.srx_wgrad_force(-1, 0)
     assert defaults() == pinned
     assert lib.srx_conv2d_bwd_weight_multi_ws_floats(C.byref(wl), 1) == ws_default
+
+
+def test_step_ops_integer_cases_stay_exact():
+    """The exact checks of test_step_ops_gpu.py rest on one precondition: for every output of every integer case of
+    step_layers.STEP_OPS the sum of the ABSOLUTE values of its terms -- counted in the smallest unit present, quarters where the
+    slope 0.25 multiplies -- stays below 2^24.  Then every partial sum, in whatever order a kernel takes it, is a whole number
+    of units below 2^24 and so an fp32 number: nothing rounds, and the kernel's result must equal the int64 truth.  (A bound on
+    the signed sum would not do: a partial sum may exceed the total.)  Every case is built here and counted in int64."""
+    from step_layers import STEP_OPS, int_abs_sums, int_inputs
+    ids = [c['id'] for c in STEP_OPS]
+    assert len(ids) == len(set(ids))
+    built = 0
+    for case in STEP_OPS:
+        d = int_inputs(case)
+        if d is None:
+            continue
+        built += 1
+        for arr in d.values():
+            assert arr.dtype.kind == 'i' and np.abs(arr).max() > 0, case['id']
+        for what, s in int_abs_sums(case, d).items():
+            assert 0 < s < 2 ** 24, (case['id'], what, s)
+        # non-zeros everywhere a kernel could lose them: per row block for the row reductions, per 1024 elements and in the last
+        # element (the n & 3 tail) for the flat ones
+        if case['op'] == 'bn':  # 32 rows: the smallest row block
+            for name in ('y', 'dout'):
+                rows = np.abs(d[name].astype(np.int64)).sum(1)
+                assert np.add.reduceat(rows, np.arange(0, case['M'], 32)).min() > 0 and rows[-1] > 0, (case['id'], name)
+        elif case['op'] == 'colsum':  # 16 rows: the smallest partial block
+            rows = np.abs(d['x'].astype(np.int64)[:, :case['C']]).sum(1)
+            assert np.add.reduceat(rows, np.arange(0, case['M'], 16)).min() > 0 and rows[-1] > 0, case['id']
+        elif case['op'] == 'bn_finish':
+            assert np.abs(d['table']).sum(1).min() > 0, case['id']  # every table row
+        else:
+            for name, arr in d.items():
+                flat = np.abs(arr.reshape(-1).astype(np.int64))
+                assert flat[-1] > 0 and np.add.reduceat(flat, np.arange(0, flat.size, 1024)).min() > 0, (case['id'], name)
+    assert built >= 60
+
+
+def test_abi_refuses_bad_batchnorm_groups_and_channels_without_a_gpu():
+    """srx_bn_*: `groups` must divide the rows (and the partial-table rows), a row block must not straddle two groups, C is a
+    multiple of 4 in [4, 1024] -- refused with a status code before anything is launched (fake pointers, CPU only)."""
+    import ctypes as C
+    from torchsr_amd import _lib
+    if torch.cuda.is_available():
+        pytest.skip('fake pointers: argument validation is exercised where a missed check cannot reach a device')
+    lib = _lib.lib()
+    fake = 0x10000
+
+    def err():
+        buf = C.create_string_buffer(256)
+        lib.srx_last_error(buf, 256)
+        return buf.value.decode()
+
+    def train_fwd(rows, m, c, groups):
+        return lib.srx_bn_train_fwd(fake, fake, rows, m, c, groups, 1e-5, 0.1, fake, fake, None, fake, 0, 0.0, None, fake, fake,
+                                    None, None, None, None)
+
+    def act_bwd(m, c, groups):
+        return lib.srx_bn_act_bwd(fake, fake, fake, fake, fake, fake, fake, fake, m, c, groups, 0, 0.0, None, 1, None, None, None,
+                                  fake, 1 << 30, None)
+
+    assert train_fwd(36, 1153, 64, 2) != 0 and 'do not split' in err()          # rows % groups
+    assert train_fwd(37, 1152, 64, 2) != 0 and 'partial rows' in err()          # table rows % groups
+    assert train_fwd(36, 1152, 64, 0) != 0 and 'groups' in err()
+    assert train_fwd(36, 1152, 64, 65) != 0 and 'groups' in err()
+    assert act_bwd(1153, 64, 2) != 0 and 'do not split' in err()
+    assert act_bwd(1152 + 32, 64, 2) != 0 and 'straddle' in err()               # 592 rows per group: not whole 32-row blocks
+    assert act_bwd(65536 + 128, 64, 2) != 0 and 'straddle' in err()             # 128-row blocks, 32832 rows per group
+    for c in (0, 2, 6, 1028, 2048, -4):
+        assert train_fwd(36, 1152, c, 1) != 0 and 'multiple of 4' in err(), c
+        assert act_bwd(1152, c, 1) != 0 and 'multiple of 4' in err(), c
+        assert lib.srx_bn_partial_stats(fake, fake, 1152, c, None) != 0 and 'multiple of 4' in err(), c
+        assert lib.srx_bn_act_fwd(fake, fake, fake, fake, fake, None, fake, 1152, c, 0, 0.0, None, None) != 0 and 'multiple of 4' in err(), c
+        assert lib.srx_bn_act_bwd_reduce(fake, fake, fake, fake, fake, fake, fake, 1152, c, 0, 0.0, None, None, None, None, fake,
+                                         1 << 30, None) != 0 and 'multiple of 4' in err(), c
+        assert lib.srx_bn_act_bwd_apply(fake, fake, fake, fake, fake, fake, fake, fake, 1152, c, 0, 0.0, None, 1, None) != 0 and 'multiple of 4' in err(), c
+        assert lib.srx_bn_act_bwd_finish(fake, fake, fake, fake, fake, fake, fake, 36, 1, fake, fake, 1152, c, 0, 0.0, None, None, None,
+                                         None, None) != 0 and 'multiple of 4' in err(), c
+    # the row-block regimes the tests' bounds and the group check rest on
+    assert [lib.srx_bn_rows_per_block(m) for m in (1, 32767, 32768, 131071, 131072, 1 << 22)] == [32, 32, 128, 128, 512, 512]
+    assert lib.srx_bn_stat_rows(32767) == 1024 and lib.srx_bn_stat_rows(32768) == 256 and lib.srx_bn_stat_rows(131072) == 256
