@@ -12,7 +12,9 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('SRX_LIB') or os.path.join(CSRC, 'libsrx_hip.so')  # SRX_LIB: developer A/B builds on one GPU box
-SOURCES = ['api.cpp', 'gconv.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip']
+SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip']
+# headers the sources include, relative to CSRC: part of the build's digest and of every object's cache key
+HEADERS = ['srx_common.h', 'conv_host.h', os.path.join('..', '..', 'include', 'srx.h')]
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_PRELU = 0, 1, 2, 3
 
@@ -50,7 +52,7 @@ def source_digest() -> str:
     """sha256 over every source of the library (names + bytes, fixed order): the identity of a build."""
     import hashlib
     h = hashlib.sha256()
-    for name in SOURCES + ['srx_common.h', os.path.join('..', '..', 'include', 'srx.h')]:
+    for name in SOURCES + HEADERS:
         h.update(os.path.basename(name).encode() + b'\0')
         with open(os.path.join(CSRC, name), 'rb') as f:
             h.update(f.read())
@@ -80,7 +82,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     A build is identified by the sha256 of its sources, compiled into the library (``srx_build_info``): an existing
     library is reused only when it carries the digest of the sources lying next to it -- never by file times.
     ``force`` (or ``SRX_FORCE_BUILD=1``) recompiles every translation unit.  Objects are compiled in parallel into
-    ``csrc/build/`` and cached per source digest, so an edit recompiles one file."""
+    ``csrc/build/`` and cached per digest of the source and the headers it includes, so an edit recompiles what it touches."""
     import hashlib
     from concurrent.futures import ThreadPoolExecutor
     force = force or os.environ.get('SRX_FORCE_BUILD') == '1'
@@ -91,16 +93,26 @@ def build(force: bool = False, verbose: bool = False) -> str:
     objdir = os.path.join(CSRC, 'build')
     os.makedirs(objdir, exist_ok=True)
     flags = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
-    with open(os.path.join(CSRC, 'srx_common.h'), 'rb') as f:
-        hdr = f.read()
-    with open(os.path.join(_HERE, '..', 'include', 'srx.h'), 'rb') as f:
-        hdr += f.read()
+    hdr = {}
+    for name in HEADERS:
+        with open(os.path.join(CSRC, name), 'rb') as f:
+            hdr[name] = f.read()
+
+    def included(text, found):
+        """The HEADERS that ``text`` includes, directly or through one of them, in the order met."""
+        for name in HEADERS:
+            if name not in found and b'#include "%s"' % name.encode() in text:
+                found.append(name)
+                included(hdr[name], found)
+        return found
 
     def compile_one(name):
         src = os.path.join(CSRC, name)
         extra = ['-DSRX_SOURCES_SHA256="%s"' % digest] if name == 'api.cpp' else []
         with open(src, 'rb') as f:
-            key = hashlib.sha256(hdr + f.read() + ' '.join(flags + extra).encode()).hexdigest()[:24]
+            text = f.read()
+        seen = b''.join(hdr[h] for h in included(text, []))  # an edit to a header recompiles the units that see it
+        key = hashlib.sha256(seen + text + ' '.join(flags + extra).encode()).hexdigest()[:24]
         obj = os.path.join(objdir, f'{os.path.splitext(name)[0]}.{key}.o')
         if force or not os.path.exists(obj):
             for stale in os.listdir(objdir):

@@ -53,7 +53,7 @@ bool srx_prof_take(const char* name, double flops, hipEvent_t* e0, hipEvent_t* e
       hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);                                 \
   } while (0)
 
-// thin.hip: 3-channel-side convolutions on v_mfma_f32_4x4x1 (internal, called from gconv.hip)
+// thin.hip: 3-channel-side convolutions on v_mfma_f32_4x4x1 (internal, called from gconv.hip, wgrad.hip and convpack.hip)
 bool srx_thin_wgrad_applicable(const srx_conv2d_t* d);
 size_t srx_thin_wgrad_ws_floats(const srx_conv2d_t* d);
 int srx_thin_wgrad(const srx_conv2d_t* d, const float* x, const float* dy, float* dw, int accumulate, float* ws,
@@ -122,12 +122,12 @@ __device__ __forceinline__ float srx_wave_sum(float v) {
 }
 
 // wino.hip's weight transform for ONE (row channel, contraction channel) pair `idx` (U = G g G^T, sixteen values scattered to
-// where wino_kernel's waves load them); shared with gconv.hip's pack_table_kernel, which refreshes the Winograd-domain weights
+// where wino_kernel's waves load them); shared with convpack.hip's pack_table_kernel, which refreshes the Winograd-domain weights
 // of trainable layers after an optimiser step.  transpose = 1: the layer's data gradient (channels swapped, taps flipped).
 __device__ __forceinline__ void srx_wino_pack_one(const float* __restrict__ w, float* __restrict__ upk, int Cout, int Cin,
                                                   int transpose, int64_t idx) {
   // transpose: 0 the layer; 1 its data gradient; 2 the layer with a PixelShuffle(2) store: GEMM row r = (sub-pixel ij, channel cc)
-  // is the conv's output channel cc * 4 + ij (the order gconv.hip's packs use), so a lane's four consecutive rows are four
+  // is the conv's output channel cc * 4 + ij (the order convpack.hip's packs use), so a lane's four consecutive rows are four
   // consecutive channels of ONE output pixel
   const int R = transpose == 1 ? Cin : Cout, K = transpose == 1 ? Cout : Cin;  // rows (the GEMM's channels out) and contraction length
   const int r = (int)(idx / K), k = (int)(idx - (int64_t)r * K);

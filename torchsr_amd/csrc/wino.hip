@@ -114,7 +114,7 @@ __global__ __launch_bounds__(WINO_THREADS, 2) void wino_kernel(const WinoArgs a)
   const int tid = threadIdx.x, lane = tid & 63, wave = srx_uniform(tid >> 6);
   const int h = lane >> 5, l31 = lane & 31;
   // Work item = (split, channel block, tile block), tile blocks fastest.  Workgroups are dealt round-robin over the 8 XCDs; this
-  // remap gives every XCD a contiguous run of items (as gconv.hip's weight-gradient kernels do) -- the tile blocks of a run share
+  // remap gives every XCD a contiguous run of items (as wgrad.hip's weight-gradient kernels do) -- the tile blocks of a run share
   // their U block and their halo rows in ONE L2 (a speed matter only: with the plain order every XCD pulled all of U through the
   // fabric, 142 MB of HBM reads for a 512 -> 512 layer whose operands are 22 MB; PMC, round 5)
   int b = (int)blockIdx.x;

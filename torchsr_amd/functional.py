@@ -60,7 +60,7 @@ class WeightGradQueue:
     and fake passes) become segments of one gradient.  Only gradients that accumulate straight into the flat
     ``.grad`` buffers are deferred; the queued tensors stay alive until the flush.
     """
-    MAXP = 72  # WG_MAXP of gconv.hip
+    MAXP = 72  # WG_MAXP of wgrad.hip
 
     def __init__(self):
         self.groups = {}
