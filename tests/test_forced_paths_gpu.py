@@ -304,6 +304,93 @@ def test_forced_strided_forms_a_layer_cannot_run_are_refused(dev):
             _lib.call('srx_conv2d_force_plan', *bad)
 
 
+# ------------------------------------------------------------------ b. single-launch convs (gconv_kernel) under forced tiles
+class DenseLayer:
+    """3x3 / stride 1 / pad 1, 128 -> 128 channels, N = 2, 22 x 18: M = 792 leaves a ragged last row tile for every BM
+    (792 = 5 x 144 + 72 = 6 x 128 + 24 = 12 x 64 + 24 = 3 x 256 + 24), every BN divides the 128 padded columns, K = 1152 is 36
+    chunks (a forced split of 3: 12 each).  Neither the 36-pixel row-tile shape nor a thin layer.  Forward (with bias) and data
+    gradient against the fp64 convolution of bf16-rounded (precision 1) or plain fp32 operands."""
+    N, H, W, CH = 2, 22, 18, 128
+
+    def __init__(self, prec, dev):
+        from torchsr_amd import _lib
+        L = _lib.lib()
+        n, h, w, c = self.N, self.H, self.W, self.CH
+        self.d = _lib.Conv2dDesc(n, h, w, c, c, c, c, 3, 3, 1, 1, 0, 0, 0.0, 0, prec)
+        g = torch.Generator().manual_seed(792 + prec)
+        wt = torch.randn(c, c, 3, 3, generator=g) * 0.05
+        x = torch.randn(n, h, w, c, generator=g)
+        dy = torch.randn(n, h, w, c, generator=g)
+        bias = torch.randn(c, generator=g)
+        self.x, self.dy, self.bias = x.to(dev), dy.to(dev), bias.to(dev)
+        self.wf = torch.empty(L.srx_conv2d_packed_fwd_floats(C.byref(self.d)), device=dev)
+        self.wb = torch.empty(L.srx_conv2d_packed_bwd_floats(C.byref(self.d)), device=dev)
+        wg = wt.to(dev)
+        _lib.call('srx_conv2d_pack', C.byref(self.d), wg.data_ptr(), self.wf.data_ptr(), self.wb.data_ptr(), _stream())
+        r = (lambda t: t.bfloat16().double()) if prec else (lambda t: t.double())
+        y = torch.nn.functional.conv2d(r(x.permute(0, 3, 1, 2)), r(wt), bias.double(), padding=1)
+        dx = torch.nn.grad.conv2d_input((n, c, h, w), r(wt), r(dy.permute(0, 3, 1, 2)), padding=1)
+        self.want = [y.permute(0, 2, 3, 1).contiguous(), dx.permute(0, 2, 3, 1).contiguous()]   # NHWC, fp64
+        torch.cuda.synchronize()
+
+    def run(self, which):
+        """Forward (which = 0) or data gradient (1) into a NaN-filled output, the split-K workspace NaN-filled too."""
+        from torchsr_amd import _lib
+        L = _lib.lib()
+        need = (L.srx_conv2d_bwd_data_ws_floats if which else L.srx_conv2d_fwd_ws_floats)(C.byref(self.d))
+        ws = torch.full((max(need, 4),), float('nan'), device=self.x.device)
+        out = torch.full((self.N, self.H, self.W, self.CH), float('nan'), device=self.x.device)
+        if which:
+            _lib.call('srx_conv2d_bwd_data', C.byref(self.d), self.dy.data_ptr(), self.wb.data_ptr(), out.data_ptr(), 0,
+                      ws.data_ptr(), need, _stream())
+        else:
+            _lib.call('srx_conv2d_fwd', C.byref(self.d), self.x.data_ptr(), self.wf.data_ptr(), self.bias.data_ptr(), out.data_ptr(),
+                      None, ws.data_ptr(), need, _stream())
+        return out, need
+
+
+@functools.lru_cache(maxsize=None)
+def _dense_layer(prec):
+    return DenseLayer(prec, torch.device('cuda:0'))
+
+
+# (precision, BM, BN, KS asked for, KS of the kernel): the 64 x 32 tile deals its k-chunks to 2 (fp32) / 4 (bf16) wave groups
+SINGLE_TILES = [(0, 144, 128, 1, 1), (0, 144, 64, 1, 1), (0, 128, 128, 1, 1), (0, 128, 64, 1, 1), (0, 64, 64, 1, 1),
+                (0, 64, 64, 2, 2), (0, 64, 32, 1, 2), (0, 128, 32, 1, 1),
+                (1, 256, 128, 1, 1), (1, 128, 128, 1, 1), (1, 128, 64, 1, 1), (1, 64, 64, 1, 1), (1, 64, 64, 2, 2),
+                (1, 128, 32, 1, 1), (1, 64, 32, 1, 4)]
+
+
+@pytest.mark.parametrize('prec,bm,bn,ks_arg,ks', SINGLE_TILES, ids=lambda v: str(v))
+def test_forced_tiles_on_single_launch_convs(dev, prec, bm, bn, ks_arg, ks):
+    """Every gconv_kernel tile a plan can ask for at fp32 / bf16 products, forced on a stride-1 layer's forward and data
+    gradient, whole (split 1) and with every tile cut three ways along K (split 3): the reported plan, the launch that ran and
+    the numbers.  The fix-up pass of a split plan (tail_fixup_kernel) is not a recorded launch, so the recorder shows the
+    gconv_kernel launch alone; that the fix-up ran after it is shown by the output: under a forced split every tile's partial
+    sums go to the workspace and tail_fixup_kernel alone writes the output tensor, which starts as NaN (the workspace too)."""
+    from torchsr_amd import _lib
+    lay = _dense_layer(prec)
+    m, c = lay.N * lay.H * lay.W, lay.CH
+    head, _, wm, wn, xr = _tile_args(bm, bn)
+    if bm == 256:
+        wn = 64   # (the 256-row tile: 64 x 64 per wave)
+    name = f'gconv_kernel<{head}, {bn}, {wm}, {wn}, {ks}, {xr}, {prec}> MxNxK={m}x{c}x{9 * c}'
+    for split in (1, 3):
+        _lib.call('srx_conv2d_force_plan', bm, bn, split, ks_arg)
+        for which in (0, 1):
+            assert _plan(lay.d, which) == [bm, bn, split, -(-m // bm) * (c // bn) * split, ks, 0], (_plan(lay.d, which), split, which)
+            holder = []
+            names = _launched(lambda: holder.append(lay.run(which)))
+            out, need = holder[0]
+            assert names == [name], (names, name, split, which)
+            assert need == (0 if split == 1 else -(-m // bm) * (c // bn) * split * bm * bn), (need, split, which)
+            torch.cuda.synchronize()
+            assert not torch.isnan(out).any(), (split, which)
+            err = rel_err(out, lay.want[which])
+            print(f'prec {prec} tile {bm}x{bn} ks {ks} split {split} which {which}: rel err {err:.3g}')
+            assert err < 1e-5, (split, which, err)
+
+
 # ------------------------------------------------------------------ c. the LIN weight gradient
 def _wgrad(dev, n, h, w, cin, cout, k, nsplit=0, nprob=1, accumulate=0, lin_names=True):
     """fp32 stride-1 same-size layer(s): the LIN and the plain WIDE form of wgrad_dma_kernel (forced), bit for bit against each

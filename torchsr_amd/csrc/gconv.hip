@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -1289,7 +1290,74 @@ namespace {
 // unless they leave the chip under-filled.
 struct Plan { int BM, BN, mtiles, ntiles, tiles, full, tail, split, kc_per_split, ks; float cost; bool refused; };
 
-int device_cus() { return srx_plan_cus(); }  // the device's CUs less the reserved ones (api.cpp)
+// The tile table: every (BM, BN) tile a plan may name, the template head it launches and the instantiations that exist.  The
+// planners, the forced-plan refusals, the argument checks of srx_conv2d_force_plan / srx_conv2d_force_s2 and the dispatchers
+// read this table and nothing else: a new instantiation is one more entry in a row's `ks`, a new tile one more row.  The ORDER
+// is the planners' candidate order -- they pick with a strict <, so the earlier row wins a tie.
+enum Family { F_GCONV, F_BIG, F_MULTI, F_S2F, NFAM };  // gconv_kernel, gconv_kernel BIG, gconv_multi_kernel, gconv_s2f_kernel
+constexpr unsigned char K1 = 1, K2 = 2, K4 = 4, K12 = K1 | K2;  // sets of wave-group counts KS: a bit's value is the count
+struct Tile {
+  int BM, BN, WM, WN, XR;  // the planner's tile, rows x columns per wave, extension rows: the template head is <BM - XR, BN, WM, WN, .., XR>
+  float eff;               // measured MFMA efficiency in steady state
+  unsigned char ks[NFAM][4];  // [family][PR = 0 fp32, 1 bf16 products, 2 bf16 storage, 3 fp16 products]: the KS instantiated; 0: none
+};
+// (144, *): 128 rows + a 16-row extension, fp32 only
+// (64, 32): narrow layers (the 32-channel growth convs of ESRGAN's dense blocks) on twice as many tiles, the
+// k-chunks of each tile split over 2 (fp32) / 4 (bf16) wave groups inside the workgroup -- no fix-up pass
+// (256, 128), bf16 only (round 4): 64 x 64 per wave, one LDS fragment read per MFMA instead of 1.5 -- the bf16 loop is bound
+// by LDS traffic: 256 -> 256 at 32 x 32 x 32 pixels 560 -> 650 TFLOP/s, 128 -> 256 at 64^2 484 -> 546; with fp32 products the
+// same tile LOSES a third (72 vs 110 TFLOP/s: 212 registers, and nothing there was LDS-bound) and is never planned
+constexpr Tile kTiles[] = {
+    // BM, BN, WM, WN, XR, eff, {gconv_kernel, its BIG form (whole frames), gconv_multi_kernel, gconv_s2f_kernel}
+    {144, 128, 64, 32, 16, 0.91f, {{K1}, {}, {K1}, {K1}}},
+    {144, 64, 32, 32, 16, 0.82f, {{K1}, {}, {K1}, {K1}}},
+    {128, 128, 64, 32, 0, 0.95f, {{K1, K1, K1, K1}, {K1, K1, 0, K1}, {K1, K1}, {K1, K1}}},
+    {128, 64, 32, 32, 0, 0.85f, {{K1, K1, K1, K1}, {K1, K1, 0, K1}, {K1, K1}, {K1, K1}}},
+    {64, 64, 32, 32, 0, 0.60f, {{K12, K12, K12, K12}, {}, {K12, K12}, {K1, K1}}},
+    {128, 32, 32, 32, 0, 0.50f, {{K1, K1, 0, K1}, {K1, K1, 0, K1}, {K1, K1}, {}}},
+    {64, 32, 32, 32, 0, 0.50f, {{K2, K4, 0, K4}}},
+    {256, 128, 64, 64, 0, 1.08f, {{0, K1, K1, K1}}},
+};
+constexpr int NTILES = sizeof(kTiles) / sizeof(kTiles[0]);
+
+const Tile* find_tile(int bm, int bn) {
+  const Tile* t = std::find_if(kTiles, kTiles + NTILES, [&](const Tile& x) { return x.BM == bm && x.BN == bn; });
+  return t != kTiles + NTILES ? t : nullptr;
+}
+// does family f have tile bm x bn with ks (1 / 2 / 4; 0: any number of) wave groups at arithmetic pr?
+bool has_tile(Family f, int bm, int bn, int ks, int pr) {
+  const Tile* t = find_tile(bm, bn);
+  return t && (t->ks[f][pr] & (ks ? ks : K1 | K2 | K4)) != 0;
+}
+// bm is the rows of one of family f's tiles and bn the columns of one: what the force calls take (whether the pair is a tile,
+// and one the layer can run, is answered per layer, with a reason)
+bool tile_sides_known(Family f, int bm, int bn) {
+  bool rows = false, cols = false;
+  for (const Tile& t : kTiles)
+    if (t.ks[f][0] | t.ks[f][1] | t.ks[f][2] | t.ks[f][3]) { rows |= t.BM == bm; cols |= t.BN == bn; }
+  return rows && cols;
+}
+// wave groups of tile t in family f at arithmetic pr: the one count it is instantiated with (64 x 32: 2 in fp32, 4 in bf16) or,
+// where it has one and two (64 x 64), two when `two` says so
+int tile_ks(const Tile& t, Family f, int pr, bool two) {
+  const int have = t.ks[f][pr];
+  return have == K12 ? (two ? 2 : 1) : have ? have : 1;
+}
+// the 32-column tiles are for the layers of 32 padded columns, which take no other; elsewhere the tile's columns divide the layer's
+bool columns_fit(int Cnp, int bn) { return Cnp == 32 ? bn == 32 : (bn != 32 && Cnp % bn == 0); }
+
+// microseconds for one whole tile of `chunks` k-chunks on an otherwise idle CU (4 SIMDs x 64 FLOP/clk at ~2.1 GHz).  bf16 products:
+// the loop is bound by the fp32 operand stream, not by the matrix pipe, and runs ~3x the fp32 rate (measured
+// 240-360 vs ~105 TFLOP/s on the VGG layers) -- the fixed cost of a K-split fix-up pass weighs 3x more
+float tile_us(int bm, int bn, int chunks, float eff, bool bf16) {
+  return 2.0f * bm * bn * (float)chunks * BK / (4 * 64 * 2.1e3f) / eff / (bf16 ? 3.0f : 1.0f);
+}
+
+// dynamic LDS of a launch: KS x 3 stages of the tile's operand rows (2-byte elements under bf16 / fp16 products) and, for
+// gconv_kernel / gconv_multi_kernel, the k-table of the longest K range; for gconv_s2f_kernel, the classes' k-positions and a word per row
+size_t stage_bytes(int bm, int bn, int ks, int pr) { return (size_t)(ks * 3 * (bm + bn) * BK) * (pr == 1 || pr == 3 ? 2 : 4); }
+size_t gconv_lds_bytes(int bm, int bn, int ks, int pr, int chunks) { return stage_bytes(bm, bn, ks, pr) + (size_t)chunks * 8 * sizeof(int2); }
+size_t s2f_lds_bytes(int bm, int bn, int pr, int pos) { return stage_bytes(bm, bn, 1, pr) + (size_t)(pos + 3) * sizeof(int4) + (size_t)srx_roundup(bm, 4) * 4; }
 
 bool forced_plan(int& bm, int& bn, int& sp, int& ks) {
   ConvForce& f = conv_force();
@@ -1298,46 +1366,29 @@ bool forced_plan(int& bm, int& bn, int& sp, int& ks) {
   return bn > 0;
 }
 
-// nullptr: gconv_kernel (multi = false) / gconv_multi_kernel (multi = true) has an instantiation for tile bm x bn with ks wave
+// nullptr: family f (gconv_kernel / gconv_multi_kernel) has an instantiation for tile bm x bn with ks wave
 // groups at this arithmetic and the tile's columns divide the layer's padded ones; otherwise why not
-const char* forced_tile_refusal(int bm, int bn, int ks, int Cnp, bool bf16, bool multi) {
+const char* forced_tile_refusal(Family f, int bm, int bn, int ks, int Cnp, bool bf16) {
   if (Cnp % bn != 0) return "the tile's columns do not divide the layer's padded output columns";
-  if (ks == 2 && !(bm == 64 && (bn == 64 || bn == 32))) return "two wave groups (KS = 2) on a tile other than 64 x 64 / 64 x 32";
+  const Tile* t = find_tile(bm, bn);
+  if (ks == 2 && !(t && (t->ks[F_GCONV][0] & (K2 | K4)))) return "two wave groups (KS = 2) on a tile other than 64 x 64 / 64 x 32";
   if (bf16 && bm == 144) return "no 144-row tile with bf16 products";
   if (!bf16 && bm == 256) return "no 256-row tile with fp32 products";
-  const bool known = (bm == 144 && (bn == 128 || bn == 64)) || (bm == 128 && (bn == 128 || bn == 64 || bn == 32)) ||
-                     (bm == 64 && bn == 64) || (!multi && bm == 64 && bn == 32) || (!multi && bm == 256 && bn == 128);
-  return known ? nullptr : "no instantiation of this tile";
+  return has_tile(f, bm, bn, 0, bf16 ? 1 : 0) ? nullptr : "no instantiation of this tile";
 }
 
 Plan make_plan(int M, int Cnp, int kchunks, bool can_split, bool bf16 = false, bool big = false) {
-  const int P = device_cus();
-  constexpr int NC = 8;
-  // (64, 32): narrow layers (the 32-channel growth convs of ESRGAN's dense blocks) on twice as many tiles, the
-  // k-chunks of each tile split over 2 (fp32) / 4 (bf16) wave groups inside the workgroup -- no fix-up pass
-  // (256, 128), bf16 only (round 4): 64 x 64 per wave, one LDS fragment read per MFMA instead of 1.5 -- the bf16 loop is bound
-  // by LDS traffic: 256 -> 256 at 32 x 32 x 32 pixels 560 -> 650 TFLOP/s, 128 -> 256 at 64^2 484 -> 546; with fp32 products the
-  // same tile LOSES a third (72 vs 110 TFLOP/s: 212 registers, and nothing there was LDS-bound) and is never planned
-  const int cand[NC][2] = {{144, 128}, {144, 64}, {128, 128}, {128, 64}, {64, 64}, {128, 32}, {64, 32}, {256, 128}};
-  const float eff[NC] = {0.91f, 0.82f, 0.95f, 0.85f, 0.60f, 0.50f, 0.50f, 1.08f};  // measured MFMA efficiency in steady state
+  const int P = srx_plan_cus();  // the device's CUs less the reserved ones (api.cpp)
+  const Family fam = big ? F_BIG : F_GCONV;  // (whole-frame calls, the BIG instantiations: 128 x {128, 64, 32})
+  const int pr = bf16 ? 1 : 0;
   Plan best{};
   best.cost = 1e30f;
-  for (int i = 0; i < NC; ++i) {
-    const int bm = cand[i][0], bn = cand[i][1];
-    if (bf16 && bm == 144) continue;
-    if (!bf16 && bm == 256) continue;
-    if (big && bm != 128) continue;  // whole-frame calls (BIG instantiations): 128 x {128, 64, 32}
-    if (Cnp == 32) { if (bn != 32) continue; }
-    else if (bn == 32 || Cnp % bn != 0) continue;
+  for (const Tile& t : kTiles) {
+    const int bm = t.BM, bn = t.BN;
+    if (!t.ks[fam][pr] || !columns_fit(Cnp, bn)) continue;
     Plan p{};
-    p.BM = bm; p.BN = bn;
-    p.mtiles = (int)srx_cdiv(M, bm);
-    p.ntiles = Cnp / bn;
-    p.tiles = p.mtiles * p.ntiles;
-    // microseconds for one whole tile on an otherwise idle CU (4 SIMDs x 64 FLOP/clk at ~2.1 GHz).  bf16 products:
-    // the loop is bound by the fp32 operand stream, not by the matrix pipe, and runs ~3x the fp32 rate (measured
-    // 240-360 vs ~105 TFLOP/s on the VGG layers) -- the fixed cost of a K-split fix-up pass weighs 3x more
-    const float t_tile = 2.0f * bm * bn * (float)kchunks * BK / (4 * 64 * 2.1e3f) / eff[i] / (bf16 ? 3.0f : 1.0f);
+    p.BM = bm; p.BN = bn; p.mtiles = (int)srx_cdiv(M, bm); p.ntiles = Cnp / bn; p.tiles = p.mtiles * p.ntiles;
+    const float t_tile = tile_us(bm, bn, kchunks, t.eff, bf16);
     const int rounds = p.tiles / P, r = p.tiles % P;
     p.full = rounds * P; p.tail = r; p.split = 1; p.kc_per_split = kchunks;
     float tail_cost = r ? t_tile : 0.f;
@@ -1361,7 +1412,7 @@ Plan make_plan(int M, int Cnp, int kchunks, bool can_split, bool bf16 = false, b
   int bm, bn, sp, ks;
   if (!big && forced_plan(bm, bn, sp, ks)) {
     Plan p{};
-    if (const char* why = forced_tile_refusal(bm, bn, ks, Cnp, bf16, false)) {
+    if (const char* why = forced_tile_refusal(F_GCONV, bm, bn, ks, Cnp, bf16)) {
       srx_set_error("conv2d: forced plan %d x %d (KS %d) refused: %s (%d padded columns, %s products)", bm, bn, ks, why, Cnp,
                     bf16 ? "bf16" : "fp32");
       p.refused = true;
@@ -1370,14 +1421,12 @@ Plan make_plan(int M, int Cnp, int kchunks, bool can_split, bool bf16 = false, b
     p.BM = bm; p.BN = bn; p.mtiles = (int)srx_cdiv(M, bm); p.ntiles = Cnp / bn; p.tiles = p.mtiles * p.ntiles;
     if (sp > 1 && can_split) { p.full = 0; p.tail = p.tiles; p.kc_per_split = (int)srx_cdiv(kchunks, sp); p.split = (int)srx_cdiv(kchunks, p.kc_per_split); }
     else { p.full = p.tiles; p.tail = 0; p.split = 1; p.kc_per_split = kchunks; }
-    p.ks = (bm == 64 && bn == 64 && ks == 2) ? 2 : 1;
-    if (bm == 64 && bn == 32) p.ks = bf16 ? 4 : 2;
+    p.ks = tile_ks(*find_tile(bm, bn), F_GCONV, pr, ks == 2);
     return p;
   }
-  // fewer workgroups than CUs and a 4-wave tile: split its k-chunks over two wave groups (KS = 2)
-  best.ks = (best.BM == 64 && best.BN == 64 && best.full + best.tail * best.split <= P && best.kc_per_split >= 4) ? 2 : 1;
-  if (best.BM == 64 && best.BN == 32) best.ks = bf16 ? 4 : 2;
-  if (big) best.ks = 1;
+  // fewer workgroups than CUs and a 4-wave tile (64 x 64): split its k-chunks over two wave groups (KS = 2)
+  const Tile* t = find_tile(best.BM, best.BN);
+  best.ks = t ? tile_ks(*t, fam, pr, best.full + best.tail * best.split <= P && best.kc_per_split >= 4) : 1;
   return best;
 }
 
@@ -1386,7 +1435,7 @@ size_t plan_ws_floats(const Plan& p) { return p.split > 1 ? (size_t)p.tail * p.s
 template <int BM, int BN, int WM, int WN, int KS, int XR, int PR = 0, int BIG = 0>
 int launch_gconv(const GArgs& a, const Plan& p, hipStream_t st) {
   const int ktab_chunks = p.full > 0 || p.split == 1 ? a.kchunks : p.kc_per_split;
-  const size_t lds = (size_t)(KS * 3 * (BM + XR + BN) * BK) * (PR == 1 || PR == 3 ? 2 : 4) + (size_t)ktab_chunks * 8 * sizeof(int2);
+  const size_t lds = gconv_lds_bytes(BM + XR, BN, KS, PR, ktab_chunks);
   if (lds > 160 * 1024) SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: K range needs %zu bytes of LDS", lds);
   static std::once_flag once;
   std::call_once(once, [] {
@@ -1427,36 +1476,72 @@ int launch_gconv_multi(const GMulti& m, size_t lds, hipStream_t st) {
   return SRX_OK;
 }
 
+template <int BM, int BN, int WM, int WN, int XR, int PR>
+int launch_gconv_s2f(const GFused& f, dim3 grid, size_t lds, double fl, hipStream_t st) {
+  static std::once_flag once;
+  std::call_once(once, [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gconv_s2f_kernel<BM, BN, WM, WN, XR, PR>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  });
+  char nm[64];
+  if (srx_prof_on()) snprintf(nm, sizeof(nm), "gconv_s2f_kernel<%d, %d, %d, %d, %d, %d>", BM, BN, WM, WN, XR, PR);
+  SRX_LAUNCH_PROF(nm, fl, (gconv_s2f_kernel<BM, BN, WM, WN, XR, PR>), grid, dim3((BM / WM) * (BN / WN) * 64), lds, st, f);
+  SRX_CHECK_LAUNCH("gconv_s2f_kernel");
+  return SRX_OK;
+}
+
+// Dispatch: the run-time (BM, BN, KS, PR) of a plan to the one instantiation of family F the table lists for it -- and only the
+// listed ones are instantiated (every gconv_kernel costs seconds of build time).  `args` are the launcher's own.
+struct TileKey { int bm, bn, ks, pr; };
+
+// instantiation (row I, PR, KS) of family F: launched (status in rc) if the table has it and k names it; false: not this one
+template <int F, int I, int PR, int KS, class... A>
+bool launch_if(const TileKey& k, int& rc, const A&... args) {
+  constexpr Tile t = kTiles[I];
+  if constexpr ((t.ks[F][PR] & KS) != 0) {
+    if (k.bm != t.BM || k.bn != t.BN || k.ks != KS || k.pr != PR) return false;
+    if constexpr (F == F_MULTI) rc = launch_gconv_multi<t.BM - t.XR, t.BN, t.WM, t.WN, t.XR, PR, KS>(args...);
+    else if constexpr (F == F_S2F) rc = launch_gconv_s2f<t.BM - t.XR, t.BN, t.WM, t.WN, t.XR, PR>(args...);
+    else rc = launch_gconv<t.BM - t.XR, t.BN, t.WM, t.WN, KS, t.XR, PR, F == F_BIG>(args...);
+    return true;
+  }
+  return false;
+}
+// every (row, PR, KS) the table could list, J = (row * 4 + PR) * 3 + log2 KS; false: family F has no kernel for k, nothing launched
+using Listable = std::make_integer_sequence<int, NTILES * 12>;
+template <int F, int... J, class... A>
+bool launch_tile(std::integer_sequence<int, J...>, const TileKey& k, int& rc, const A&... args) {
+  return (launch_if<F, J / 12, J / 3 % 4, 1 << J % 3>(k, rc, args...) || ...);
+}
+
 // Tile for a multi-problem launch.  The stride-parity classes of a data gradient have the same M but
 // 1x..4x different K, and their strided outputs cannot take the split-K fix-up path, so balance comes
 // from the tile size alone: every candidate's workgroups are list-scheduled heavy-first (the order
 // run_gconv_multi launches them in) over the CUs and the shortest makespan wins.  A forced plan (srx_conv2d_force_plan) costs 0;
 // one without a gconv_multi_kernel instantiation returns -1 with the message set.
 float multi_tile(const GMulti& m, int Cnp, int& BM, int& BN, int& KS, bool bf16 = false) {
-  const int P = device_cus();
-  constexpr int NC = 7;
-  // (the last candidate: 64 x 64 with the k-chunks of a tile dealt to two wave groups -- half the chain, one workgroup per CU)
-  const int cand[NC][2] = {{144, 128}, {144, 64}, {128, 128}, {128, 64}, {64, 64}, {128, 32}, {64, 64}};
-  const float eff[NC] = {0.91f, 0.82f, 0.95f, 0.85f, 0.60f, 0.50f, 0.80f};
+  const int P = srx_plan_cus();
+  const int pr = bf16 ? 1 : 0;
   float best = 1e30f;
   BM = 128; BN = Cnp == 32 ? 32 : 64; KS = 1;
   int fbm, fbn, fsp, fks;
   if (forced_plan(fbm, fbn, fsp, fks)) {
-    if (const char* why = forced_tile_refusal(fbm, fbn, fks, Cnp, bf16, true)) {
+    if (const char* why = forced_tile_refusal(F_MULTI, fbm, fbn, fks, Cnp, bf16)) {
       srx_set_error("conv2d_bwd_data: forced plan %d x %d (KS %d) refused for gconv_multi_kernel: %s (%d padded columns, %s products)",
                     fbm, fbn, fks, why, Cnp, bf16 ? "bf16" : "fp32");
       return -1.f;
     }
-    BM = fbm; BN = fbn; KS = (BM == 64 && BN == 64 && fks == 2) ? 2 : 1;
+    BM = fbm; BN = fbn; KS = tile_ks(*find_tile(fbm, fbn), F_MULTI, pr, fks == 2);
     return 0.f;
   }
   std::vector<float> heap;
-  for (int i = 0; i < NC; ++i) {
-    const int bm = cand[i][0], bn = cand[i][1];
-    if (bf16 && bm == 144) continue;  // (the 16-row extension is fp32 only)
-    if (i == 6 && (srx_dev().s2_mode & 2)) continue;
-    if (Cnp == 32) { if (bn != 32) continue; }
-    else if (bn == 32 || Cnp % bn != 0) continue;
+  // every tile on one wave group; then, last, the tiles that have two (64 x 64: the k-chunks of a tile dealt to two wave
+  // groups -- half the chain, one workgroup per CU)
+  for (int i = 0; i < 2 * NTILES; ++i) {
+    const Tile& tile = kTiles[i % NTILES];
+    const int bm = tile.BM, bn = tile.BN, ks = 1 + i / NTILES;
+    if (!(tile.ks[F_MULTI][pr] & ks) || !columns_fit(Cnp, bn)) continue;
+    if (ks == 2 && (srx_dev().s2_mode & 2)) continue;
     heap.assign(P, 0.f);  // min-heap of CU finish times
     auto later = [](float x, float y) { return x > y; };
     float makespan = 0.f;
@@ -1468,8 +1553,8 @@ float multi_tile(const GMulti& m, int Cnp, int& BM, int& BN, int& KS, bool bf16 
         if (rank != pass) continue;
         // (see make_plan; the two-group tile: half the chain at 0.8, and a fixed cost nothing overlaps -- set-up and fold of a
         // 512-thread workgroup that has the CU to itself: measured ~6.5 us on the discriminator's layers)
-        const float t = 2.0f * bm * bn * (float)kch * BK / (4 * 64 * 2.1e3f) / (bf16 ? 3.0f : 1.0f);
-        const float cost = i == 6 ? 6.5f + 0.5f * t / 0.8f : 1.0f + t / eff[i];
+        const float t = tile_us(bm, bn, kch, 1.0f, bf16);
+        const float cost = ks == 2 ? 6.5f + 0.5f * t / 0.8f : 1.0f + t / tile.eff;
         const int tiles = (int)srx_cdiv(m.g[c].M, bm) * (int)srx_cdiv(m.g[c].Cn, bn);
         for (int t = 0; t < tiles; ++t) {
           std::pop_heap(heap.begin(), heap.end(), later);
@@ -1478,7 +1563,7 @@ float multi_tile(const GMulti& m, int Cnp, int& BM, int& BN, int& KS, bool bf16 
           std::push_heap(heap.begin(), heap.end(), later);
         }
       }
-    if (makespan < best) { best = makespan; BM = bm; BN = bn; KS = i == 6 ? 2 : 1; }
+    if (makespan < best) { best = makespan; BM = bm; BN = bn; KS = ks; }
   }
   return best;
 }
@@ -1500,27 +1585,12 @@ int run_gconv_multi(GMulti& m, int BM, int BN, int KS, hipStream_t st, int preci
     m.first[i + 1] = m.first[i] + tiles;
     if (a.kchunks > maxk) maxk = a.kchunks;
   }
-  const size_t lds = (size_t)(KS * 3 * (BM + BN) * BK) * (precision ? 2 : 4) + (size_t)maxk * 8 * sizeof(int2);
+  const int pr = precision ? 1 : 0;  // (bf16 products, round 4: the stride-parity classes of a strided data gradient too)
+  const size_t lds = gconv_lds_bytes(BM, BN, KS, pr, maxk);
   if (lds > 160 * 1024) SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: K range needs %zu bytes of LDS", lds);
-  if (KS == 2) {
-    if (BM != 64 || BN != 64) SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: internal: two wave groups on a tile other than 64 x 64");
-    if (precision) return launch_gconv_multi<64, 64, 32, 32, 0, 1, 2>(m, lds, st);
-    return launch_gconv_multi<64, 64, 32, 32, 0, 0, 2>(m, lds, st);
-  }
-  if (precision) {  // bf16 products (round 4: the stride-parity classes of a strided data gradient too)
-    if (BM == 128 && BN == 128) return launch_gconv_multi<128, 128, 64, 32, 0, 1>(m, lds, st);
-    if (BM == 128 && BN == 64) return launch_gconv_multi<128, 64, 32, 32, 0, 1>(m, lds, st);
-    if (BM == 64 && BN == 64) return launch_gconv_multi<64, 64, 32, 32, 0, 1>(m, lds, st);
-    if (BM == 128 && BN == 32) return launch_gconv_multi<128, 32, 32, 32, 0, 1>(m, lds, st);
-    SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_bwd_data: no bf16 gconv_multi_kernel for tile %d x %d", BM, BN);
-  }
-  if (BM == 144 && BN == 128) return launch_gconv_multi<128, 128, 64, 32, 16>(m, lds, st);
-  if (BM == 144 && BN == 64) return launch_gconv_multi<128, 64, 32, 32, 16>(m, lds, st);
-  if (BM == 128 && BN == 128) return launch_gconv_multi<128, 128, 64, 32, 0>(m, lds, st);
-  if (BM == 128 && BN == 64) return launch_gconv_multi<128, 64, 32, 32, 0>(m, lds, st);
-  if (BM == 64 && BN == 64) return launch_gconv_multi<64, 64, 32, 32, 0>(m, lds, st);
-  if (BM == 128 && BN == 32) return launch_gconv_multi<128, 32, 32, 32, 0>(m, lds, st);
-  SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_bwd_data: no gconv_multi_kernel for tile %d x %d", BM, BN);
+  int rc = SRX_OK;
+  if (launch_tile<F_MULTI>(Listable{}, {BM, BN, KS, pr}, rc, m, lds, st)) return rc;
+  SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_bwd_data: no%s gconv_multi_kernel for tile %d x %d", pr ? " bf16" : "", BM, BN);
 }
 
 // ---- the fused-class strided data gradient (gconv_s2f_kernel) ----
@@ -1536,40 +1606,23 @@ bool s2f_eligible(const srx_conv2d_t* d, const BwdClass* cls, int nc) {
 // tile of the fused launch and its estimated time (the model of make_plan / multi_tile: one workgroup slot per CU); a
 // workgroup pays one set-up, one pipeline fill and an epilogue per class
 float s2f_tile(const srx_conv2d_t* d, const BwdClass* cls, int nc, int& BM, int& BN) {
-  const int P = device_cus();
+  const int P = srx_plan_cus();
   const bool bf16 = d->precision != 0;
   const int Cnp = pad_rows(d->Cin);
   const int M = d->N * cls[0].Hm * cls[0].Wm;
   int chunks = 0;
   for (int i = 0; i < nc; ++i) chunks += cls[i].K / BK;
-  constexpr int NC = 5;
-  const int cand[NC][2] = {{144, 128}, {144, 64}, {128, 128}, {128, 64}, {64, 64}};
-  const float eff[NC] = {0.91f, 0.82f, 0.95f, 0.85f, 0.60f};
   float best = 1e30f;
   BM = 0; BN = 0;
-  for (int i = 0; i < NC; ++i) {
-    const int bm = cand[i][0], bn = cand[i][1];
-    if ((bf16 && bm == 144) || Cnp % bn != 0) continue;
-    const float t = 2.0f * bm * bn * (float)chunks * BK / (4 * 64 * 2.1e3f) / eff[i] / (bf16 ? 3.0f : 1.0f);
+  for (const Tile& tile : kTiles) {
+    const int bm = tile.BM, bn = tile.BN;
+    if (!tile.ks[F_S2F][bf16 ? 1 : 0] || Cnp % bn != 0) continue;
+    const float t = tile_us(bm, bn, chunks, tile.eff, bf16);
     const int64_t tiles = srx_cdiv(M, bm) * (Cnp / bn);
     const float cost = (float)srx_cdiv(tiles, P) * (1.5f + 0.7f * nc * (bm * bn / 8192.0f) + t);
     if (cost < best) { best = cost; BM = bm; BN = bn; }
   }
   return best;
-}
-
-template <int BM, int BN, int WM, int WN, int XR, int PR>
-int launch_gconv_s2f(const GFused& f, dim3 grid, size_t lds, double fl, hipStream_t st) {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gconv_s2f_kernel<BM, BN, WM, WN, XR, PR>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
-  char nm[64];
-  if (srx_prof_on()) snprintf(nm, sizeof(nm), "gconv_s2f_kernel<%d, %d, %d, %d, %d, %d>", BM, BN, WM, WN, XR, PR);
-  SRX_LAUNCH_PROF(nm, fl, (gconv_s2f_kernel<BM, BN, WM, WN, XR, PR>), grid, dim3((BM / WM) * (BN / WN) * 64), lds, st, f);
-  SRX_CHECK_LAUNCH("gconv_s2f_kernel");
-  return SRX_OK;
 }
 
 // `shared`: the launch arguments of any one class (gconv_multi's), `wpk` / `wfloats`: the whole packed data-gradient buffer
@@ -1596,21 +1649,12 @@ int run_gconv_s2f(const srx_conv2d_t* d, const GArgs& shared, const BwdClass* cl
   }
   f.ptotal = pos;
   const int Cnp = pad_rows(d->Cin);
-  const bool bf16 = d->precision != 0;
-  const size_t lds = (size_t)(3 * (BM + BN) * BK) * (bf16 ? 2 : 4) + (size_t)(pos + 3) * sizeof(int4) + (size_t)srx_roundup(BM, 4) * 4;
+  const int pr = d->precision != 0 ? 1 : 0;
+  const size_t lds = s2f_lds_bytes(BM, BN, pr, pos);
   if (lds > 160 * 1024) SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_bwd_data: K range needs %zu bytes of LDS", lds);
   const dim3 grid((unsigned)(f.g.mtiles * (Cnp / BN)));
-  if (bf16) {
-    if (BM == 128 && BN == 128) return launch_gconv_s2f<128, 128, 64, 32, 0, 1>(f, grid, lds, fl, st);
-    if (BM == 128 && BN == 64) return launch_gconv_s2f<128, 64, 32, 32, 0, 1>(f, grid, lds, fl, st);
-    if (BM == 64 && BN == 64) return launch_gconv_s2f<64, 64, 32, 32, 0, 1>(f, grid, lds, fl, st);
-  } else {
-    if (BM == 144 && BN == 128) return launch_gconv_s2f<128, 128, 64, 32, 16, 0>(f, grid, lds, fl, st);
-    if (BM == 144 && BN == 64) return launch_gconv_s2f<128, 64, 32, 32, 16, 0>(f, grid, lds, fl, st);
-    if (BM == 128 && BN == 128) return launch_gconv_s2f<128, 128, 64, 32, 0, 0>(f, grid, lds, fl, st);
-    if (BM == 128 && BN == 64) return launch_gconv_s2f<128, 64, 32, 32, 0, 0>(f, grid, lds, fl, st);
-    if (BM == 64 && BN == 64) return launch_gconv_s2f<64, 64, 32, 32, 0, 0>(f, grid, lds, fl, st);
-  }
+  int rc = SRX_OK;
+  if (launch_tile<F_S2F>(Listable{}, {BM, BN, 1, pr}, rc, f, grid, lds, fl, st)) return rc;
   SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_bwd_data: internal: no fused-class instantiation for tile %d x %d", BM, BN);
 }
 
@@ -1633,8 +1677,7 @@ int strided_dgrad_plan(const srx_conv2d_t* d, const BwdClass* cls, int nc, const
     if (bm == 0) {
       s2f_tile(d, cls, nc, bm, bn);
     } else {
-      const bool known = bf16 ? ((bm == 128 && (bn == 128 || bn == 64)) || (bm == 64 && bn == 64))
-                              : (((bm == 144 || bm == 128) && (bn == 128 || bn == 64)) || (bm == 64 && bn == 64));
+      const bool known = has_tile(F_S2F, bm, bn, 1, bf16 ? 1 : 0);
       if (!known || Cnp % bn != 0)
         SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d_bwd_data: forced gconv_s2f_kernel tile %d x %d refused: %s (%d padded columns, %s products)",
                  bm, bn, known ? "the tile's columns do not divide the layer's" : "no instantiation of this tile", Cnp, bf16 ? "bf16" : "fp32");
@@ -1666,60 +1709,16 @@ int run_gconv(GArgs& a, const Plan& p, float* ws, size_t ws_floats, hipStream_t 
   a.full_tiles = p.full;
   a.tail_split = p.split;
   a.ws = ws;
-  if (a.big) {  // whole-frame calls: three tiles, no K split (plans made with `big` ask for nothing else)
+  int rc = SRX_OK;
+  if (a.big) {  // whole-frame calls: fp32, bf16 or fp16 products, no K split (plans made with `big` ask for nothing else)
     if (p.split > 1) SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: internal: split plan on a call above 2^24 pixels");
-    if (precision == 3) {
-      if (p.BM == 128 && p.BN == 128) return launch_gconv<128, 128, 64, 32, 1, 0, 3, 1>(a, p, st);
-      if (p.BM == 128 && p.BN == 64) return launch_gconv<128, 64, 32, 32, 1, 0, 3, 1>(a, p, st);
-      if (p.BM == 128 && p.BN == 32) return launch_gconv<128, 32, 32, 32, 1, 0, 3, 1>(a, p, st);
-    } else if (precision) {
-      if (p.BM == 128 && p.BN == 128) return launch_gconv<128, 128, 64, 32, 1, 0, 1, 1>(a, p, st);
-      if (p.BM == 128 && p.BN == 64) return launch_gconv<128, 64, 32, 32, 1, 0, 1, 1>(a, p, st);
-      if (p.BM == 128 && p.BN == 32) return launch_gconv<128, 32, 32, 32, 1, 0, 1, 1>(a, p, st);
-    } else {
-      if (p.BM == 128 && p.BN == 128) return launch_gconv<128, 128, 64, 32, 1, 0, 0, 1>(a, p, st);
-      if (p.BM == 128 && p.BN == 64) return launch_gconv<128, 64, 32, 32, 1, 0, 0, 1>(a, p, st);
-      if (p.BM == 128 && p.BN == 32) return launch_gconv<128, 32, 32, 32, 1, 0, 0, 1>(a, p, st);
-    }
+    if (launch_tile<F_BIG>(Listable{}, {p.BM, p.BN, p.ks, precision == 3 ? 3 : precision ? 1 : 0}, rc, a, p, st)) return rc;
     SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: no whole-frame kernel for tile %dx%d", p.BM, p.BN);
   }
-  if (precision == 2) {  // bf16 storage (round 5): the tensors hold bf16, a chunk is 64 k-values
-    if (p.BM == 256 && p.BN == 128) return launch_gconv<256, 128, 64, 64, 1, 0, 2>(a, p, st);
-    if (p.BM == 128 && p.BN == 128) return launch_gconv<128, 128, 64, 32, 1, 0, 2>(a, p, st);
-    if (p.BM == 128 && p.BN == 64) return launch_gconv<128, 64, 32, 32, 1, 0, 2>(a, p, st);
-    if (p.BM == 64 && p.BN == 64)
-      return p.ks == 2 ? launch_gconv<64, 64, 32, 32, 2, 0, 2>(a, p, st) : launch_gconv<64, 64, 32, 32, 1, 0, 2>(a, p, st);
-    SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: no bf16-storage kernel for tile %dx%d", p.BM, p.BN);
-  }
-  if (precision == 3) {  // fp16 products (the input conv of fp16 inference; plans made with `bf16 = true`: same tiles as below)
-    if (p.BM == 256 && p.BN == 128) return launch_gconv<256, 128, 64, 64, 1, 0, 3>(a, p, st);
-    if (p.BM == 128 && p.BN == 128) return launch_gconv<128, 128, 64, 32, 1, 0, 3>(a, p, st);
-    if (p.BM == 128 && p.BN == 64) return launch_gconv<128, 64, 32, 32, 1, 0, 3>(a, p, st);
-    if (p.BM == 64 && p.BN == 64)
-      return p.ks == 2 ? launch_gconv<64, 64, 32, 32, 2, 0, 3>(a, p, st) : launch_gconv<64, 64, 32, 32, 1, 0, 3>(a, p, st);
-    if (p.BM == 128 && p.BN == 32) return launch_gconv<128, 32, 32, 32, 1, 0, 3>(a, p, st);
-    if (p.BM == 64 && p.BN == 32) return launch_gconv<64, 32, 32, 32, 4, 0, 3>(a, p, st);
-    SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: no fp16 kernel for tile %dx%d", p.BM, p.BN);
-  }
-  if (precision) {  // bf16 products (plans made with `bf16 = true` never ask for the 144-row tiles)
-    if (p.BM == 256 && p.BN == 128) return launch_gconv<256, 128, 64, 64, 1, 0, 1>(a, p, st);
-    if (p.BM == 128 && p.BN == 128) return launch_gconv<128, 128, 64, 32, 1, 0, 1>(a, p, st);
-    if (p.BM == 128 && p.BN == 64) return launch_gconv<128, 64, 32, 32, 1, 0, 1>(a, p, st);
-    if (p.BM == 64 && p.BN == 64)
-      return p.ks == 2 ? launch_gconv<64, 64, 32, 32, 2, 0, 1>(a, p, st) : launch_gconv<64, 64, 32, 32, 1, 0, 1>(a, p, st);
-    if (p.BM == 128 && p.BN == 32) return launch_gconv<128, 32, 32, 32, 1, 0, 1>(a, p, st);
-    if (p.BM == 64 && p.BN == 32) return launch_gconv<64, 32, 32, 32, 4, 0, 1>(a, p, st);
-    SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: no bf16 kernel for tile %dx%d", p.BM, p.BN);
-  }
-  if (p.BM == 144 && p.BN == 128) return launch_gconv<128, 128, 64, 32, 1, 16>(a, p, st);
-  if (p.BM == 144 && p.BN == 64) return launch_gconv<128, 64, 32, 32, 1, 16>(a, p, st);
-  if (p.BM == 128 && p.BN == 128) return launch_gconv<128, 128, 64, 32, 1, 0>(a, p, st);
-  if (p.BM == 128 && p.BN == 64) return launch_gconv<128, 64, 32, 32, 1, 0>(a, p, st);
-  if (p.BM == 64 && p.BN == 64)
-    return p.ks == 2 ? launch_gconv<64, 64, 32, 32, 2, 0>(a, p, st) : launch_gconv<64, 64, 32, 32, 1, 0>(a, p, st);
-  if (p.BM == 64 && p.BN == 32) return launch_gconv<64, 32, 32, 32, 2, 0>(a, p, st);
-  if (p.BM == 128 && p.BN == 32) return launch_gconv<128, 32, 32, 32, 1, 0>(a, p, st);
-  SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: no fp32 kernel for tile %dx%d", p.BM, p.BN);
+  // (precision 2, bf16 storage: the tensors hold bf16, a chunk is 64 k-values; 3, fp16 products: the input conv of fp16 inference)
+  if (launch_tile<F_GCONV>(Listable{}, {p.BM, p.BN, p.ks, precision}, rc, a, p, st)) return rc;
+  static const char* const arith[4] = {"fp32", "bf16", "bf16-storage", "fp16"};
+  SRX_FAIL(SRX_E_UNSUPPORTED, "conv2d: no %s kernel for tile %dx%d", arith[precision & 3], p.BM, p.BN);
 }
 
 void set_mgrid(GArgs& a, int N, int Hm, int Wm) {
@@ -1834,8 +1833,7 @@ extern "C" int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out) {
 
 extern "C" int srx_conv2d_force_plan(int bm, int bn, int split, int ks) {
   SRX_REQUIRE((bm == 0 && bn == 0 && split == 0 && ks == 0) ||
-              ((bm == 64 || bm == 128 || bm == 144 || bm == 256) && (bn == 32 || bn == 64 || bn == 128) && split >= 1 && split <= 16 &&
-               (ks == 1 || ks == 2)),
+              (tile_sides_known(F_GCONV, bm, bn) && split >= 1 && split <= 16 && (ks == 1 || ks == 2)),
               "conv2d_force_plan: (0, 0, 0, 0) or BM 64 / 128 / 144 / 256, BN 32 / 64 / 128, split 1..16, KS 1 / 2");
   ConvForce& f = conv_force();
   f.plan[1].store(0);  // (off while the others change)
@@ -1845,7 +1843,7 @@ extern "C" int srx_conv2d_force_plan(int bm, int bn, int split, int ks) {
 
 extern "C" int srx_conv2d_force_s2(int mode, int bm, int bn) {
   SRX_REQUIRE(((mode == 0 || mode == 1) && bm == 0 && bn == 0) ||
-              (mode == 2 && ((bm == 0 && bn == 0) || ((bm == 64 || bm == 128 || bm == 144) && (bn == 64 || bn == 128)))),
+              (mode == 2 && ((bm == 0 && bn == 0) || tile_sides_known(F_S2F, bm, bn))),
               "conv2d_force_s2: (0, 0, 0), (1, 0, 0) or (2, BM 64 / 128 / 144, BN 64 / 128) -- (2, 0, 0): the model's fused tile");
   ConvForce& f = conv_force();
   f.s2[0].store(0);
