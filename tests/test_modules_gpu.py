@@ -209,6 +209,41 @@ def test_residual_block_one_node_equals_layer_by_layer(dev, shape):
     assert flat.grad.abs().sum() > 0
 
 
+def test_single_residual_block_one_node_equals_layer_by_layer(dev):
+    """A lone ``ResidualBlock`` under a trainer is a tower of one (``functional.residual_block``): the same node, with the
+    tower's fused normalise and reduce launches (12 x 12 runs on the row-tile kernel).  Against the block run layer by layer
+    on a copy of the same state, with the assertions of the tower test above."""
+    from torchsr_amd import functional as F
+    from torchsr_amd.optim import FlatParams
+    from torchsr_amd.srgan.residual import ResidualBlock
+    torch.manual_seed(22)
+    a, b = ResidualBlock().to(dev).train(), ResidualBlock().to(dev).train()
+    b.load_state_dict(a.state_dict())
+    flat = FlatParams(a)
+    x = torch.rand(2, 12, 12, 64, device=dev)
+    xa, xb = x.clone().requires_grad_(True), x.clone().requires_grad_(True)
+    old = F.direct_grads[0]
+    try:
+        F.direct_grads[0] = True
+        assert F.residual_block_fused_ok(a)
+        ya = a(xa)
+        ya.square().mean().backward()
+        F.direct_grads[0] = False
+        assert not F.residual_block_fused_ok(b)
+        yb = b(xb)
+        yb.square().mean().backward()
+    finally:
+        F.direct_grads[0] = old
+    assert torch.equal(ya, yb)
+    assert rel(xa.grad, xb.grad) < 1e-5
+    for (k, pa), (_, pb) in zip(a.named_parameters(), b.named_parameters()):
+        assert rel(pa.grad, pb.grad) < (1e-4 if pa.numel() == 1 else 1e-5), k
+    for (k, va), (_, vb) in zip(a.state_dict().items(), b.state_dict().items()):
+        if 'running_' in k or 'num_batches' in k:
+            assert torch.equal(va, vb), k
+    assert flat.grad.abs().sum() > 0
+
+
 def test_vgg_loss_vs_golden(dev):
     from torchsr_amd import functional as F
     from torchsr_amd.srgan.loss import VGGLoss

@@ -1,0 +1,118 @@
+"""Trace every C-ABI call of the training steps and of inference (developer tool, needs the GPU): the check that a change to the
+host code -- the autograd Functions and launchers of torchsr_amd/functional.py -- changed no launch.
+
+    python tools/call_trace.py OUT.txt      # once per tree, both against the same library (SRX_LIB); then `cmp` the two files
+
+``_lib.call`` and every module-level alias of it in the package are wrapped (as tests/step_layers.py::record_op_calls does, but for
+every entry point, the conv ones included).  One line per call: the name, then per argument -- by the declared ctypes signature --
+the value of an int / int64 / size_t / float, the fields of a conv descriptor, and for any other pointer only whether it is null.
+Each case runs once, eagerly (no hipGraph), from one seed, at the smallest sizes the step tests use (batch 2, their trainer
+settings, their golden inputs): an SRGAN step, an ESRGAN step in fp32 and one under autocast (bf16-storage VGG stack, fused dense
+blocks), the VGG loss forward and backward alone, and Generator inference in fp32, bf16 and fp16.  Sizing calls made on the
+library handle directly (``*_ws_floats``) are not traced; the sizes they return are (``nws`` arguments).  A swapped pair of
+non-null pointers is invisible here: the numerical tests cover that.
+"""
+import ctypes as C
+import os
+import sys
+from argparse import Namespace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from oracle.weights import closed_form_state, step_state  # noqa: E402
+from torchsr_amd import _lib  # noqa: E402
+import torchsr_amd.esrgan.trainer  # noqa: E402,F401  (every module that binds `call` is loaded before the wrap)
+import torchsr_amd.srgan.trainer  # noqa: E402,F401
+import torchsr_amd.functional  # noqa: E402,F401
+import torchsr_amd.optim  # noqa: E402,F401
+import torchsr_amd.test  # noqa: E402,F401
+
+GOLDEN = os.path.join(ROOT, 'tests', 'golden')
+VALUES = (C.c_int, C.c_int64, C.c_size_t, C.c_float)
+DESC = C.POINTER(_lib.Conv2dDesc)
+
+
+def show(v, t) -> str:
+    if t in VALUES:
+        return repr(float(v)) if t is C.c_float else str(int(v))
+    if t is DESC and v is not None:
+        d = v._obj if hasattr(v, '_obj') else v.contents  # ctypes.byref(d), or ctypes.pointer(d)
+        return '{' + ','.join(format(getattr(d, f), '.9g' if ft is C.c_float else 'd') for f, ft in d._fields_) + '}'
+    null = v is None or v == 0 or (isinstance(v, C.c_void_p) and not v.value)
+    return 'null' if null else 'ptr'
+
+
+def traced(out, tag, fn) -> None:
+    """Run ``fn`` with the wrap in place; its calls go to ``out`` under the heading ``tag``."""
+    real = _lib.call
+
+    def spy(name, *args):
+        out.append(name + ' ' + ' '.join(show(v, t) for v, t in zip(args, _lib._SIGS[name][1])))
+        return real(name, *args)
+
+    bound = [(mod, attr) for name, mod in list(sys.modules.items())
+             if mod is not None and (name == 'torchsr_amd' or name.startswith('torchsr_amd.'))
+             for attr, val in list(vars(mod).items()) if val is real]
+    out.append('# ' + tag)
+    for mod, attr in bound:
+        setattr(mod, attr, spy)
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        for mod, attr in bound:
+            setattr(mod, attr, real)
+
+
+def trainer(cls, dev, tag, disable_amp):
+    """The settings of ``make_trainer`` in tests/test_step_gpu.py and tests/test_esrgan_gpu.py, batch 2, no hipGraph."""
+    args = Namespace(disable_amp=disable_amp, batch_size=2, epochs=8, gan_checkpoint=None, local_rank=0, pretrain_epochs=1,
+                     psnr_checkpoint=None, skip_image_save=True, world_size=1, rank=-1, use_graphs=False, vgg_weights='random')
+    t = cls(dev, args, [], [], 2, 2, distributed=False)
+    t.generator.load_state_dict(step_state(t.generator.state_dict(), tag + '.G'))
+    t.discriminator.load_state_dict(step_state(t.discriminator.state_dict(), tag + '.D'))
+    t.vgg_loss.features.load_state_dict(closed_form_state(t.vgg_loss.features.state_dict(), prefix='features.'))
+    t.generator.train()
+    t.discriminator.train()
+    return t
+
+
+def main():
+    from torchsr_amd.esrgan.trainer import ESRGANTrainer
+    from torchsr_amd.srgan.generator import Generator
+    from torchsr_amd.srgan.loss import VGGLoss
+    from torchsr_amd.srgan.trainer import SRGANTrainer
+    from torchsr_amd.test import upscale
+    dev = torch.device('cuda:0')
+    torch.manual_seed(0)
+    out = []
+
+    def step(cls, tag, gold, disable_amp, what):
+        g = np.load(os.path.join(GOLDEN, gold))
+        lr, hr = torch.from_numpy(g['low_res']).to(dev), torch.from_numpy(g['high_res']).to(dev)
+        t = trainer(cls, dev, tag, disable_amp)
+        traced(out, what, lambda: t.gan_step(lr, hr))
+
+    step(SRGANTrainer, 'srgan', 'srgan_steps.npz', True, 'SRGAN step, fp32')
+    step(ESRGANTrainer, 'esrgan', 'esrgan.npz', True, 'ESRGAN step, fp32')
+    step(ESRGANTrainer, 'esrgan', 'esrgan.npz', False, 'ESRGAN step, autocast')
+
+    vgg = VGGLoss(weights='random').to(dev)
+    src, tgt = torch.rand(2, 3, 32, 48, device=dev).requires_grad_(True), torch.rand(2, 3, 32, 48, device=dev)
+    traced(out, 'VGG loss forward and backward, fp32', lambda: vgg(src, tgt).backward())
+
+    gen = Generator().to(dev)
+    low = torch.rand(2, 3, 24, 24, device=dev)
+    for precision in ('fp32', 'bf16', 'fp16'):
+        traced(out, 'Generator inference, ' + precision, lambda: upscale(gen, low, precision=precision))
+
+    with open(sys.argv[1], 'w') as f:
+        f.write('\n'.join(out) + '\n')
+    print('%d calls in %d cases written to %s' % (sum(not ln.startswith('#') for ln in out), sum(ln.startswith('#') for ln in out),
+                                                  sys.argv[1]))
+
+
+if __name__ == '__main__':
+    main()

@@ -253,6 +253,153 @@ def round4(c: int) -> int:
     return (c + 3) // 4 * 4
 
 
+# --------------------------------------------------------------------------- launchers
+# The only places that size a conv, BatchNorm or colsum workspace and name these entry points.  Pointer arguments are raw
+# (``_p(t)``, or ``t.data_ptr() + offset`` for a channel slice); ``like`` gives the workspace its device; ``s``: the stream.
+def _conv_fwd(d: Conv2dDesc, x_ptr, w_ptr, b_ptr, y_ptr, like: Tensor, s, part_ptr=None, residual=None) -> None:
+    """The direct conv forward; ``residual = (ptr, scale)``: ``y = conv * scale + residual`` in the epilogue."""
+    dref = C.byref(d)
+    nws = _lib.lib().srx_conv2d_fwd_ws_floats(dref)
+    ws = _p(_ws(nws, like)) if nws else None
+    if residual is None:
+        call('srx_conv2d_fwd', dref, x_ptr, w_ptr, b_ptr, y_ptr, part_ptr, ws, nws, s)
+    else:
+        call('srx_conv2d_fwd_residual', dref, x_ptr, w_ptr, b_ptr, residual[0], residual[1], y_ptr, ws, nws, s)
+
+
+def _wino_fwd(d: Conv2dDesc, x: Tensor, u: Tensor, b: Optional[Tensor], y: Tensor, part: Optional[Tensor], s) -> None:
+    """The Winograd forward, with BatchNorm partial statistics when ``part`` is given."""
+    dref = C.byref(d)
+    nws = _lib.lib().srx_wino_ws_floats(dref, 0 if part is None else 2)
+    ws = _p(_ws(nws, x)) if nws else None
+    if part is None:
+        call('srx_wino_fwd', dref, _p(x), _p(u), _p(b), _p(y), ws, nws, s)
+    else:
+        call('srx_wino_fwd_stats', dref, _p(x), _p(u), _p(b), _p(y), _p(part), ws, nws, s)
+
+
+def _conv_dgrad(d: Conv2dDesc, dy_ptr, w_ptr, dx_ptr, like: Tensor, s, accumulate: int = 0, addend_ptr=None, mask=None,
+                nws: Optional[int] = None) -> None:
+    """The direct data gradient: plain / accumulating, ``+ addend``, or masked by ``(act_out_ptr, slope, c_lo, c_hi)``."""
+    dref = C.byref(d)
+    if nws is None:  # (a caller looping over equal layers sizes once and passes it in)
+        nws = _lib.lib().srx_conv2d_bwd_data_ws_floats(dref)
+    ws = _p(_ws(nws, like)) if nws else None
+    if mask is not None:
+        call('srx_conv2d_bwd_data_act', dref, dy_ptr, w_ptr, mask[0], mask[1], mask[2], mask[3], accumulate, dx_ptr, ws, nws, s)
+    elif addend_ptr is not None:
+        call('srx_conv2d_bwd_data_add', dref, dy_ptr, w_ptr, addend_ptr, dx_ptr, ws, nws, s)
+    else:
+        call('srx_conv2d_bwd_data', dref, dy_ptr, w_ptr, dx_ptr, accumulate, ws, nws, s)
+
+
+def _layer_dgrad(st, d: Conv2dDesc, master: Tensor, wino: bool, wino_bwd: Optional[Tensor], wpk_bwd: Optional[Tensor], dy: Tensor,
+                 x: Tensor, in_act, s) -> Tuple[Tensor, bool]:
+    """``(dx, masked)`` of a layer that ran on Winograd or the direct kernel; ``masked``: the backward of ``in_act``, which made ``x``, is in."""
+    dx = torch.empty_like(x)
+    masked = in_act is not None
+    if wino and (not masked or in_act.act == ACT_RELU) and wino_bwd is not None:
+        dref = C.byref(d)
+        nws = _lib.lib().srx_wino_ws_floats(dref, 1)
+        call('srx_wino_bwd_data', dref, _p(dy), _p(wino_bwd), _p(x) if masked else None, _p(dx), _p(_ws(nws, x)) if nws else None,
+             nws, s)
+        return dx, masked
+    if wino:  # (a Winograd forward whose data gradient takes the direct kernel: its packed copy is made now)
+        st.pack(master, d)
+        wpk_bwd = st.wpk_bwd
+    mask = (_p(x), 0.0 if in_act.act == ACT_RELU else in_act.slope, 0, st.cin_s) if masked else None
+    _conv_dgrad(d, _p(dy), _p(wpk_bwd), _p(dx), x, s, mask=mask)
+    return dx, masked
+
+
+def _conv_wgrad(d: Conv2dDesc, x_ptr, dy_ptr, dw: Optional[Tensor], sink: Optional[Tensor], b_ptr, keep, like: Tensor, s,
+                scale: Optional[float] = None) -> None:
+    """Weight (+ riding bias) gradient: accumulated into ``sink`` -- queued, with ``keep``, under a queue -- or written to ``dw``."""
+    queue = wgrad_queue[0]
+    if queue is not None and sink is not None:
+        queue.add(d, x_ptr, dy_ptr, _p(sink), b_ptr, keep, 1.0 if scale is None else scale)
+        return
+    dref = C.byref(d)
+    nws = _lib.lib().srx_conv2d_bwd_weight_ws_floats(dref)
+    ws = _ws(nws, like)
+    out, acc = (_p(dw), 0) if sink is None else (_p(sink), 1)
+    if scale is None:
+        call('srx_conv2d_bwd_weight', dref, x_ptr, dy_ptr, out, acc, b_ptr, _p(ws), nws, s)
+    else:
+        one = lambda v: (C.c_void_p * 1)(v)  # noqa: E731
+        call('srx_conv2d_bwd_weight_multi_scaled', dref, 1, 1, one(x_ptr), one(dy_ptr), one(out), acc, one(b_ptr),
+             (C.c_float * 1)(scale), _p(ws), nws, s)
+
+
+def _colsum(src_ptr, rows: int, cols: int, ld: int, out: Tensor, accumulate: int, like: Tensor, s) -> None:
+    """Column sums of a ``rows x cols`` matrix (row stride ``ld``) written or accumulated into ``out``."""
+    nws = _lib.lib().srx_colsum_ws_floats(rows, cols)
+    call('srx_colsum', src_ptr, _p(out), rows, cols, ld, accumulate, _p(_ws(nws, like)), nws, s)
+
+
+def _conv_param_grads(st, d: Conv2dDesc, x_ptr, dy_ptr, dy_rows: int, dy_ld: int, wparam: Optional[Tensor], bparam: Optional[Tensor],
+                      keep, like: Tensor, s, scale: Optional[float] = None):
+    """``(dw, db)`` of one conv for autograd, ``None`` where the parameter is ``None`` (no gradient wanted) or its ``.grad`` took it."""
+    dev = like.device
+    dw = db = sink = b_ptr = None
+    if wparam is not None:
+        sink = _sink(wparam)
+        if sink is None:
+            dw = torch.empty((st.cout, st.cin, st.k, st.k), dtype=torch.float32, device=dev)
+        # the bias gradient rides along in the weight-gradient kernel (it stages every dy row anyway) when both results go
+        # the same way: both accumulated into .grad, or both returned (PixelShuffle layers too: the reduction maps packed
+        # columns back)
+        if bparam is not None:
+            bsink = _sink(bparam)
+            if (bsink is None) == (sink is None):
+                if bsink is None:
+                    db = torch.empty(st.cout, dtype=torch.float32, device=dev)
+                b_ptr = _p(db if bsink is None else bsink)
+                bparam = None
+    if bparam is not None and scale is not None:
+        raise RuntimeError('conv gradients: with a scale the bias gradient must ride in the weight-gradient kernel (weight and '
+                           'bias both with a gradient sink, or both without)')
+    if wparam is not None:
+        _conv_wgrad(d, x_ptr, dy_ptr, dw, sink, b_ptr, keep, like, s, scale)
+    if bparam is None:
+        return dw, db
+    if st.shuffle:
+        # dy is [N, 2Ho, 2Wo, cps]; bias index co = c*4 + i*2 + j
+        w2, cps = st.out_shape(d.N, d.H, d.W)[2], dy_ld
+        cols = 2 * w2 * cps
+        t = torch.empty(cols, dtype=torch.float32, device=dev)
+        _colsum(dy_ptr, dy_rows // (2 * w2), cols, cols, t, 0, like, s)
+        # t is [i][wo][j][c]; fold wo (tiny tensor, plumbing) and permute to (c,i,j)
+        return dw, t.view(2, w2 // 2, 2, cps).sum(1).permute(2, 0, 1).reshape(-1)[:st.cout].contiguous()
+    bsink = _sink(bparam)
+    if bsink is None:
+        db = torch.empty(st.cout, dtype=torch.float32, device=dev)
+    _colsum(dy_ptr, dy_rows, st.cout, dy_ld, db if bsink is None else bsink, 0 if bsink is None else 1, like, s)
+    return dw, db
+
+
+def _bn_train_fwd(y: Tensor, part: Tensor, m: int, c: int, groups: int, bn_eps: float, momentum: Optional[float], gamma: Tensor,
+                  beta: Tensor, residual: Optional[Tensor], out: Tensor, act: int, slope: float, prelu: Optional[Tensor],
+                  running_mean, running_var, nbt, s) -> Tuple[Tensor, Tensor]:
+    """``out = act(BatchNorm(y)) [+ residual]`` from the partial statistics ``part``; returns the batch ``(mean, invstd)``."""
+    mean = torch.empty(groups * c, dtype=torch.float32, device=y.device)
+    invstd = torch.empty(groups * c, dtype=torch.float32, device=y.device)
+    call('srx_bn_train_fwd', _p(y), _p(part), part.shape[0], m, c, groups, bn_eps, 0.1 if momentum is None else momentum, _p(gamma.detach()),
+         _p(beta.detach()), _p(residual), _p(out), act, slope, _p(prelu), _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(nbt), s)
+    return mean, invstd
+
+
+def _bn_act_bwd(dout: Tensor, y: Tensor, mean: Tensor, invstd: Tensor, gamma: Tensor, beta: Tensor, prelu: Optional[Tensor], m: int,
+                c: int, groups: int, act: int, slope: float, training: bool, sinks, s, want_dy: bool = True):
+    """``(dy, sums)`` of ``act(BatchNorm(y))``; ``sinks``: the ``.grad`` of gamma, beta and the PReLU slope, or ``None`` each."""
+    sums = torch.empty(groups * (2 * c + 4), dtype=torch.float32, device=y.device)
+    nws = _lib.lib().srx_bn_bwd_ws_floats(m, c)
+    dy = torch.empty_like(y) if want_dy else None
+    call('srx_bn_act_bwd', _p(dout), _p(y), _p(mean), _p(invstd), _p(gamma.detach()), _p(beta.detach()), _p(sums), _p(dy), m, c, groups, act, slope,
+         _p(prelu), 1 if training else 0, _p(sinks[0]), _p(sinks[1]), _p(sinks[2]), _p(_ws(nws, y)), nws, s)
+    return dy, sums
+
+
 # --------------------------------------------------------------------------- layout
 class _ToNHWC(Function):
     @staticmethod
@@ -571,20 +718,13 @@ class _Conv2d(Function):
             st.pack_wino(master, d, need_bwd=ctx.needs_input_grad[0] and not fwd_only)
             if want_stats:
                 part = torch.empty((L.srx_wino_stat_rows(dref), st.cout, 2), dtype=torch.float32, device=x.device)
-                nws = L.srx_wino_ws_floats(dref, 2)
-                call('srx_wino_fwd_stats', dref, _p(x), _p(st.wino_fwd), _p(b), _p(y), _p(part), _p(_ws(nws, x)) if nws else None, nws,
-                     _stream())
-            else:
-                nws = L.srx_wino_ws_floats(dref, 0)
-                call('srx_wino_fwd', dref, _p(x), _p(st.wino_fwd), _p(b), _p(y), _p(_ws(nws, x)) if nws else None, nws, _stream())
+            _wino_fwd(d, x, st.wino_fwd, b, y, part, _stream())
         else:
             st.pack(master, d)
             if want_stats:
                 rows = L.srx_conv2d_stat_rows(dref)
                 part = torch.empty((rows, st.cout, 2), dtype=torch.float32, device=x.device)
-            nws = L.srx_conv2d_fwd_ws_floats(dref)
-            ws = _ws(nws, x) if nws else None
-            call('srx_conv2d_fwd', dref, _p(x), _p(st.wpk_fwd), _p(b), _p(y), _p(part), _p(ws), nws, _stream())
+            _conv_fwd(d, _p(x), _p(st.wpk_fwd), _p(b), _p(y), x, _stream(), part_ptr=_p(part))
         ctx.master = master
         ctx.st, ctx.d = st, d
         ctx.has_bias = bias is not None
@@ -599,8 +739,6 @@ class _Conv2d(Function):
     @staticmethod
     def backward(ctx, dy: Tensor, _dpart):
         st, d = ctx.st, ctx.d
-        dref = C.byref(d)
-        L = _lib.lib()
         x, y = ctx.saved_tensors
         dy = _chk(dy, 'conv2d.grad')
         s = _stream()
@@ -611,71 +749,15 @@ class _Conv2d(Function):
             g = torch.empty_like(dy)
             call('srx_act_bwd_from_out', _p(dy), _p(y), _p(g), dy.numel(), st.act, st.slope, s)
             dy = g
-        dx = dw = db = None
-        if ctx.needs_input_grad[0] and ctx.wino and (ctx.in_act is None or ctx.in_act.act == ACT_RELU) and st.wino_bwd is not None:
-            dx = torch.empty_like(x)
-            nws = L.srx_wino_ws_floats(dref, 1)
-            call('srx_wino_bwd_data', dref, _p(dy), _p(st.wino_bwd), _p(x) if ctx.in_act is not None else None, _p(dx),
-                 _p(_ws(nws, x)) if nws else None, nws, s)
-            if ctx.in_act is not None:
+        dx = None
+        if ctx.needs_input_grad[0]:  # ... with the backward of the activation that produced x (in_act)
+            dx, masked = _layer_dgrad(st, d, ctx.master, ctx.wino, st.wino_bwd if ctx.wino else None, ctx.wpk_bwd, dy, x, ctx.in_act, s)
+            if masked:
                 ctx.in_act.masked = True
-        elif ctx.needs_input_grad[0]:
-            if ctx.wino:  # (a Winograd forward whose data gradient takes the direct kernel: its packed copy is made now)
-                st.pack(ctx.master, d)
-                ctx.wpk_bwd = st.wpk_bwd
-            dx = torch.empty_like(x)
-            nws = L.srx_conv2d_bwd_data_ws_floats(dref)
-            ws = _ws(nws, x) if nws else None
-            if ctx.in_act is not None:  # ... and the backward of the activation that produced x
-                slope = 0.0 if ctx.in_act.act == ACT_RELU else ctx.in_act.slope
-                call('srx_conv2d_bwd_data_act', dref, _p(dy), _p(ctx.wpk_bwd), _p(x), slope, 0, st.cin_s, 0, _p(dx), _p(ws), nws, s)
-                ctx.in_act.masked = True
-            else:
-                call('srx_conv2d_bwd_data', dref, _p(dy), _p(ctx.wpk_bwd), _p(dx), 0, _p(ws), nws, s)
         wparam, bparam = ctx.params
-        bias_done = False
-        if ctx.needs_input_grad[1]:
-            sink = _sink(wparam)
-            dw = None if sink is not None else torch.empty((st.cout, st.cin, st.k, st.k), dtype=torch.float32,
-                                                             device=x.device)
-            # the bias gradient rides along in the weight-gradient kernel (it stages every dy row anyway)
-            # when both results go the same way: both accumulated into .grad, or both returned
-            bptr = None
-            if ctx.has_bias and ctx.needs_input_grad[2]:  # (PixelShuffle layers too: the reduction maps packed columns back)
-                bsink = _sink(bparam)
-                if (bsink is None) == (sink is None):
-                    if bsink is None:
-                        db = torch.empty(st.cout, dtype=torch.float32, device=x.device)
-                    bptr = _p(db if bsink is None else bsink)
-                    bias_done = True
-            queue = wgrad_queue[0]
-            if queue is not None and sink is not None:
-                queue.add(d, _p(x), _p(dy), _p(sink), bptr, (x, dy))
-            else:
-                nws = L.srx_conv2d_bwd_weight_ws_floats(dref)
-                ws = _ws(nws, x)
-                call('srx_conv2d_bwd_weight', dref, _p(x), _p(dy), _p(dw if sink is None else sink),
-                     0 if sink is None else 1, bptr, _p(ws), nws, s)
-        if ctx.has_bias and ctx.needs_input_grad[2] and not bias_done:
-            sink = None if st.shuffle else _sink(bparam)
-            if sink is not None:
-                m = dy.numel() // st.cout_s
-                nws = L.srx_colsum_ws_floats(m, st.cout)
-                call('srx_colsum', _p(dy), _p(sink), m, st.cout, st.cout_s, 1, _p(_ws(nws, dy)), nws, s)
-            elif st.shuffle:
-                # dy is [N, 2Ho, 2Wo, cps]; bias index co = c*4 + i*2 + j
-                n, h2, w2, cps = dy.shape
-                rows, cols = n * (h2 // 2), 2 * w2 * cps
-                t = torch.empty(cols, dtype=torch.float32, device=dy.device)
-                nws = L.srx_colsum_ws_floats(rows, cols)
-                call('srx_colsum', _p(dy), _p(t), rows, cols, cols, 0, _p(_ws(nws, dy)), nws, s)
-                # t is [i][wo][j][c]; fold wo (tiny tensor, plumbing) and permute to (c,i,j)
-                db = t.view(2, w2 // 2, 2, cps).sum(1).permute(2, 0, 1).reshape(-1)[:st.cout].contiguous()
-            else:
-                m = dy.numel() // st.cout_s
-                db = torch.empty(st.cout, dtype=torch.float32, device=dy.device)
-                nws = L.srx_colsum_ws_floats(m, st.cout)
-                call('srx_colsum', _p(dy), _p(db), m, st.cout, st.cout_s, 0, _p(_ws(nws, dy)), nws, s)
+        dw, db = _conv_param_grads(st, d, _p(x), _p(dy), dy.numel() // st.cout_s, st.cout_s,
+                                   wparam if ctx.needs_input_grad[1] else None,
+                                   bparam if ctx.has_bias and ctx.needs_input_grad[2] else None, (x, dy), x, s)
         return dx, dw, db, None, None, None, None, None
 
 
@@ -700,8 +782,6 @@ class _BNAct(Function):
         s = _stream()
         if not training:
             groups = 1  # eval: one set of running statistics for every row
-        mean = torch.empty(groups * c, dtype=torch.float32, device=y.device)
-        invstd = torch.empty(groups * c, dtype=torch.float32, device=y.device)
         g = _chk(gamma.detach(), 'bn.weight')
         b = _chk(beta.detach(), 'bn.bias')
         pw = None if prelu is None else _chk(prelu.detach(), 'prelu.weight')
@@ -712,9 +792,11 @@ class _BNAct(Function):
                 rows = _lib.lib().srx_bn_stat_rows(m)
                 part = torch.empty((rows, c, 2), dtype=torch.float32, device=y.device)
                 call('srx_bn_partial_stats', _p(y), _p(part), m, c, s)
-            call('srx_bn_train_fwd', _p(y), _p(part), part.shape[0], m, c, groups, eps, momentum, _p(g), _p(b), _p(res),
-                 _p(out), act, slope, _p(pw), _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(nbt), s)
+            mean, invstd = _bn_train_fwd(y, part, m, c, groups, eps, momentum, g, b, res, out, act, slope, pw, running_mean,
+                                         running_var, nbt, s)
         else:
+            mean = torch.empty(c, dtype=torch.float32, device=y.device)
+            invstd = torch.empty(c, dtype=torch.float32, device=y.device)
             call('srx_bn_eval_stats', _p(running_mean), _p(running_var), c, eps, _p(mean), _p(invstd), s)
             call('srx_bn_act_fwd', _p(y), _p(mean), _p(invstd), _p(g), _p(b), _p(res), _p(out), m, c, act, slope, _p(pw),
                  s)
@@ -728,13 +810,9 @@ class _BNAct(Function):
         y, mean, invstd, g, b, pw = ctx.saved_tensors
         m, c, act, slope, training, has_res, has_prelu, groups = ctx.cfg
         dout = _chk(dout, 'bn.grad')
-        s = _stream()
-        sums = torch.empty(groups * (2 * c + 4), dtype=torch.float32, device=y.device)
-        nws = _lib.lib().srx_bn_bwd_ws_floats(m, c)
         gs, bs, ps = (_sink(t) for t in ctx.params)
-        dy = torch.empty_like(y) if ctx.needs_input_grad[0] else None
-        call('srx_bn_act_bwd', _p(dout), _p(y), _p(mean), _p(invstd), _p(g), _p(b), _p(sums), _p(dy), m, c, groups, act,
-             slope, _p(pw), 1 if training else 0, _p(gs), _p(bs), _p(ps), _p(_ws(nws, y)), nws, s)
+        dy, sums = _bn_act_bwd(dout, y, mean, invstd, g, b, pw, m, c, groups, act, slope, training, (gs, bs, ps), _stream(),
+                               want_dy=ctx.needs_input_grad[0])
         want = ((ctx.needs_input_grad[2] and gs is None), (ctx.needs_input_grad[3] and bs is None),
                 (has_prelu and ctx.needs_input_grad[4] and ps is None))
         dgamma = dbeta = dprelu = None
@@ -784,110 +862,16 @@ def bn_act(y, part, bn, act=ACT_NONE, slope=0.0, prelu: Optional[Tensor] = None,
                         int(groups))
 
 
-class _ResidualBlock(Function):
-    """SRGAN's ``ResidualBlock.forward`` -- ``x + BN2(conv2(PReLU(BN1(conv1(x)))))`` (srgan/residual.py:86-91) -- as ONE
-    autograd node in training mode.  Same kernels as the layer-by-layer path; what the node buys is the backward
-    pass: autograd would add the skip connection's gradient to conv1's input gradient in a pass of its own (17 such
-    adds per generator backward); here that sum is the epilogue of conv1's data gradient
-    (``srx_conv2d_bwd_data_add``).  Parameter gradients accumulate straight into the flat ``.grad`` buffers; the
-    conv weight gradients go to the ``WeightGradQueue`` when one is installed.
-    """
-
-    @staticmethod
-    def forward(ctx, x: Tensor, block, *params):
-        ctx.set_materialize_grads(False)
-        x = _chk(x, 'residual_block.input')
-        n, h, w, c = x.shape
-        m = n * h * w
-        L, s = _lib.lib(), _stream()
-        convs, bns = (block.conv1, block.conv2), (block.bn1, block.bn2)
-        descs, ys, stats = [], [], []
-        inp = x
-        for i in range(2):
-            st, bn = convs[i]._st, bns[i]
-            d = st.desc(n, h, w)
-            dref = C.byref(d)
-            st.pack(convs[i].weight, d)
-            y = torch.empty_like(x)
-            part = torch.empty((L.srx_conv2d_stat_rows(dref), c, 2), dtype=torch.float32, device=x.device)
-            nws = L.srx_conv2d_fwd_ws_floats(dref)
-            call('srx_conv2d_fwd', dref, _p(inp), _p(st.wpk_fwd), None, _p(y), _p(part), _p(_ws(nws, x)) if nws else None, nws, s)
-            mean = torch.empty(c, dtype=torch.float32, device=x.device)
-            invstd = torch.empty(c, dtype=torch.float32, device=x.device)
-            out = torch.empty_like(x)
-            momentum = 0.1 if bn.momentum is None else bn.momentum
-            g, b = bn.weight.detach(), bn.bias.detach()
-            if i == 0:   # BN1 + PReLU
-                call('srx_bn_train_fwd', _p(y), _p(part), part.shape[0], m, c, 1, bn.eps, momentum, _p(g), _p(b), None, _p(out),
-                     ACT_PRELU, 0.0, _p(block.prelu.weight.detach()), _p(mean), _p(invstd), _p(bn.running_mean),
-                     _p(bn.running_var), _p(bn.num_batches_tracked), s)
-            else:        # BN2 + skip connection
-                call('srx_bn_train_fwd', _p(y), _p(part), part.shape[0], m, c, 1, bn.eps, momentum, _p(g), _p(b), _p(x), _p(out),
-                     ACT_NONE, 0.0, None, _p(mean), _p(invstd), _p(bn.running_mean), _p(bn.running_var),
-                     _p(bn.num_batches_tracked), s)
-            descs.append(d)
-            ys.append(y)
-            stats += [mean, invstd]
-            if i == 0:
-                a1 = inp = out
-        ctx.block, ctx.descs = block, descs
-        ctx.packs = (convs[0]._st.wpk_bwd, convs[1]._st.wpk_bwd)
-        ctx.save_for_backward(x, ys[0], a1, ys[1], *stats)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout: Tensor):
-        x, y1, a1, y2, mean1, inv1, mean2, inv2 = ctx.saved_tensors
-        block = ctx.block
-        dout = _chk(dout, 'residual_block.grad')
-        n, h, w, c = x.shape
-        m = n * h * w
-        L, s = _lib.lib(), _stream()
-        queue = wgrad_queue[0]
-
-        def bn_bwd(dz_in, y, mean, invstd, bn, act, prelu):
-            sums = torch.empty(2 * c + 4, dtype=torch.float32, device=x.device)
-            dy = torch.empty_like(y)
-            nws = L.srx_bn_bwd_ws_floats(m, c)
-            pw = None if prelu is None else prelu.detach()
-            call('srx_bn_act_bwd', _p(dz_in), _p(y), _p(mean), _p(invstd), _p(bn.weight.detach()), _p(bn.bias.detach()),
-                 _p(sums), _p(dy), m, c, 1, act, 0.0, _p(pw), 1, _p(bn.weight.grad), _p(bn.bias.grad),
-                 None if prelu is None else _p(prelu.grad), _p(_ws(nws, y)), nws, s)
-            return dy
-
-        def wgrad(conv, d, inp, dy):
-            if queue is not None:
-                queue.add(d, _p(inp), _p(dy), _p(conv.weight.grad), None, (inp, dy))
-                return
-            dref = C.byref(d)
-            nws = L.srx_conv2d_bwd_weight_ws_floats(dref)
-            call('srx_conv2d_bwd_weight', dref, _p(inp), _p(dy), _p(conv.weight.grad), 1, None, _p(_ws(nws, inp)), nws, s)
-
-        dy2 = bn_bwd(dout, y2, mean2, inv2, block.bn2, ACT_NONE, None)
-        wgrad(block.conv2, ctx.descs[1], a1, dy2)
-        da1 = torch.empty_like(x)
-        dref = C.byref(ctx.descs[1])
-        nws = L.srx_conv2d_bwd_data_ws_floats(dref)
-        call('srx_conv2d_bwd_data', dref, _p(dy2), _p(ctx.packs[1]), _p(da1), 0, _p(_ws(nws, x)) if nws else None, nws, s)
-        dy1 = bn_bwd(da1, y1, mean1, inv1, block.bn1, ACT_PRELU, block.prelu.weight)
-        wgrad(block.conv1, ctx.descs[0], x, dy1)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            dref = C.byref(ctx.descs[0])
-            nws = L.srx_conv2d_bwd_data_ws_floats(dref)
-            call('srx_conv2d_bwd_data_add', dref, _p(dy1), _p(ctx.packs[0]), _p(dout), _p(dx), _p(_ws(nws, x)) if nws else None,
-                 nws, s)
-        return (dx, None) + (None,) * (len(ctx.needs_input_grad) - 2)
-
-
 class _ResidualTower(Function):
-    """The chain of SRGAN ``ResidualBlock``s (srgan/generator.py:42-45,76) as ONE autograd node: the same kernels as
-    ``_ResidualBlock`` per block, plus what only a node that sees neighbouring layers can do -- the first pass of every
-    BatchNorm backward (the per-channel sums of dz and dz * xhat) rides in the epilogue of the data gradient that
-    PRODUCES that BatchNorm's output gradient (``srx_conv2d_bwd_data_bn``): conv2's data gradient reduces for bn1 + PReLU
-    of its own block, conv1's (plus the skip gradient) for bn2 of the block BEFORE.  32 of the 33 ``bn_bwd_reduce``
-    launches of a generator backward pass (and their second read of two 2.4 MB tensors each) disappear.
+    """The chain of SRGAN ``ResidualBlock``s -- each ``x + BN2(conv2(PReLU(BN1(conv1(x)))))`` (srgan/residual.py:86-91;
+    srgan/generator.py:42-45,76) -- as ONE autograd node in training mode, for one block or many.  Per block: the skip
+    connection's gradient, which autograd would add to conv1's input gradient in a pass of its own, is the epilogue of conv1's
+    data gradient (``srx_conv2d_bwd_data_add``); parameter gradients accumulate straight into the flat ``.grad`` buffers; the
+    conv weight gradients go to the ``WeightGradQueue`` when one is installed.  And what only a node that sees neighbouring
+    layers can do -- the first pass of every BatchNorm backward (the per-channel sums of dz and dz * xhat) rides in the
+    epilogue of the data gradient that PRODUCES that BatchNorm's output gradient (``srx_conv2d_bwd_data_bn``): conv2's data
+    gradient reduces for bn1 + PReLU of its own block, conv1's (plus the skip gradient) for bn2 of the block BEFORE.  32 of
+    the 33 ``bn_bwd_reduce`` launches of a generator backward pass (and their second read of two 2.4 MB tensors each) disappear.
     """
 
     @staticmethod
@@ -921,27 +905,21 @@ class _ResidualTower(Function):
                          _p(st.wpk_fwd), None, _p(y), _p(part), s)
                     pending = None
                 else:
-                    nws = L.srx_conv2d_fwd_ws_floats(dref)
-                    call('srx_conv2d_fwd', dref, _p(inp), _p(st.wpk_fwd), None, _p(y), _p(part), _p(_ws(nws, x)) if nws else None, nws, s)
-                mean = torch.empty(c, dtype=torch.float32, device=x.device)
-                invstd = torch.empty(c, dtype=torch.float32, device=x.device)
+                    _conv_fwd(d, _p(inp), _p(st.wpk_fwd), None, _p(y), x, s, part_ptr=_p(part))
                 out = torch.empty_like(x)
-                momentum = 0.1 if bn.momentum is None else bn.momentum
-                g, b = bn.weight.detach(), bn.bias.detach()
                 last = i == 1 and bi == len(blocks) - 1
                 if fuse and not last:  # statistics only; the normalise pass rides in the next conv's launch
-                    call('srx_bn_finalize', _p(part), part.shape[0], m, c, bn.eps, momentum, _p(mean), _p(invstd),
-                         _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), s)
+                    mean = torch.empty(c, dtype=torch.float32, device=x.device)
+                    invstd = torch.empty(c, dtype=torch.float32, device=x.device)
+                    call('srx_bn_finalize', _p(part), part.shape[0], m, c, bn.eps, 0.1 if bn.momentum is None else bn.momentum,
+                         _p(mean), _p(invstd), _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), s)
+                    g, b = bn.weight.detach(), bn.bias.detach()
                     pending = (y, mean, invstd, g, b, block.prelu.weight.detach(), None, out) if i == 0 else \
                         (y, mean, invstd, g, b, None, x, out)
-                elif i == 0:   # BN1 + PReLU
-                    call('srx_bn_train_fwd', _p(y), _p(part), part.shape[0], m, c, 1, bn.eps, momentum, _p(g), _p(b), None, _p(out),
-                         ACT_PRELU, 0.0, _p(block.prelu.weight.detach()), _p(mean), _p(invstd), _p(bn.running_mean),
-                         _p(bn.running_var), _p(bn.num_batches_tracked), s)
-                else:        # BN2 + skip connection
-                    call('srx_bn_train_fwd', _p(y), _p(part), part.shape[0], m, c, 1, bn.eps, momentum, _p(g), _p(b), _p(x), _p(out),
-                         ACT_NONE, 0.0, None, _p(mean), _p(invstd), _p(bn.running_mean), _p(bn.running_var),
-                         _p(bn.num_batches_tracked), s)
+                else:  # BN1 + PReLU, or BN2 + skip connection
+                    mean, invstd = _bn_train_fwd(y, part, m, c, 1, bn.eps, bn.momentum, bn.weight, bn.bias, None if i == 0 else x, out,
+                                                 ACT_PRELU if i == 0 else ACT_NONE, 0.0, block.prelu.weight if i == 0 else None,
+                                                 bn.running_mean, bn.running_var, bn.num_batches_tracked, s)
                 if i == 0:
                     a1 = inp = out
                 ys.append(y)
@@ -961,28 +939,23 @@ class _ResidualTower(Function):
         n, h, w, c = grad.shape
         m = n * h * w
         L, s = _lib.lib(), _stream()
-        queue = wgrad_queue[0]
         dref = C.byref(d)
         rows = L.srx_conv2d_bwd_data_bn_rows(dref)  # 0: the layers do not run on the row-tile kernel at this size
         if _dev.NO_BN_DGRAD_FUSE:  # developer switch (A/B runs): separate reduce launches
             rows = 0
-        W = 2 * c + 4
         nws_d = L.srx_conv2d_bwd_data_ws_floats(dref)
+        W = 2 * c + 4
 
         def finish(dz_in, y, mean, invstd, bn, act, prelu, table):
             """dy of act(BN(y)) given dz_in; the reduce pass comes from `table` when the producer of dz_in filled one"""
+            pg = None if prelu is None else prelu.grad
+            if table is None:
+                return _bn_act_bwd(dz_in, y, mean, invstd, bn.weight, bn.bias, prelu, m, c, 1, act, 0.0, True,
+                                   (bn.weight.grad, bn.bias.grad, pg), s)[0]
             sums = torch.empty(W, dtype=torch.float32, device=grad.device)
             dy = torch.empty_like(y)
-            pw = None if prelu is None else prelu.detach()
-            gw, gb = bn.weight.detach(), bn.bias.detach()
-            pg = None if prelu is None else _p(prelu.grad)
-            if table is not None:
-                call('srx_bn_act_bwd_finish', _p(dz_in), _p(y), _p(mean), _p(invstd), _p(gw), _p(gb), _p(table), rows, 2, _p(sums),
-                     _p(dy), m, c, act, 0.0, _p(pw), _p(bn.weight.grad), _p(bn.bias.grad), pg, s)
-            else:
-                nws = L.srx_bn_bwd_ws_floats(m, c)
-                call('srx_bn_act_bwd', _p(dz_in), _p(y), _p(mean), _p(invstd), _p(gw), _p(gb), _p(sums), _p(dy), m, c, 1, act, 0.0,
-                     _p(pw), 1, _p(bn.weight.grad), _p(bn.bias.grad), pg, _p(_ws(nws, y)), nws, s)
+            call('srx_bn_act_bwd_finish', _p(dz_in), _p(y), _p(mean), _p(invstd), _p(bn.weight), _p(bn.bias), _p(table), rows, 2,
+                 _p(sums), _p(dy), m, c, act, 0.0, _p(prelu), _p(bn.weight.grad), _p(bn.bias.grad), _p(pg), s)
             return dy
 
         def dgrad(pack, dy, addend, below):
@@ -994,19 +967,11 @@ class _ResidualTower(Function):
                 call('srx_conv2d_bwd_data_bn', dref, _p(dy), _p(pack), _p(addend), _p(dx), _p(y), _p(mean), _p(invstd),
                      _p(bn.weight.detach()), _p(bn.bias.detach()), None if prelu is None else _p(prelu.detach()), _p(table), s)
                 return dx, table
-            ws = _ws(nws_d, dy) if nws_d else None
-            if addend is None:
-                call('srx_conv2d_bwd_data', dref, _p(dy), _p(pack), _p(dx), 0, _p(ws), nws_d, s)
-            else:
-                call('srx_conv2d_bwd_data_add', dref, _p(dy), _p(pack), _p(addend), _p(dx), _p(ws), nws_d, s)
+            _conv_dgrad(d, _p(dy), _p(pack), _p(dx), dy, s, addend_ptr=_p(addend), nws=nws_d)
             return dx, None
 
         def wgrad(conv, inp, dy):
-            if queue is not None:
-                queue.add(d, _p(inp), _p(dy), _p(conv.weight.grad), None, (inp, dy))
-                return
-            nws = L.srx_conv2d_bwd_weight_ws_floats(dref)
-            call('srx_conv2d_bwd_weight', dref, _p(inp), _p(dy), _p(conv.weight.grad), 1, None, _p(_ws(nws, inp)), nws, s)
+            _conv_wgrad(d, _p(inp), _p(dy), None, conv.weight.grad, None, (inp, dy), inp, s)
 
         # With a table from the producer, the APPLY pass of a BatchNorm backward rides in the data gradient that consumes its
         # result too (srx_conv2d_bwd_data_bn_in: the layer's input gradient is formed while the patch is staged and written on
@@ -1090,9 +1055,8 @@ def residual_block_fused_ok(block) -> bool:
 
 
 def residual_block(x: Tensor, block) -> Tensor:
-    ps = (block.conv1.weight, block.bn1.weight, block.bn1.bias, block.prelu.weight, block.conv2.weight, block.bn2.weight,
-          block.bn2.bias)
-    return _ResidualBlock.apply(x, block, *ps)
+    """One ``ResidualBlock`` that satisfies ``residual_block_fused_ok``: a tower of one."""
+    return residual_tower(x, [block])
 
 
 # --------------------------------------------------------------------------- activations
@@ -1249,7 +1213,7 @@ class _FrozenConvStack(Function):
         source = _chk(source, 'conv_stack.source')
         n_src = source.shape[0]
         x = source if target is None else torch.cat([source, _chk(target, 'conv_stack.target')], dim=0)
-        L, s = _lib.lib(), _stream()
+        s = _stream()
         ctx.bf16s = _bf16_stack_ok(layers, x.shape)
         if ctx.bf16s:
             return _FrozenConvStack._forward_bf16s(ctx, x, n_src, target is None, layers)
@@ -1265,22 +1229,17 @@ class _FrozenConvStack(Function):
                 if st.act not in (ACT_RELU, ACT_LRELU) or st.stride != 1 or st.shuffle:
                     raise RuntimeError('conv_stack: stride-1 conv + ReLU / LeakyReLU layers only')
                 d = st.desc(n, h, w)
-                dref = C.byref(d)
                 y = torch.empty(st.out_shape(n, h, w), dtype=torch.float32, device=x.device)
                 b = None if conv.bias is None else _chk(conv.bias.detach(), 'conv_stack.bias')
                 # wide 3x3 layers: Winograd F(2x2, 3x3), 2.25x fewer fp32 multiplications (csrc/wino.hip)
                 wino = wino_layer_ok(st, d)
                 if wino:
                     st.pack_wino(conv.weight, d, need_bwd=ctx.needs_input_grad[0])
-                    nws = L.srx_wino_ws_floats(dref, 0)
-                    ws = _ws(nws, x) if nws else None
-                    call('srx_wino_fwd', dref, _p(x), _p(st.wino_fwd), _p(b), _p(y), _p(ws), nws, s)
+                    _wino_fwd(d, x, st.wino_fwd, b, y, None, s)
                     plan.append(('conv', st, ('wino', st.wino_bwd)))
                 else:
                     st.pack(conv.weight, d)
-                    nws = L.srx_conv2d_fwd_ws_floats(dref)
-                    ws = _ws(nws, x) if nws else None
-                    call('srx_conv2d_fwd', dref, _p(x), _p(st.wpk_fwd), _p(b), _p(y), None, _p(ws), nws, s)
+                    _conv_fwd(d, _p(x), _p(st.wpk_fwd), _p(b), _p(y), x, s)
                     plan.append(('conv', st, st.wpk_bwd))
             saved.append(y)
             x = y
@@ -1365,12 +1324,8 @@ class _FrozenConvStack(Function):
         st = plan[0][1]
         x = saved[0][:n]
         _, h, w, _c = x.shape
-        d = st.desc(n, h, w)
-        dref = C.byref(d)
         dx = torch.empty_like(x)
-        nws = L.srx_conv2d_bwd_data_ws_floats(dref)
-        ws = _ws(nws, x) if nws else None
-        call('srx_conv2d_bwd_data', dref, _p(g), _p(st.wpk_bwd), _p(dx), 0, _p(ws), nws, s)
+        _conv_dgrad(st.desc(n, h, w), _p(g), _p(st.wpk_bwd), _p(dx), x, s)
         return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
     @staticmethod
@@ -1380,7 +1335,7 @@ class _FrozenConvStack(Function):
             return (None,) * len(ctx.needs_input_grad)
         if ctx.bf16s:
             return _FrozenConvStack._backward_bf16s(ctx, dfs)
-        L, s = _lib.lib(), _stream()
+        s = _stream()
         g = _chk(dfs, 'conv_stack.grad')
         # the topmost activation's backward is the only elementwise pass
         top = saved[-1][:n]
@@ -1407,27 +1362,10 @@ class _FrozenConvStack(Function):
                 g = dx
                 continue
             _, h, w, _c = x.shape
-            d = st.desc(n, h, w)
-            dref = C.byref(d)
-            dx = torch.empty_like(x)
             fold = below is not None and below[0] == 'conv'   # x = act(conv below): fold that activation's backward in
-            if isinstance(wpk_bwd, tuple) and (not fold or below[1].act == ACT_RELU) and wpk_bwd[1] is not None:
-                nws = L.srx_wino_ws_floats(dref, 1)
-                ws = _ws(nws, x) if nws else None
-                call('srx_wino_bwd_data', dref, _p(g), _p(wpk_bwd[1]), _p(x) if fold else None, _p(dx), _p(ws), nws, s)
-                g = dx
-                continue
-            if isinstance(wpk_bwd, tuple):  # (a Winograd forward whose data gradient takes the direct kernel: pack it now)
-                st.pack(ctx.masters[i], d)
-                wpk_bwd = st.wpk_bwd
-            nws = L.srx_conv2d_bwd_data_ws_floats(dref)
-            ws = _ws(nws, x) if nws else None
-            if fold:
-                slope = 0.0 if below[1].act == ACT_RELU else below[1].slope
-                call('srx_conv2d_bwd_data_act', dref, _p(g), _p(wpk_bwd), _p(x), slope, 0, st.cin_s, 0, _p(dx), _p(ws), nws, s)
-            else:
-                call('srx_conv2d_bwd_data', dref, _p(g), _p(wpk_bwd), _p(dx), 0, _p(ws), nws, s)
-            g = dx
+            wino = isinstance(wpk_bwd, tuple)
+            g, _ = _layer_dgrad(st, st.desc(n, h, w), ctx.masters[i], wino, wpk_bwd[1] if wino else None, None if wino else wpk_bwd,
+                                g, x, below[1] if fold else None, s)
         return (g, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
 
@@ -1505,9 +1443,7 @@ class _Linear(Function):
         if has_bias and ctx.needs_input_grad[2]:
             sink = _sink(bparam)
             db = None if sink is not None else torch.empty(j, dtype=torch.float32, device=x.device)
-            n2 = _lib.lib().srx_colsum_ws_floats(bsz, j)
-            call('srx_colsum', _p(dy), _p(db if sink is None else sink), bsz, j, j, 0 if sink is None else 1,
-                 _p(_ws(n2, x)), n2, s)
+            _colsum(_p(dy), bsz, j, j, db if sink is None else sink, 0 if sink is None else 1, x, s)
         return dx, dw, db, None, None
 
 
@@ -1885,8 +1821,6 @@ class FoldedConv:
         if cs != st.cin_s:
             raise RuntimeError(f'folded_conv: input has {cs} channels (stride), layer expects {st.cin_s}')
         d = st.desc(n, h, w)
-        dref = C.byref(d)
-        L = _lib.lib()
         y = torch.empty(st.out_shape(n, h, w), dtype=torch.float32, device=x.device)
         r = None
         if residual is not None:
@@ -1896,19 +1830,15 @@ class FoldedConv:
         # exact-fp32 inference: the 3x3 layers of the trunk as Winograd F(2x2, 3x3) (csrc/wino.hip; 4/9 of the multiplications,
         # PReLU / skip in its epilogue) -- at 1080p each 64 -> 64 layer is 16 200 tile blocks
         if (st.precision == 0 and not _dev.NO_WINO and st.act in (ACT_NONE, ACT_RELU, ACT_LRELU)
-                and L.srx_wino_infer_applicable(dref) == 1):
+                and _lib.lib().srx_wino_infer_applicable(C.byref(d)) == 1):
             st.pack_wino(self.w, d, need_bwd=False)
-            nws = L.srx_wino_ws_floats(dref, 0)
+            dref = C.byref(d)
+            nws = _lib.lib().srx_wino_ws_floats(dref, 0)
             ws = _ws(nws, x) if nws else None
             call('srx_wino_fwd_act', dref, _p(x), _p(st.wino_fwd), _p(self.b), _p(r), _p(y), _p(ws), nws, _stream())
             return y
         st.pack(self.w, d)
-        nws = L.srx_conv2d_fwd_ws_floats(dref)
-        ws = _ws(nws, x) if nws else None
-        if residual is None:
-            call('srx_conv2d_fwd', dref, _p(x), _p(st.wpk_fwd), _p(self.b), _p(y), None, _p(ws), nws, _stream())
-        else:
-            call('srx_conv2d_fwd_residual', dref, _p(x), _p(st.wpk_fwd), _p(self.b), _p(r), 1.0, _p(y), _p(ws), nws, _stream())
+        _conv_fwd(d, _p(x), _p(st.wpk_fwd), _p(self.b), _p(y), x, _stream(), residual=None if residual is None else (_p(r), 1.0))
         return y
 
 
@@ -1940,7 +1870,6 @@ class _DenseBlock(Function):
         g = states[0].cout
         total = c0 + 4 * g
         m = n * h * w
-        L = _lib.lib()
         s = _stream()
         dev = x.device
         buf = torch.empty((n, h, w, total), dtype=torch.float32, device=dev)
@@ -1953,17 +1882,14 @@ class _DenseBlock(Function):
             d = Conv2dDesc(n, h, w, cin, total, st.cout, st.cout if last else total, st.k, st.k, st.stride, st.pad, 0,
                            st.act, st.slope, 0, st.precision)
             descs.append(d)
-            dref = C.byref(d)
             st.pack(masters[k], d)
             bias = wb[2 * k + 1]
             bp = None if bias is None else _p(_chk(bias.detach(), 'dense_block.bias'))
-            nws = L.srx_conv2d_fwd_ws_floats(dref)
-            ws = _ws(nws, x) if nws else None
             if last:  # y = conv5(...) * scale + x in the conv's epilogue (esrgan/residual.py:86)
                 y = torch.empty_like(x)
-                call('srx_conv2d_fwd_residual', dref, _p(buf), _p(st.wpk_fwd), bp, _p(x), float(scale), _p(y), _p(ws), nws, s)
+                _conv_fwd(d, _p(buf), _p(st.wpk_fwd), bp, _p(y), x, s, residual=(_p(x), float(scale)))
             else:
-                call('srx_conv2d_fwd', dref, _p(buf), _p(st.wpk_fwd), bp, buf.data_ptr() + 4 * cin, None, _p(ws), nws, s)
+                _conv_fwd(d, _p(buf), _p(st.wpk_fwd), bp, buf.data_ptr() + 4 * cin, x, s)
         ctx.states, ctx.descs, ctx.scale = states, descs, float(scale)
         ctx.dims = (n, h, w, c0, g, total, m)
         ctx.params = wb
@@ -1976,7 +1902,6 @@ class _DenseBlock(Function):
         (buf,) = ctx.saved_tensors
         dy = _chk(dy, 'dense_block.grad')
         n, h, w, c0, g, total, m = ctx.dims
-        L = _lib.lib()
         s = _stream()
         dev = dy.device
         gbuf = torch.empty((n, h, w, total), dtype=torch.float32, device=dev)
@@ -1985,53 +1910,20 @@ class _DenseBlock(Function):
         grads = [None] * 10
         for k in (4, 3, 2, 1, 0):
             st, d = ctx.states[k], ctx.descs[k]
-            dref = C.byref(d)
             cin = c0 + k * g
             if k == 4:
                 gk, ldg = g5.data_ptr(), st.cout
             else:  # this conv's output gradient is complete AND masked: the data gradient of conv k+1 finished the slice
                 gk, ldg = gbuf.data_ptr() + 4 * cin, total
-            wparam, bparam = ctx.params[2 * k], ctx.params[2 * k + 1]
-            bias_done = False
-            if ctx.needs_input_grad[4 + 2 * k]:
-                sink = _sink(wparam)
-                dw = None if sink is not None else torch.empty((st.cout, st.cin, st.k, st.k), dtype=torch.float32,
-                                                                 device=dev)
-                bptr = None
-                if bparam is not None and ctx.needs_input_grad[5 + 2 * k]:  # bias gradient in the same kernel
-                    bsink = _sink(bparam)
-                    if (bsink is None) == (sink is None):
-                        if bsink is None:
-                            grads[2 * k + 1] = torch.empty(st.cout, dtype=torch.float32, device=dev)
-                        bptr = _p(grads[2 * k + 1] if bsink is None else bsink)
-                        bias_done = True
-                queue = wgrad_queue[0]
-                if queue is not None and sink is not None:
-                    queue.add(d, _p(buf), gk, _p(sink), bptr, (buf, gbuf, g5))
-                else:
-                    nws = L.srx_conv2d_bwd_weight_ws_floats(dref)
-                    call('srx_conv2d_bwd_weight', dref, _p(buf), gk, _p(dw if sink is None else sink),
-                         0 if sink is None else 1, bptr, _p(_ws(nws, dy)), nws, s)
-                grads[2 * k] = dw
-            if bparam is not None and ctx.needs_input_grad[5 + 2 * k] and not bias_done:
-                sink = _sink(bparam)
-                db = None if sink is not None else torch.empty(st.cout, dtype=torch.float32, device=dev)
-                nws = L.srx_colsum_ws_floats(m, st.cout)
-                call('srx_colsum', gk, _p(db if sink is None else sink), m, st.cout, ldg, 0 if sink is None else 1,
-                     _p(_ws(nws, dy)), nws, s)
-                grads[2 * k + 1] = db
+            grads[2 * k], grads[2 * k + 1] = _conv_param_grads(
+                st, d, _p(buf), gk, m, ldg, ctx.params[2 * k] if ctx.needs_input_grad[4 + 2 * k] else None,
+                ctx.params[2 * k + 1] if ctx.needs_input_grad[5 + 2 * k] else None, (buf, gbuf, g5), dy, s)
             if k > 0 or ctx.needs_input_grad[0]:
-                nws = L.srx_conv2d_bwd_data_ws_floats(dref)
-                ws = _ws(nws, dy) if nws else None
                 # conv5 writes all `total` channels; the others add their share to the first `cin`.  The slice of
                 # conv k's output, channels [cin - g, cin), is complete with this call (every later conv has added
                 # its share): the LeakyReLU backward of conv k (esrgan/residual.py:81-84) is applied to it on the way out
-                if k > 0:
-                    prev = ctx.states[k - 1]
-                    call('srx_conv2d_bwd_data_act', dref, gk, _p(ctx.packs[k]), _p(buf), prev.slope, cin - g, cin,
-                         0 if k == 4 else 1, _p(gbuf), _p(ws), nws, s)
-                else:
-                    call('srx_conv2d_bwd_data', dref, gk, _p(ctx.packs[k]), _p(gbuf), 1, _p(ws), nws, s)
+                mask = (_p(buf), ctx.states[k - 1].slope, cin - g, cin) if k > 0 else None
+                _conv_dgrad(d, gk, _p(ctx.packs[k]), _p(gbuf), dy, s, accumulate=0 if k == 4 else 1, mask=mask)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(dy)
@@ -2131,7 +2023,6 @@ class _RRDBTrunk(Function):
         g = states[0][0].cout
         total = c0 + 4 * g
         m = n * h * w
-        L = _lib.lib()
         s = _stream()
         need_bwd = any(ctx.needs_input_grad)
         # without a backward pass four rotating buffers are enough (an RRDB reads its first block's input at its end)
@@ -2154,20 +2045,16 @@ class _RRDBTrunk(Function):
                 d = Conv2dDesc(n, h, w, cin, total, st.cout, total, st.k, st.k, st.stride, st.pad, 0, st.act, st.slope, 0,
                                st.precision)
                 row.append(d)
-                dref = C.byref(d)
                 st.fused_only = fused  # fused: forward and data gradients read RDBPack's bf16 streams, nothing reads wpk_*
                 if fused:
                     continue
                 st.pack(masters[i][k], d)
                 bias = wb[10 * i + 2 * k + 1]
                 bp = None if bias is None else _p(_chk(bias.detach(), 'rrdb_trunk.bias'))
-                nws = L.srx_conv2d_fwd_ws_floats(dref)
-                ws = _ws(nws, x) if nws else None
                 if k == 4:  # the next block's input = conv5 * scale + x, x = the first 64 channels of this buffer (:86)
-                    call('srx_conv2d_fwd_residual', dref, _p(buf), _p(st.wpk_fwd), bp, _p(buf), float(rdb_scales[i]), _p(nxt),
-                         _p(ws), nws, s)
+                    _conv_fwd(d, _p(buf), _p(st.wpk_fwd), bp, _p(nxt), x, s, residual=(_p(buf), float(rdb_scales[i])))
                 else:
-                    call('srx_conv2d_fwd', dref, _p(buf), _p(st.wpk_fwd), bp, buf.data_ptr() + 4 * cin, None, _p(ws), nws, s)
+                    _conv_fwd(d, _p(buf), _p(st.wpk_fwd), bp, buf.data_ptr() + 4 * cin, x, s)
             if fused:
                 biases = (C.c_void_p * 5)(*[_p(_chk(wb[10 * i + 2 * k + 1].detach(), 'rrdb_trunk.bias')) for k in range(5)])
                 if i % 3 == 2:  # end of an RRDB: its `out * 0.2 + x` (:128) is the second addend of this block's last epilogue
@@ -2204,7 +2091,6 @@ class _RRDBTrunk(Function):
         grad = _chk(dy, 'rrdb_trunk.grad')
         n, h, w, c0, g, total, m, nb = ctx.dims
         rdb_scales, rrdb_scale = ctx.scales
-        L = _lib.lib()
         s = _stream()
         dev = grad.device
         grads = [None] * (10 * nb)
@@ -2257,33 +2143,12 @@ class _RRDBTrunk(Function):
                     gk, wscale = grad.data_ptr(), eff * rdb_scales[i]
                 else:  # complete and masked: the data gradient of conv k+1 finished this slice of the shared buffer
                     gk, wscale = gbuf.data_ptr() + 4 * cin, 1.0
-                dref = C.byref(d)
-                wparam, bparam = ctx.params[10 * i + 2 * k], ctx.params[10 * i + 2 * k + 1]
-                if paired and k < 4:
-                    pass  # (queued above: the queue runs after the whole backward pass, when every slice of gbuf is complete)
-                elif ctx.needs_input_grad[6 + 10 * i + 2 * k]:
-                    sink = _sink(wparam)
-                    dw = None if sink is not None else torch.empty((st.cout, st.cin, st.k, st.k), dtype=torch.float32,
-                                                                     device=dev)
-                    bptr = None
-                    if bparam is not None and ctx.needs_input_grad[7 + 10 * i + 2 * k]:
-                        bsink = _sink(bparam)
-                        if (bsink is None) != (sink is None):
-                            raise RuntimeError('rrdb_trunk: weight and bias of a conv must both (or neither) have a gradient sink')
-                        if bsink is None:
-                            grads[10 * i + 2 * k + 1] = torch.empty(st.cout, dtype=torch.float32, device=dev)
-                        bptr = _p(grads[10 * i + 2 * k + 1] if bsink is None else bsink)
-                    if queue is not None and sink is not None:
-                        queue.add(d, _p(buf), gk, _p(sink), bptr, keep, wscale)
-                    else:
-                        nws = L.srx_conv2d_bwd_weight_ws_floats(dref)
-                        one = lambda v: (C.c_void_p * 1)(v)  # noqa: E731
-                        call('srx_conv2d_bwd_weight_multi_scaled', dref, 1, 1, one(_p(buf)), one(gk),
-                             one(_p(dw if sink is None else sink)), 0 if sink is None else 1, one(bptr),
-                             (C.c_float * 1)(wscale), _p(_ws(nws, grad)), nws, s)
-                    grads[10 * i + 2 * k] = dw
-                elif bparam is not None and ctx.needs_input_grad[7 + 10 * i + 2 * k]:
-                    raise RuntimeError('rrdb_trunk: a bias gradient without its weight gradient is not implemented')
+                # (pairs were queued above: the queue runs after the whole backward pass, when every slice of gbuf is complete.
+                # With a scale the bias gradient rides in the weight-gradient kernel, or the launcher refuses)
+                if not (paired and k < 4):
+                    grads[10 * i + 2 * k], grads[10 * i + 2 * k + 1] = _conv_param_grads(
+                        st, d, _p(buf), gk, m, d.Cout_s, ctx.params[10 * i + 2 * k] if ctx.needs_input_grad[6 + 10 * i + 2 * k] else None,
+                        ctx.params[10 * i + 2 * k + 1] if ctx.needs_input_grad[7 + 10 * i + 2 * k] else None, keep, grad, s, scale=wscale)
                 if ctx.pack is not None:
                     continue  # (the block's five data gradients are one launch, below)
                 e = _lib.DgradEpilogue()
@@ -2302,7 +2167,7 @@ class _RRDBTrunk(Function):
                                     st.precision)
                     out = dx
                 ddref = C.byref(dd)
-                nws = L.srx_conv2d_bwd_data_ws_floats(ddref)
+                nws = _lib.lib().srx_conv2d_bwd_data_ws_floats(ddref)
                 ws = _ws(nws, grad) if nws else None
                 call('srx_conv2d_bwd_data_ex', ddref, gk, _p(st.wpk_bwd), _p(out), C.byref(e), _p(ws), nws, s)
             grad = dx
