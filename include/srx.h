@@ -636,6 +636,38 @@ int srx_gan_head_bwd(const srx_gan_head_t* h, const float* hidden, const float* 
 int srx_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* lr, float beta1,
                   float beta2, float eps, float grad_scale, int64_t* step, void* stream);
 
+/* Gradient guard: what torch.cuda.amp.GradScaler's skipped step (srgan/trainer.py:196,382-388) and
+ * torch.nn.utils.clip_grad_norm_ do, decided on the device so that the pair of calls below replays
+ * from a captured graph.  The state lives in DEVICE memory; the host zeroes it once. */
+typedef struct {
+  float   scale;    /* multiplies the gradient in srx_adam_step_guarded, on top of grad_scale */
+  int32_t skip;     /* 1: this step is skipped */
+  float   norm;     /* l2 norm of grad_scale * g of the last call (fp64 sum, rounded once; +inf / NaN
+                       when g is not finite) */
+  int32_t reserved;
+  int64_t skipped;  /* running count of skipped steps */
+  int64_t clipped;  /* running count of steps with scale < 1 (a skipped step has scale 0: it counts) */
+} srx_grad_guard_t;
+
+/* One streaming read of g[0..n) and a one-workgroup finalise.  Squares and sums are fp64 throughout,
+ * so the sum is finite exactly when every g[i] is; the order of the sum is a fixed function of n
+ * (no floating-point atomics): two calls on the same buffer write the same bits.
+ *   norm  = |grad_scale| * sqrt(sum g^2)
+ *   skip  = skip_nonfinite && the sum is not finite
+ *   scale = 0 when skip; else min(1, max_norm / (norm + 1e-6)) for a finite max_norm > 0 (NaN stays
+ *           NaN, as in clip_grad_norm_ with error_if_nonfinite=False); else 1
+ * max_norm <= 0 or +inf: no clipping.  ws: srx_grad_guard_ws_bytes(n) bytes, 8-byte aligned, needs
+ * no initialisation; g 16-byte, state 8-byte aligned. */
+size_t srx_grad_guard_ws_bytes(int64_t n);
+int srx_grad_guard(const float* g, int64_t n, float grad_scale, float max_norm, int skip_nonfinite,
+                   void* ws, size_t ws_bytes, srx_grad_guard_t* state, void* stream);
+/* srx_adam_step behind the guard's decision, read from `state` on the device: with state->skip set
+ * neither *step nor p, m, v change; otherwise g is multiplied by grad_scale * state->scale (one fp32
+ * product: with scale == 1 the results are srx_adam_step's bit for bit). */
+int srx_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, const float* lr, float beta1,
+                          float beta2, float eps, float grad_scale, int64_t* step,
+                          const srx_grad_guard_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -286,6 +286,9 @@ _SIGS = {
     'srx_gan_head_fwd': (_I, [C.POINTER(GanHead), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'srx_gan_head_bwd': (_I, [C.POINTER(GanHead), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     'srx_adam_step': (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _P, _P]),
+    'srx_grad_guard_ws_bytes': (_Z, [_L]),
+    'srx_grad_guard': (_I, [_P, _L, _F, _F, _I, _P, _Z, _P, _P]),
+    'srx_adam_step_guarded': (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _P, _P, _P]),
 }
 # functions whose int return value is data, not a status
 _UNCHECKED = {'srx_wino_applicable', 'srx_wino_infer_applicable', 'srx_conv3x3_bf16s_applicable', 'srx_wino_stat_rows', 'srx_conv2d_bwd_data_bn_rows', 'srx_conv2d_fwd_bn_in_ok', 'srx_conv2d_bwd_data_bn_in_ok', 'srx_pack_table_bytes', 'srx_version', 'srx_last_error', 'srx_device_cus', 'srx_plan_cus', 'srx_prof_stop', 'srx_conv2d_stat_rows', 'srx_bn_stat_rows', 'srx_bn_rows_per_block'}

@@ -12,6 +12,7 @@ into a second one), so that
 
 while ``state_dict()`` / ``load_state_dict()`` keep working on the (now view) parameters.
 """
+import struct
 from typing import Iterable, List
 
 import torch
@@ -79,7 +80,10 @@ class FlatAdam:
     ``lr`` and the step count live on the device (hipGraph friendly).
     """
 
-    def __init__(self, flat: FlatParams, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8):
+    def __init__(self, flat: FlatParams, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm: float = None, skip_nonfinite: bool = False):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:  # (also NaN)
+            raise ValueError(f'FlatAdam: max_grad_norm must be > 0, got {max_grad_norm}')
         self.flat = flat
         self.betas, self.eps = betas, eps
         dev = flat.data.device
@@ -91,6 +95,17 @@ class FlatAdam:
         self.grad_scale = 1.0
         self.pack_table = None  # functional.PackTable of the model's convs (set by the trainer)
         self.param_groups = [{'lr': float(lr), 'initial_lr': float(lr)}]  # StepLR-style access
+        # gradient guard (off by default: ``step`` is then the single srx_adam_step call): the global l2 norm of the
+        # flat gradient is clipped to ``max_grad_norm`` (torch.nn.utils.clip_grad_norm_) and / or a step whose gradient
+        # holds an inf or a NaN is skipped (what GradScaler.step does) -- decided on the device, so it replays in a hipGraph
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        if self.guarded:
+            # allocated once: a captured graph holds these pointers
+            self.guard_state = torch.zeros(4, dtype=torch.int64, device=dev)  # srx_grad_guard_t, 32 bytes
+            ws_bytes = int(call('srx_grad_guard_ws_bytes', flat.numel))
+            self.guard_ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.float64, device=dev)
 
     @property
     def lr(self) -> float:
@@ -107,12 +122,31 @@ class FlatAdam:
     @torch.no_grad()
     def step(self) -> None:
         f = self.flat
-        call('srx_adam_step', f.data.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
-             self.exp_avg_sq.data_ptr(), f.numel, self.lr_dev.data_ptr(), self.betas[0], self.betas[1], self.eps,
-             self.grad_scale, self.step_count.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        st = torch.cuda.current_stream().cuda_stream
+        if self.guarded:
+            call('srx_grad_guard', f.grad.data_ptr(), f.numel, self.grad_scale, self.max_grad_norm or 0.0,
+                 int(self.skip_nonfinite), self.guard_ws.data_ptr(), self.guard_ws.numel() * 8, self.guard_state.data_ptr(), st)
+            call('srx_adam_step_guarded', f.data.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
+                 self.exp_avg_sq.data_ptr(), f.numel, self.lr_dev.data_ptr(), self.betas[0], self.betas[1], self.eps,
+                 self.grad_scale, self.step_count.data_ptr(), self.guard_state.data_ptr(), st)
+        else:
+            call('srx_adam_step', f.data.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
+                 self.exp_avg_sq.data_ptr(), f.numel, self.lr_dev.data_ptr(), self.betas[0], self.betas[1], self.eps,
+                 self.grad_scale, self.step_count.data_ptr(), st)
+        # (on a skipped step the repack rewrites the same weights: the launch sequence of a captured step stays static)
         self.flat.pack_epoch[0] += 1
         if self.pack_table is not None:  # every conv of the model repacked by one launch
             self.pack_table.run()
+
+    def guard_stats(self) -> dict:
+        """The guard's device state after the last ``step`` (one device -> host copy, which synchronises): ``norm`` of the
+        scaled gradient, the ``scale`` applied, whether the step was ``skip``-ped, and the running ``skipped`` / ``clipped``
+        counts (a skipped step has scale 0 and counts as both).  The counts are not part of ``state_dict``: they restart
+        with the process."""
+        if not self.guarded:
+            raise RuntimeError('FlatAdam.guard_stats: no gradient guard (max_grad_norm / skip_nonfinite) on this optimiser')
+        scale, skip, norm, _, skipped, clipped = struct.unpack('<fifiqq', self.guard_state.cpu().numpy().tobytes())
+        return {'norm': norm, 'scale': scale, 'skip': skip, 'skipped': skipped, 'clipped': clipped}
 
     def state_dict(self):
         return {'exp_avg': self.exp_avg, 'exp_avg_sq': self.exp_avg_sq, 'step': self.step_count, 'lr': self._lr}

@@ -129,7 +129,8 @@ class SRGANTrainer:
 
     ``args`` needs the attributes the reference reads (trainer.py:67-84): ``disable_amp, batch_size,
     epochs, gan_checkpoint, local_rank, pretrain_epochs, psnr_checkpoint, skip_image_save,
-    world_size, rank``.  Optional extras: ``use_graphs`` (default True), ``vgg_weights``.
+    world_size, rank``.  Optional extras: ``use_graphs`` (default True), ``vgg_weights``, ``clip_grad_norm`` (float or
+    None) and ``skip_nonfinite_steps`` (bool): the gradient guard of all three optimisers (``optim.FlatAdam``), off by default.
     """
 
     phase_prefix = 'srgan'
@@ -168,6 +169,8 @@ class SRGANTrainer:
         self.main_process = args.rank in [-1, 0]
         self.use_graphs = bool(getattr(args, 'use_graphs', True))
         self.vgg_weights = getattr(args, 'vgg_weights', None)
+        self.clip_grad_norm = getattr(args, 'clip_grad_norm', None)
+        self.skip_nonfinite_steps = bool(getattr(args, 'skip_nonfinite_steps', False))
         # issue the gradient all-reduces even at world size 1 (a one-GPU rehearsal of the RCCL path)
         self.force_collectives = bool(getattr(args, 'force_collectives', False))
         # compute units the launch plans leave to RCCL's channel workgroups while a large gradient bucket is on the wire
@@ -247,9 +250,11 @@ class SRGANTrainer:
 
     def _initialize_optimizers(self) -> None:
         """trainer.py:167-196: three Adam states, two StepLR (epochs // 8, gamma 0.6)."""
-        self.psnr_optimizer = FlatAdam(self.gen_flat, lr=0.0001, betas=(0.9, 0.999))
-        self.disc_optimizer = FlatAdam(self.disc_flat, lr=0.0001, betas=(0.9, 0.999))
-        self.gen_optimizer = FlatAdam(self.gen_flat, lr=0.0001, betas=(0.9, 0.999))
+        guard = {'max_grad_norm': self.clip_grad_norm, 'skip_nonfinite': self.skip_nonfinite_steps}
+        self.psnr_optimizer = FlatAdam(self.gen_flat, lr=0.0001, betas=(0.9, 0.999), **guard)
+        self.disc_optimizer = FlatAdam(self.disc_flat, lr=0.0001, betas=(0.9, 0.999), **guard)
+        self.gen_optimizer = FlatAdam(self.gen_flat, lr=0.0001, betas=(0.9, 0.999), **guard)
+        self._guard_seen = {}  # (phase, 'g' | 'd') -> (skipped, clipped) at the last epoch's end
         if self.distributed:
             for opt in (self.psnr_optimizer, self.gen_optimizer):
                 opt.grad_scale = self.gen_sync.scale
@@ -285,6 +290,25 @@ class SRGANTrainer:
         code without a run simply does not log."""
         if wandb and self.main_process and getattr(wandb, 'run', None) is not None:
             wandb.log({k: (v.item() if torch.is_tensor(v) else v) for k, v in contents.items()}, step=step)
+
+    def _log_guard(self, phase: str, optimizers: dict, step: int) -> None:
+        """End of an epoch, after its synchronise, with a gradient guard on: per optimiser (``{'g' | 'd': FlatAdam}``) the
+        steps skipped and clipped in this epoch and the last gradient norm -- one read-back each, on the logging rank only.
+        ``clipped-steps`` is the device counter's "scale < 1", which a skipped step (scale 0) also meets."""
+        if not self.main_process or not all(opt.guarded for opt in optimizers.values()):
+            return  # guard off (no read-back, no new keys), or a rank that does not log
+        contents = {f'{phase}/skipped-steps': 0, f'{phase}/clipped-steps': 0}
+        for tag, opt in optimizers.items():
+            stats = opt.guard_stats()
+            seen = self._guard_seen.get((phase, tag), (0, 0))
+            skipped, clipped = stats['skipped'] - seen[0], stats['clipped'] - seen[1]
+            self._guard_seen[(phase, tag)] = (stats['skipped'], stats['clipped'])
+            self._log(f'Gradient guard ({phase}, {tag}): {skipped} steps skipped, {clipped} with scale < 1 (the skipped ones '
+                      f'included: {clipped - skipped} clipped and taken), last gradient norm {stats["norm"]:.4g}')
+            contents[f'{phase}/skipped-steps'] += skipped
+            contents[f'{phase}/clipped-steps'] += clipped
+            contents[f'{phase}/grad-norm-{tag}'] = stats['norm']
+        self._log_wandb(contents, step=step)
 
     def _cleanup(self) -> None:
         if wandb and getattr(wandb, 'run', None) is not None:
@@ -499,6 +523,7 @@ class SRGANTrainer:
             throughput = len(self.train_loader) * self.batch_size * self.world_size / time_taken
             self._log(f'Throughput: {round(throughput, 3)} images/sec')
             self._log_wandb({'psnr/throughput/train': throughput, 'psnr/epoch': epoch}, step=step)
+            self._log_guard('psnr', {'g': self.psnr_optimizer}, step)
             self._test(epoch, f'{self.phase_prefix}-psnr', step)
 
     # ------------------------------------------------------------------ GAN phase
@@ -689,6 +714,7 @@ class SRGANTrainer:
             throughput = len(self.train_loader) * self.batch_size * self.world_size / time_taken
             self._log(f'Throughput: {round(throughput, 3)} images/sec')
             self._log_wandb({'gan/throughput/train': throughput, 'gan/epoch': epoch}, step=step)
+            self._log_guard('gan', {'g': self.gen_optimizer, 'd': self.disc_optimizer}, step)
             self.disc_scheduler.step()
             self.gen_scheduler.step()
             self._test(epoch, f'{self.phase_prefix}-gan', step)

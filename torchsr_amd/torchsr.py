@@ -36,6 +36,16 @@ def positive_integer(value: str) -> int:
     return int_value
 
 
+def positive_float(value: str) -> float:
+    try:
+        float_value = float(value)
+    except (TypeError, ValueError):
+        raise ArgumentTypeError(f'invalid float value: \'{value}\'')
+    if not float_value > 0:  # (also NaN)
+        raise ArgumentTypeError('value must be a positive number!')
+    return float_value
+
+
 def get_device(args: Namespace) -> torch.device:
     """torchsr.py:69-98."""
     count = torch.cuda.device_count()
@@ -103,6 +113,12 @@ def parse_args(argv=None) -> Namespace:
     train.add_argument('--no-graphs', action='store_true', help='run the step eagerly instead of as a hipGraph')
     train.add_argument('--device-data', action='store_true',
                        help='keep the decoded images in HBM and crop / flip / bicubic-downsample on the GPU')
+    train.add_argument('--clip-grad-norm', type=positive_float, default=None, metavar='FLOAT',
+                       help='clip the global l2 norm of each model\'s gradient to FLOAT before its Adam step '
+                            '(torch.nn.utils.clip_grad_norm_, computed on the GPU inside the captured step; default: off)')
+    train.add_argument('--skip-nonfinite-steps', action='store_true',
+                       help='skip an optimiser step whose gradient holds an inf or a NaN (what the reference\'s GradScaler '
+                            'does); the skipped steps are counted and logged per epoch')
     test = commands.add_parser('test', help='Generate a super resolution image from a trained model.')
     test.add_argument('image', type=str)
     test.add_argument('--model', type=str, default=MODEL, choices=MODELS.keys())
