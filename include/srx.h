@@ -70,8 +70,11 @@ int srx_occupy_cus(int k, int whole_cu, const int* stop_flag, int max_ms, void* 
  * reference counterpart).  Between start and stop every conv kernel is dispatched with its own start /
  * stop HIP events on its stream (hipExtLaunchKernelGGL) -- the main kernel only, not its fix-up / reduce
  * companion.  Not to be used inside a hipGraph capture.  srx_prof_stop returns the number of records; srx_prof_get
- * (after stop) synchronises on record i and returns its kernel name, duration and FLOPs. */
+ * (after stop) synchronises on record i and returns its kernel name, duration and FLOPs.
+ * srx_prof_start_aux: the same, and the slab reductions behind the weight-gradient kernels (wgrad_reduce_rows_kernel,
+ * wgrad_reduce_kernel) get records of their own, 0 FLOPs each: what a test needs that accounts for every launch of a step. */
 int srx_prof_start(int max_launches);
+int srx_prof_start_aux(int max_launches);
 int srx_prof_stop(void);
 int srx_prof_get(int i, char* name, size_t n, float* ms, double* flops);
 

@@ -59,14 +59,210 @@ for _id, _hw, _ci, _co in _VGG:
 STEP_CONVS.append(dict(id='v28.stack', stack=(16, 6, 6, 512, 512), kernels=('wino_kernel<32> MxNxK=576x512x4608',)))
 
 
-def prof_launches(fn, buf_len=160):
+# ---------------------------------------------------------------------------------------------------------------------------
+# The conv problems of the batch-16 ESRGAN GAN step (BASELINE configs[3]: 23 RRDBs, 128 x 128 crops; bf16 products in the
+# quoted configuration, exact fp32 with --disable-amp), read off the model code and one eager step per precision under
+# prof_launches.  Row format of STEP_CONVS plus: up (nearest x2 upsampling in the conv's gather; shape holds the INPUT size),
+# fold_out (the step hands this layer's activation backward to its consumer: ActFold, act_bwd_folded), precisions (in which
+# precision the step makes the call); kernels: launch-name prefixes per precision, filled in from _EK below the table.  exact: outputs the bf16 step computes in
+# exact fp32 (the layers with a 3-channel side: oracle.srgan._ConvBF16, thin_in / thin_out).
+def _ecase(id_, shape, precisions=('fp32', 'bf16'), **kw):
+    return dict(id=id_, shape=shape, precisions=precisions, **kw)
+
+
+_ED = [  # discriminator conv + BatchNorm layers: id, input H = W, Cin, Cout, stride
+    ('d2', 128, 64, 64, 2), ('d5', 64, 64, 128, 1), ('d8', 64, 128, 128, 2), ('d11', 32, 128, 256, 1), ('d14', 32, 256, 256, 2),
+    ('d17', 16, 256, 512, 1), ('d20', 16, 512, 512, 2), ('d23', 8, 512, 512, 1), ('d26', 8, 512, 512, 2)]
+_EVGG = [  # VGG19 features[:36] at 128 x 128, every distinct shape behind the first layer: id, H = W, Cin, Cout
+    ('v2', 128, 64, 64), ('v5', 64, 64, 128), ('v7', 64, 128, 128), ('v10', 32, 128, 256), ('v12', 32, 256, 256),
+    ('v19', 16, 256, 512), ('v21', 16, 512, 512), ('v28', 8, 512, 512)]
+
+_LR = dict(act=ACT_LRELU, slope=0.2)
+ESRGAN_STEP_CONVS = [
+    # generator (esrgan/generator.py): 3 -> 64 on the 32 x 32 crops, the trunk's tail, two nearest-x2 gather convs, 64 -> 3
+    _ecase('g.conv1', (16, 32, 32, 3, 64, 3, 1, 1), bias=True, dx=False, exact=('dx', 'dW')),
+    _ecase('g.conv2', (16, 32, 32, 64, 64, 3, 1, 1), bias=True),
+    _ecase('g.up1', (16, 32, 32, 64, 64, 3, 1, 1), bias=True, up=2, **_LR),
+    _ecase('g.up2', (16, 64, 64, 64, 64, 3, 1, 1), bias=True, up=2, fold_out=True, **_LR),
+    _ecase('g.conv3', (16, 128, 128, 64, 64, 3, 1, 1), bias=True, in_act='lrelu', **_LR),
+    _ecase('g.conv4', (16, 128, 128, 64, 3, 3, 1, 1), bias=True, exact=('y', 'dW')),
+]
+# the dense blocks (functional._RRDBTrunk, 16 x 32 x 32 pixels, 64 + 4 x 32 channels in 192-strided buffers).  Exact fp32: one
+# launch per conv forward and per data gradient (dense: conv k + 1 with the trunk's descriptors and epilogues); bf16: the fused
+# block kernels (CONV_LAUNCHES_TESTED_ELSEWHERE).  Both: the weight gradients as the trunk queues them -- conv1 + conv2 and
+# conv3 + conv4 as pairs, conv5 with the block's scale -- reading 64 / 96, 128 / 160 and 192 channels, bias gradients riding along.
+for _k in range(5):
+    ESRGAN_STEP_CONVS.append(dict(id=f'g.rdb.conv{_k + 1}', dense=_k, nhw=(16, 32, 32), precisions=('fp32',)))
+for _lo in (0, 2):
+    ESRGAN_STEP_CONVS.append(dict(id=f'g.rdb.w{_lo + 1}{_lo + 2}', pair=_lo, nhw=(16, 32, 32), precisions=('fp32', 'bf16')))
+ESRGAN_STEP_CONVS.append(dict(id='g.rdb.w5', scaled=True, nhw=(16, 32, 32), precisions=('fp32', 'bf16')))
+# discriminator (esrgan/discriminator.py, 128 x 128 crops): the pair pass on real + fake (N = 32, weight gradients), the
+# adversarial pass on the fakes (N = 16, data gradients only).  The first layer's LeakyReLU backward rides in d2's data gradient.
+ESRGAN_STEP_CONVS += [
+    _ecase('d0.pair', (32, 128, 128, 3, 64, 3, 1, 1), bias=True, fold_out=True, dx=False,
+           exact=('dx', 'dW'), **_LR),
+    _ecase('d0.adv', (16, 128, 128, 3, 64, 3, 1, 1), bias=True, fold_out=True, dw=False,
+           exact=('dx', 'dW'), **_LR),
+]
+for _id, _hw, _ci, _co, _s in _ED:
+    for _tag, _n, _dw in (('pair', 32, True), ('adv', 16, False)):
+        ESRGAN_STEP_CONVS.append(_ecase(f'{_id}.{_tag}', (_n, _hw, _hw, _ci, _co, 3, _s, 1), stats=True, in_act='lrelu' if _id == 'd2' else None, dw=_dw))
+# VGG19 features[:36] (srgan/loss.py): source + target forward at N = 32, the source's data gradient at N = 16.  Exact fp32:
+# layer by layer as in STEP_CONVS; bf16: the frozen stack keeps its inner activations as bf16 (functional._FrozenConvStack.
+# _forward_bf16s) -- bf16s = (H = W, Cin, Cout), out16: the forms of the forward output at this shape (0: fp32, in front of a
+# pool and at the end; 1: bf16), dx16: the data gradient's (fp32 only for the layer behind the 3 -> 64 one), masked: the layer's
+# input is a conv's ReLU output whose backward the data gradient applies (behind a pool the pool's backward has it)
+ESRGAN_STEP_CONVS += [
+    _ecase('v0.n32', (32, 128, 128, 3, 64, 3, 1, 1), precisions=('fp32',), bias=True, act=ACT_RELU, dx=False, dw=False),
+    _ecase('v0.n16', (16, 128, 128, 3, 64, 3, 1, 1), precisions=('fp32',), bias=True, act=ACT_RELU, dw=False),
+    dict(id='v0.stack', first3=128, precisions=('bf16',)),
+]
+for _id, _hw, _ci, _co in _EVGG:
+    ESRGAN_STEP_CONVS.append(_ecase(f'{_id}.n32', (32, _hw, _hw, _ci, _co, 3, 1, 1), precisions=('fp32',), bias=True, act=ACT_RELU,
+                                    in_act='relu', dx=False, dw=False))
+    ESRGAN_STEP_CONVS.append(_ecase(f'{_id}.n16', (16, _hw, _hw, _ci, _co, 3, 1, 1), precisions=('fp32',), bias=True, act=ACT_RELU,
+                                    in_act='relu', dw=False))
+    # (v2, v7: in front of a pool; v12, v21, v28: three or four layers of the shape, the last one in front of a pool / the end)
+    ESRGAN_STEP_CONVS.append(dict(id=f'{_id}.stack', bf16s=(_hw, _ci, _co), out16={'v2': (0,), 'v7': (0,), 'v5': (1,), 'v10': (1,), 'v19': (1,)}.get(_id, (1, 0)),
+                                  dx16=0 if _id == 'v2' else 1, masked=_id not in ('v5', 'v10', 'v19'), precisions=('bf16',)))
+
+# per row and precision: the launches (kernel, template arguments) the row must produce, read off a run on an MI355X
+_EK = {'g.conv1': {'fp32': ('first3x3_fwd_kernel<0>', 'thin_wgrad_kernel<3, 3, 1, 1>'),
+             'bf16': ('first3x3_fwd_kernel<1>', 'thin_wgrad_kernel<3, 3, 1, 1>')},
+ 'g.conv2': {'fp32': ('wgrad_dma_kernel<1, 1>', 'wgrad_reduce_rows_kernel', 'wino_kernel<32>'),
+             'bf16': ('gconv_kernel<64, 64, 32, 32, 2, 0, 1>', 'wgrad_reduce_rows_kernel', 'wgrad_rows_bf16_kernel<32>')},
+ 'g.up1': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'wgrad_dma_kernel<1, 1>', 'wgrad_reduce_rows_kernel'),
+           'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'wgrad_kernel<1>', 'wgrad_reduce_rows_kernel')},
+ 'g.up2': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'wgrad_dma_kernel<1, 1>', 'wgrad_reduce_rows_kernel'),
+           'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'wgrad_kernel<1>', 'wgrad_reduce_rows_kernel')},
+ 'g.conv3': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'wgrad_dma_kernel<1, 1>', 'wgrad_reduce_rows_kernel'),
+             'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'wgrad_kernel<1>', 'wgrad_reduce_rows_kernel')},
+ 'g.conv4': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'thin_fwd2_kernel<3, 3>', 'thin_wgrad_kernel<3, 3, 1, -1>'),
+             'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'thin_fwd2_kernel<3, 3>', 'thin_wgrad_kernel<3, 3, 1, -1>')},
+ 'g.rdb.conv1': {'fp32': ('gconv_kernel<64, 32, 32, 32, 2, 0, 0>', 'gconv_kernel<64, 64, 32, 32, 2, 0, 0>')},
+ 'g.rdb.conv2': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'gconv_kernel<64, 32, 32, 32, 2, 0, 0>')},
+ 'g.rdb.conv3': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'gconv_kernel<64, 32, 32, 32, 2, 0, 0>')},
+ 'g.rdb.conv4': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'gconv_kernel<64, 32, 32, 32, 2, 0, 0>')},
+ 'g.rdb.conv5': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>',)},
+ 'g.rdb.w12': {'fp32': ('wgrad_dma_kernel<0, 0>', 'wgrad_reduce_rows_kernel'),
+               'bf16': ('wgrad_reduce_rows_kernel', 'wgrad_rows_bf16_kernel<32>')},
+ 'g.rdb.w34': {'fp32': ('wgrad_dma_kernel<0, 0>', 'wgrad_reduce_rows_kernel'),
+               'bf16': ('wgrad_reduce_rows_kernel', 'wgrad_rows_bf16_kernel<32>')},
+ 'g.rdb.w5': {'fp32': ('wgrad_dma_kernel<1, 1>', 'wgrad_reduce_rows_kernel'),
+              'bf16': ('wgrad_reduce_rows_kernel', 'wgrad_rows_bf16_kernel<32>')},
+ 'd0.pair': {'fp32': ('first3x3_fwd_kernel<0>', 'thin_wgrad_kernel<3, 3, 1, 1>'),
+             'bf16': ('first3x3_fwd_kernel<1>', 'thin_wgrad_kernel<3, 3, 1, 1>')},
+ 'd0.adv': {'fp32': ('first3x3_fwd_kernel<0>', 'thin_fwd2_kernel<3, 3>'),
+            'bf16': ('first3x3_fwd_kernel<1>', 'thin_fwd2_kernel<3, 3>')},
+ 'd2.pair': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'gconv_s2f_kernel<128, 64, 32, 32, 0, 0>',
+                      'wgrad_dma_kernel<1, 0>', 'wgrad_reduce_rows_kernel'),
+             'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'gconv_s2f_kernel<128, 64, 32, 32, 0, 1>', 'wgrad_kernel<1>',
+                      'wgrad_reduce_rows_kernel')},
+ 'd2.adv': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'gconv_s2f_kernel<128, 64, 32, 32, 0, 0>'),
+            'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'gconv_s2f_kernel<128, 64, 32, 32, 0, 1>')},
+ 'd5.pair': {'fp32': ('wgrad_dma_kernel<1, 1>', 'wgrad_reduce_rows_kernel', 'wino_kernel<64>'),
+             'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'gconv_kernel<256, 128, 64, 64, 1, 0, 1>', 'wgrad_kernel<1>',
+                      'wgrad_reduce_rows_kernel')},
+ 'd5.adv': {'fp32': ('wino_kernel<64>',),
+            'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'gconv_kernel<256, 128, 64, 64, 1, 0, 1>')},
+ 'd8.pair': {'fp32': ('gconv_kernel<128, 128, 64, 32, 1, 0, 0>', 'gconv_multi_kernel<128, 128, 64, 32, 0, 0, 1>',
+                      'wgrad_dma_kernel<1, 0>', 'wgrad_reduce_rows_kernel'),
+             'bf16': ('gconv_kernel<128, 128, 64, 32, 1, 0, 1>', 'gconv_multi_kernel<128, 128, 64, 32, 0, 1, 1>',
+                      'wgrad_kernel<1>', 'wgrad_reduce_rows_kernel')},
+ 'd8.adv': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'gconv_multi_kernel<128, 128, 64, 32, 0, 0, 1>'),
+            'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'gconv_multi_kernel<128, 128, 64, 32, 0, 1, 1>')},
+ 'd11.pair': {'fp32': ('wgrad_dma_kernel<1, 1>', 'wgrad_reduce_rows_kernel', 'wino_kernel<64>'),
+              'bf16': ('gconv_kernel<128, 128, 64, 32, 1, 0, 1>', 'gconv_kernel<256, 128, 64, 64, 1, 0, 1>', 'wgrad_kernel<1>',
+                       'wgrad_reduce_rows_kernel')},
+ 'd11.adv': {'fp32': ('wino_kernel<64>',),
+             'bf16': ('gconv_kernel<128, 128, 64, 32, 1, 0, 1>', 'gconv_kernel<128, 64, 32, 32, 1, 0, 1>')},
+ 'd14.pair': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'gconv_multi_kernel<128, 128, 64, 32, 0, 0, 1>',
+                       'wgrad_dma_kernel<1, 0>', 'wgrad_reduce_rows_kernel'),
+              'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'gconv_multi_kernel<128, 128, 64, 32, 0, 1, 1>',
+                       'wgrad_kernel<1>', 'wgrad_reduce_rows_kernel')},
+ 'd14.adv': {'fp32': ('gconv_kernel<128, 128, 64, 32, 1, 0, 0>', 'gconv_multi_kernel<128, 64, 32, 32, 0, 0, 1>'),
+             'bf16': ('gconv_kernel<64, 64, 32, 32, 2, 0, 1>', 'gconv_multi_kernel<128, 64, 32, 32, 0, 1, 1>')},
+ 'd17.pair': {'fp32': ('wgrad_dma_kernel<1, 1>', 'wgrad_reduce_rows_kernel', 'wino_kernel<64>'),
+              'bf16': ('gconv_kernel<128, 128, 64, 32, 1, 0, 1>', 'gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'wgrad_kernel<1>',
+                       'wgrad_reduce_rows_kernel')},
+ 'd17.adv': {'fp32': ('wino_kernel<32>', 'wino_kernel<64>'), 'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>',)},
+ 'd20.pair': {'fp32': ('gconv_kernel<128, 128, 64, 32, 1, 0, 0>', 'gconv_multi_kernel<64, 64, 32, 32, 0, 0, 2>',
+                       'wgrad_dma_kernel<1, 0>', 'wgrad_reduce_rows_kernel'),
+              'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'gconv_multi_kernel<128, 64, 32, 32, 0, 1, 1>',
+                       'wgrad_kernel<1>', 'wgrad_reduce_rows_kernel')},
+ 'd20.adv': {'fp32': ('gconv_kernel<128, 128, 64, 32, 1, 0, 0>', 'gconv_multi_kernel<64, 64, 32, 32, 0, 0, 2>'),
+             'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'gconv_multi_kernel<64, 64, 32, 32, 0, 1, 2>')},
+ 'd23.pair': {'fp32': ('wgrad_dma_kernel<1, 1>', 'wgrad_reduce_rows_kernel', 'wino_kernel<32>'),
+              'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'wgrad_kernel<1>', 'wgrad_reduce_rows_kernel')},
+ 'd23.adv': {'fp32': ('wino_kernel<32>', 'wino_kernel<64>'), 'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>',)},
+ 'd26.pair': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'gconv_multi_kernel<64, 64, 32, 32, 0, 0, 2>',
+                       'wgrad_dma_kernel<1, 0>', 'wgrad_reduce_rows_kernel'),
+              'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 1>', 'gconv_multi_kernel<64, 64, 32, 32, 0, 1, 2>',
+                       'wgrad_kernel<1>', 'wgrad_reduce_rows_kernel')},
+ 'd26.adv': {'fp32': ('gconv_kernel<128, 64, 32, 32, 1, 0, 0>', 'gconv_multi_kernel<64, 64, 32, 32, 0, 0, 2>'),
+             'bf16': ('gconv_kernel<64, 64, 32, 32, 2, 0, 1>', 'gconv_multi_kernel<64, 64, 32, 32, 0, 1, 2>')},
+ 'v0.n32': {'fp32': ('first3x3_fwd_kernel<0>',)},
+ 'v0.n16': {'fp32': ('first3x3_fwd_kernel<0>', 'thin_fwd2_kernel<3, 3>')},
+ 'v0.stack': {'bf16': ('first3x3_fwd_kernel<1>', 'thin_fwd2_kernel<3, 3>')},
+ 'v2.n32': {'fp32': ('wino_kernel<64>',)},
+ 'v2.n16': {'fp32': ('wino_kernel<64>',)},
+ 'v2.stack': {'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 2>',)},
+ 'v5.n32': {'fp32': ('wino_kernel<64>',)},
+ 'v5.n16': {'fp32': ('wino_kernel<64>',)},
+ 'v5.stack': {'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 2>', 'gconv_kernel<256, 128, 64, 64, 1, 0, 2>')},
+ 'v7.n32': {'fp32': ('wino_kernel<64>',)},
+ 'v7.n16': {'fp32': ('wino_kernel<64>',)},
+ 'v7.stack': {'bf16': ('gconv_kernel<256, 128, 64, 64, 1, 0, 2>',)},
+ 'v10.n32': {'fp32': ('wino_kernel<64>',)},
+ 'v10.n16': {'fp32': ('wino_kernel<64>',)},
+ 'v10.stack': {'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 2>', 'gconv_kernel<256, 128, 64, 64, 1, 0, 2>')},
+ 'v12.n32': {'fp32': ('wino_kernel<64>',)},
+ 'v12.n16': {'fp32': ('wino_kernel<64>',)},
+ 'v12.stack': {'bf16': ('gconv_kernel<128, 128, 64, 32, 1, 0, 2>', 'gconv_kernel<256, 128, 64, 64, 1, 0, 2>')},
+ 'v19.n32': {'fp32': ('wino_kernel<64>',)},
+ 'v19.n16': {'fp32': ('wino_kernel<32>', 'wino_kernel<64>')},
+ 'v19.stack': {'bf16': ('gconv_kernel<128, 128, 64, 32, 1, 0, 2>', 'gconv_kernel<64, 64, 32, 32, 2, 0, 2>')},
+ 'v21.n32': {'fp32': ('wino_kernel<64>',)},
+ 'v21.n16': {'fp32': ('wino_kernel<64>',)},
+ 'v21.stack': {'bf16': ('gconv_kernel<128, 128, 64, 32, 1, 0, 2>', 'gconv_kernel<128, 64, 32, 32, 1, 0, 2>')},
+ 'v28.n32': {'fp32': ('wino_kernel<32>',)},
+ 'v28.n16': {'fp32': ('wino_kernel<64>',)},
+ 'v28.stack': {'bf16': ('gconv_kernel<128, 64, 32, 32, 1, 0, 2>', 'gconv_kernel<64, 64, 32, 32, 2, 0, 2>')}}
+for _c in ESRGAN_STEP_CONVS:
+    _c['kernels'] = {_p: _EK[_c['id']][_p] for _p in _c['precisions']}
+
+# Conv-family launches of the ESRGAN step that have no row: the fused dense block (bf16) and the pack launches, and the tests that
+# hold them at 16 x 32 x 32
+CONV_LAUNCHES_TESTED_ELSEWHERE = {
+    'rdb_kernel<0>': 'test_ops_gpu.py::test_fused_dense_block_forward[16-32-32]',
+    'rdb_kernel<1>': 'test_ops_gpu.py::test_fused_dense_block_backward[16-32-32]',
+    'rdb_pack_kernel': 'test_ops_gpu.py::test_fused_dense_block_forward[16-32-32]',
+    'pack_table_kernel': 'test_step_gpu.py::test_pack_tables_take_over_after_the_first_step',
+}
+
+
+def esrgan_case_shapes(case):
+    """The (N, H, W, Cin, Cout, k, stride, pad, up) problems of one ESRGAN_STEP_CONVS row (H, W: the conv's input size)."""
+    if 'shape' in case:
+        return {tuple(case['shape']) + (case.get('up', 0),)}
+    if 'bf16s' in case:
+        hw, cin, cout = case['bf16s']
+        return {(n, hw, hw, cin, cout, 3, 1, 1, 0) for n in (32, 16)}
+    if 'first3' in case:
+        return {(n, case['first3'], case['first3'], 3, 64, 3, 1, 1, 0) for n in (32, 16)}
+    n, h, w = case['nhw']
+    ks = (case['dense'],) if 'dense' in case else (case['pair'], case['pair'] + 1) if 'pair' in case else (4,)
+    return {(n, h, w, 64 + 32 * k, 64 if k == 4 else 32, 3, 1, 1, 0) for k in ks}
+
+
+def prof_launches(fn, buf_len=160, aux=False):
     """Run ``fn`` with the library's per-launch records on (srx_prof_*); the names of the conv kernels it launched, with the
-    template arguments and, where the name carries it, ' MxNxK=..'."""
+    template arguments and, where the name carries it, ' MxNxK=..'.  ``aux``: the weight gradients' slab reductions too."""
     import ctypes as C
     import torch
     from torchsr_amd import _lib
     torch.cuda.synchronize()
-    _lib.call('srx_prof_start', 8192)
+    _lib.call('srx_prof_start_aux' if aux else 'srx_prof_start', 8192)
     try:
         fn()
         torch.cuda.synchronize()
@@ -79,6 +275,57 @@ def prof_launches(fn, buf_len=160):
         names.append(buf.value.decode())
     return names
 
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The float64 reference of one conv product and its elementwise bound (test_step_layers_gpu.py, test_esrgan_layers_gpu.py; the
+# bound's own check without a GPU: test_cpu.py).
+U32 = 2.0 ** -24   # unit roundoff of a round-to-nearest fp32 accumulation
+
+
+def gamma(k, u=U32):
+    """gamma_k = k u / (1 - k u): the worst relative error of a k-term sum in any order, every addition rounded with unit u."""
+    return k * u / (1.0 - k * u)
+
+
+def bf16_round(t):
+    import torch
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+def conv_refs(what, a, b, x_shape, w_shape, stride, pad, up=0, bias=None, rounded=False, u=U32):
+    """One product of the layer ``x_shape`` (N, Cin, H, W: the conv's input BEFORE the nearest x2 upsampling ``up = 2`` fuses
+    into its gather) * ``w_shape`` (Cout, Cin, k, k): ``what`` = 'y' (a = x, b = W, + the fp32 bias), 'dx' (a = dy, b = W) or 'dW'
+    (a = x, b = dy), three ways: (float64 value, torch fp32 value, the elementwise bound gamma_K (|a| conv |b|), K the reduction
+    length).  ``rounded``: bf16 products -- BOTH factors are rounded to bf16 first (test_conv2d_bf16_products,
+    oracle.srgan.bf16_products(exact_sums=True)); a bf16 x bf16 product is exact in fp32, so the float64 value differs from the
+    kernel's by the K-term fp32 accumulation alone and the same bound holds, on the rounded operands."""
+    import torch
+    import torch.nn.functional as TF
+    if rounded:
+        a, b = bf16_round(a), bf16_round(b)
+    cout, cin, k, _ = w_shape
+    ups = (lambda t: TF.interpolate(t, scale_factor=2, mode='nearest')) if up == 2 else (lambda t: t)
+    n, _, h, w = x_shape
+    in_shape = (n, cin, 2 * h, 2 * w) if up == 2 else tuple(x_shape)
+    if what == 'y':
+        def f(x, wt, bb):
+            return TF.conv2d(ups(x), wt, bb, stride, pad)
+        kk = cin * k * k + (1 if bias is not None else 0)
+        bd = None if bias is None else bias.double()
+        return f(a.double(), b.double(), bd), f(a, b, bias), gamma(kk, u) * f(a.double().abs(), b.double().abs(), None if bd is None else bd.abs())
+    if what == 'dx':
+        def f(dy, wt):  # the adjoint of the gather: the gradient of the upsampled tensor summed over each 2 x 2 block
+            d = torch.nn.grad.conv2d_input(in_shape, wt, dy, stride, pad)
+            return 4.0 * TF.avg_pool2d(d, 2) if up == 2 else d
+        kk = cout * k * k * (4 if up == 2 else 1) + 1
+        return f(a.double(), b.double()), f(a, b), gamma(kk, u) * f(a.double().abs(), b.double().abs())
+    if what == 'dW':
+        def f(x, dy):
+            return torch.nn.grad.conv2d_weight(ups(x), tuple(w_shape), dy, stride, pad)
+        m = b[:, 0].numel()
+        return f(a.double(), b.double()), f(a, b), gamma(m, u) * f(a.double().abs(), b.double().abs())
+    raise KeyError(what)
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # The non-convolution launches of the steps: BatchNorm, losses, pools, activations' backward, layout, Adam (norm.hip, loss.hip,

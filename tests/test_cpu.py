@@ -784,3 +784,102 @@ def test_abi_refuses_bad_batchnorm_groups_and_channels_without_a_gpu():
     # the row-block regimes the tests' bounds and the group check rest on
     assert [lib.srx_bn_rows_per_block(m) for m in (1, 32767, 32768, 131071, 131072, 1 << 22)] == [32, 32, 128, 128, 512, 512]
     assert lib.srx_bn_stat_rows(32767) == 1024 and lib.srx_bn_stat_rows(32768) == 256 and lib.srx_bn_stat_rows(131072) == 256
+
+
+# ------------------------------------------------------------------ the ESRGAN step's conv table (test_esrgan_layers_gpu.py)
+def test_esrgan_step_conv_table_holds_the_models_geometry():
+    """Generator (16 x 32 x 32 crops), Discriminator(128) and the VGG19 features (16 and 32 crops of 128 x 128) walked layer by
+    layer through ``ConvState.out_shape``: every distinct conv problem is the shape of a row of ESRGAN_STEP_CONVS, and no row has
+    a shape the models do not produce."""
+    from step_layers import ESRGAN_STEP_CONVS, esrgan_case_shapes
+    from torchsr_amd.esrgan.discriminator import Discriminator
+    from torchsr_amd.esrgan.generator import Generator
+    from torchsr_amd.esrgan.loss import make_vgg19_features
+    from torchsr_amd.layers import Conv2d
+    seen = set()
+
+    def through(conv, shape):
+        n, h, w, c = shape
+        st = conv._st
+        assert c == st.cin_s, (shape, st.cin)
+        seen.add((n, h, w, st.cin, st.cout, st.k, st.stride, st.pad, st.up))
+        return st.out_shape(n, h, w)
+
+    gen = Generator()
+    trunk_in = through(gen.conv1, (16, 32, 32, 4))
+    for rrdb in gen.blocks:
+        for rdb in (rrdb.RDB1, rrdb.RDB2, rrdb.RDB3):
+            for k, conv in enumerate((rdb.conv1[0], rdb.conv2[0], rdb.conv3[0], rdb.conv4[0], rdb.conv5)):
+                out = through(conv, trunk_in[:3] + (64 + 32 * k,))   # (its first channels of the block's 192-wide buffer)
+                assert out[:3] == trunk_in[:3] and out[3] == (64 if k == 4 else 32)
+    shape = trunk_in
+    for conv in (gen.conv2, gen.upsample1, gen.upsample2, gen.conv3[0], gen.conv4):
+        shape = through(conv, shape)
+    assert shape == (16, 128, 128, 4)
+    for n in (32, 16):   # the pair pass on real + fake, the adversarial pass; source + target, the source's gradient
+        shape = (n, 128, 128, 4)
+        for m in Discriminator(128).features:
+            if isinstance(m, Conv2d):
+                shape = through(m, shape)
+        assert shape == (n, 4, 4, 512)
+        shape = (n, 128, 128, 4)
+        for m in make_vgg19_features(36):
+            if isinstance(m, Conv2d):
+                shape = through(m, shape)
+            elif type(m).__name__ == 'MaxPool2x2':
+                shape = (shape[0], shape[1] // 2, shape[2] // 2, shape[3])
+        assert shape == (n, 8, 8, 512)
+    rows = set()
+    for case in ESRGAN_STEP_CONVS:
+        assert case['precisions'] and set(case['precisions']) <= {'fp32', 'bf16'} and set(case['kernels']) == set(case['precisions']), case['id']
+        assert all(case['kernels'][p] for p in case['precisions']), case['id']   # every row names the form it is there to test
+        rows |= esrgan_case_shapes(case)
+    assert not seen - rows, sorted(seen - rows)
+    assert not rows - seen, sorted(rows - seen)
+    for precision in ('fp32', 'bf16'):   # ... and each precision's rows hold every shape
+        have = set().union(*[esrgan_case_shapes(c) for c in ESRGAN_STEP_CONVS if precision in c['precisions']])
+        assert have == seen, (precision, sorted(seen - have))
+    assert len({c['id'] for c in ESRGAN_STEP_CONVS}) == len(ESRGAN_STEP_CONVS)
+
+
+@pytest.mark.parametrize('cfg', [(2, 9, 7, 3, 64, 1, 0, 3), (2, 9, 7, 64, 32, 2, 0, 64), (1, 6, 5, 64, 16, 1, 2, 64), (2, 8, 8, 96, 32, 1, 0, 192)],
+                         ids=['cin3', 'stride2', 'up2', 'cin96of192'])
+def test_bf16_conv_reference_bound_separates_right_from_wrong(cfg):
+    """``step_layers.conv_refs`` before it judges a kernel: a plain fp32 torch convolution of the bf16-rounded operands lies
+    inside the elementwise bound gamma_K (|r(a)| conv |r(b)|) around the float64 value and inside the statistical budget
+    (F = 1.5 of its own distance), for the forward, the data gradient and the weight gradient -- and a result with one tap or
+    one input channel dropped lies outside the bound."""
+    from step_layers import bf16_round, conv_refs
+    n, h, w, cin, cout, stride, up, width = cfg
+    g = torch.Generator().manual_seed(cin * 7 + stride + up)
+    buf = torch.nn.functional.leaky_relu(torch.randn((n, width, h, w), generator=g), 0.2)
+    x = buf[:, :cin]                                    # (96 of 192: a dense block's conv reads the head of a wider buffer)
+    wt = torch.randn((cout, cin, 3, 3), generator=g) * (2.0 / (cin * 9)) ** 0.5
+    b = torch.randn((cout,), generator=g) * 0.1
+    y64, y32, by = conv_refs('y', x, wt, x.shape, wt.shape, stride, 1, up, b, rounded=True)
+    dy = torch.randn(y64.shape, generator=g)
+    w_cut = wt.clone()
+    w_cut[:, :, 1, 2] = 0.0                             # one tap dropped
+    x_cut = x.clone()
+    x_cut[:, cin // 2] = 0.0                            # one input channel dropped
+    wrong = {'y': conv_refs('y', x, w_cut, x.shape, wt.shape, stride, 1, up, b, rounded=True)[1],
+             'dx': conv_refs('dx', dy, w_cut, x.shape, wt.shape, stride, 1, up, None, rounded=True)[1],
+             'dW': conv_refs('dW', x_cut, dy, x.shape, wt.shape, stride, 1, up, None, rounded=True)[1]}
+    also_wrong = conv_refs('y', x_cut, wt, x.shape, wt.shape, stride, 1, up, b, rounded=True)[1]
+    for what, a, bb, bias in (('y', x, wt, b), ('dx', dy, wt, None), ('dW', x, dy, None)):
+        r64, r32, bound = conv_refs(what, a, bb, x.shape, wt.shape, stride, 1, up, bias, rounded=True)
+        assert r64.dtype == torch.float64 and r32.dtype == torch.float32 and r64.shape == r32.shape == bound.shape
+        expect = {'y': y64.shape, 'dx': x.shape, 'dW': wt.shape}[what]
+        assert tuple(r64.shape) == tuple(expect), what
+        # the float64 value is the convolution of the ROUNDED operands, not of the operands
+        plain = conv_refs(what, a, bb, x.shape, wt.shape, stride, 1, up, bias, rounded=False)[0]
+        assert torch.equal(r64, conv_refs(what, bf16_round(a), bf16_round(bb), x.shape, wt.shape, stride, 1, up, bias)[0])
+        assert ((plain - r64).abs() > bound).any(), what
+        err = (r32.double() - r64).abs()
+        assert (err <= bound).all(), (what, (err / bound.clamp_min(1e-300)).max().item())
+        dist = ((r32.double() - r64).norm() / r64.norm()).item()
+        assert dist <= 1.5 * dist + 1e-7 and dist < 1e-6, (what, dist)
+        bad = (wrong[what].double() - r64).abs()
+        assert (bad > bound).any(), what
+        assert (bad > bound).double().mean().item() > 0.01, what   # (not one element: the whole tap / channel is missing)
+    assert ((also_wrong.double() - y64).abs() > by).any()

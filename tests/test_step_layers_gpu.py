@@ -24,7 +24,7 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-from step_layers import STEP_CONVS, prof_launches
+from step_layers import STEP_CONVS, conv_refs, gamma, prof_launches
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
@@ -45,19 +45,15 @@ class FormOverBudget(AssertionError):
     """A form's distance from fp64 is above F x torch fp32's (and within its pin): the open finding OVER_F records."""
 
 
-def gamma(k):
-    return k * U / (1.0 - k * U)
-
-
 def rel_l2(a, ref):
     return ((a - ref).norm() / ref.norm().clamp_min(1e-300)).item()
 
 
-def prof_keys(fn):
+def prof_keys(fn, aux=False):
     """The conv launches fn made as 'name MxNxK=..' keys (the problem count of a grouped weight-gradient launch dropped: the
     step groups 33 equal problems, a table case one)."""
     keys = []
-    for name in prof_launches(fn):
+    for name in prof_launches(fn, aux=aux):
         if ' MxNxK=' in name and name.rsplit(' ', 1)[-1].startswith('x'):
             name = name.rsplit(' ', 1)[0]
         keys.append(name)
@@ -96,44 +92,57 @@ def check(what, got, ref64, ref32, bound, wino, report):
         assert err.max().item() <= 2e-5 * ref64.abs().max().item(), (what, err.max().item(), ref64.abs().max().item())
     else:
         worst = (err - bound).max().item()
+        print(f'  {what:44s} max err/bound {(err / bound.clamp_min(1e-300)).max().item():.3f}')
         assert worst <= 0.0, (what, worst, err.max().item())
 
 
-def run_conv_case(case, dev, report):
-    """One layer of the step: forward (+ statistics), data gradient, weight (+ bias) gradient where the step takes them."""
+def run_conv_case(case, dev, report, precision='fp32', u=U, prefill=0.0):
+    """One layer of the step: forward (+ statistics), data gradient, weight (+ bias) gradient where the step takes them.
+    ``precision`` 'bf16': the layer multiplies bf16-rounded operands (``set_conv_precision``) and every output not listed in the
+    case's ``exact`` is held to float64 of the ROUNDED operands (``step_layers.conv_refs``), with unit roundoff ``u`` in the
+    bound.  ``prefill``: scale of the values the ``.grad`` buffers hold before the backward pass accumulates into them."""
     from torchsr_amd import functional as F
-    from torchsr_amd.layers import Conv2d
+    from torchsr_amd.layers import Conv2d, set_conv_precision
     n, h, w, cin, cout, k, s, p = case['shape']
     act, slope, shuffle, bias = case.get('act', 0), case.get('slope', 0.0), case.get('shuffle', 0), case.get('bias', False)
     stats, in_act, dx_on, dw_on = case.get('stats', False), case.get('in_act'), case.get('dx', True), case.get('dw', True)
+    up, fold_out = case.get('up', 0), case.get('fold_out', False)
+    rounded = {o: precision == 'bf16' and o not in case.get('exact', ()) for o in ('y', 'dx', 'dW')}
     g = torch.Generator().manual_seed(zlib.crc32(case['id'].encode()))
     x = torch.randn((n, cin, h, w), generator=g)
     x = torch.relu(x) if in_act == 'relu' else TF.leaky_relu(x, 0.2)  # post-activation inputs
     wt = torch.randn((cout, cin, k, k), generator=g) * (2.0 / (cin * k * k)) ** 0.5  # Kaiming
     b = torch.randn((cout,), generator=g) * 0.1 if bias else None
-    conv = Conv2d(cin, cout, k, s, p, bias=bias, act=act, slope=slope, shuffle=shuffle)
+    conv = Conv2d(cin, cout, k, s, p, bias=bias, act=act, slope=slope, shuffle=shuffle, up=up)
     with torch.no_grad():
         conv.weight.copy_(wt)
         if bias:
             conv.bias.copy_(b)
     conv = conv.to(dev)
+    if precision == 'bf16':
+        set_conv_precision(conv, 'bf16')
     cs = conv._st.cin_s
     xg = nhwc(x, cs).to(dev).requires_grad_(dx_on)
     conv.weight.requires_grad_(dw_on)
     if bias:
         conv.bias.requires_grad_(dw_on)
-    if dw_on:  # the trainers' flat .grad views: the kernels accumulate into them
-        conv.weight.grad = torch.zeros_like(conv.weight)
-        if bias:
-            conv.bias.grad = torch.zeros_like(conv.bias)
     token = F.ActFold(1 if in_act == 'relu' else 2, 0.0 if in_act == 'relu' else 0.2) if (in_act and dx_on) else None
+    out_token = F.ActFold(act, slope) if fold_out else None  # the step's consumer applies this layer's activation backward
     was = F.direct_grads[0]
     F.direct_grads[0] = True
     try:
-        out = conv(xg, want_stats=stats, in_act=token)
+        out = conv(xg, want_stats=stats, in_act=token, act_bwd_folded=out_token)
         yg, part = out if stats else (out, None)
         cl = cout // 4 if shuffle else cout
         gy = torch.randn((n, cl) + tuple(nchw(yg, cl).shape[2:]), generator=g)
+        w0 = torch.randn(wt.shape, generator=g) * prefill if prefill else torch.zeros_like(wt)
+        b0 = (torch.randn((cout,), generator=g) * prefill if prefill else torch.zeros(cout)) if bias else None
+        if dw_on:  # the trainers' flat .grad views: the kernels accumulate into them
+            conv.weight.grad = w0.to(dev)
+            if bias:
+                conv.bias.grad = b0.to(dev)
+        if out_token is not None:
+            out_token.masked = True  # (what the consumer's masked data gradient reports)
         if dx_on or dw_on:
             with F.deferred_weight_grads():
                 yg.backward(nhwc(gy, yg.shape[-1]).to(dev))
@@ -143,24 +152,18 @@ def run_conv_case(case, dev, report):
     wino = conv._st.__dict__.get('wino_fwd') is not None
     tag = case['id']
 
-    x64, w64 = x.double(), wt.double()
-    b64 = None if b is None else b.double()
-    pre64 = TF.conv2d(x64, w64, b64, s, p)
-    pre32 = TF.conv2d(x, wt, b, s, p)
+    pre64, pre32, by = conv_refs('y', x, wt, x.shape, wt.shape, s, p, up, b, rounded['y'], u)
     post = lambda t: (torch.relu(t) if act == 1 else TF.leaky_relu(t, slope) if act == 2 else t)  # noqa: E731
     shuf = lambda t: TF.pixel_shuffle(t, 2) if shuffle else t  # noqa: E731
-    kk = cin * k * k + (1 if bias else 0)
-    absconv = TF.conv2d(x64.abs(), w64.abs(), None if b64 is None else b64.abs(), s, p)
     got_y = nchw(yg.detach().cpu(), cl)
-    check(f'{tag} y', got_y, shuf(post(pre64)), shuf(post(pre32)), shuf(gamma(kk) * absconv), wino, report)
+    check(f'{tag} y', got_y, shuf(post(pre64)), shuf(post(pre32)), shuf(by), wino, report)
     if stats:
         m = pre64[:, 0].numel()
         s1 = part[:, :, 0].double().sum(0).cpu()
         s2 = part[:, :, 1].double().sum(0).cpu()
         ref1, ref2 = pre64.sum((0, 2, 3)), pre64.square().sum((0, 2, 3))
-        by = gamma(kk) * absconv
-        lim1 = gamma(m) * pre64.abs().sum((0, 2, 3)) + by.sum((0, 2, 3))
-        lim2 = gamma(m) * ref2 + (2 * pre64.abs() * by + by.square()).sum((0, 2, 3)) * (1 + gamma(m))
+        lim1 = gamma(m, u) * pre64.abs().sum((0, 2, 3)) + by.sum((0, 2, 3))
+        lim2 = gamma(m, u) * ref2 + (2 * pre64.abs() * by + by.square()).sum((0, 2, 3)) * (1 + gamma(m, u))
         if wino:
             lim1, lim2 = 2e-5 * pre64.abs().sum((0, 2, 3)).max(), 2e-5 * ref2.max()
         print(f'  {tag} stats: max |s1-ref| / bound {((s1 - ref1).abs() / lim1).max().item():.3f}, '
@@ -172,32 +175,32 @@ def run_conv_case(case, dev, report):
     # the gradient at the conv's output, the activation's decisions taken from the kernel's output
     g_post = TF.pixel_unshuffle(gy, 2) if shuffle else gy
     y_k = TF.pixel_unshuffle(got_y, 2) if shuffle else got_y
-    if act == 1:
+    if act == 1 and not fold_out:
         g_pre = g_post * (y_k > 0)
-    elif act == 2:
+    elif act == 2 and not fold_out:
         g_pre = torch.where(y_k > 0, g_post, g_post * slope)
     else:
         g_pre = g_post
-    g64 = g_pre.double()
     if dx_on:
-        dx64 = torch.nn.grad.conv2d_input(x.shape, w64, g64, s, p)
-        dx32 = torch.nn.grad.conv2d_input(x.shape, wt, g_pre, s, p)
-        absdx = torch.nn.grad.conv2d_input(x.shape, w64.abs(), g64.abs(), s, p)
+        dx64, dx32, bdx = conv_refs('dx', g_pre, wt, x.shape, wt.shape, s, p, up, None, rounded['dx'], u)
         if in_act:
             mask = (x > 0).double() if in_act == 'relu' else torch.where(x > 0, 1.0, 0.2).double()
-            dx64, dx32, absdx = dx64 * mask, dx32 * mask.float(), absdx * mask
+            dx64, dx32, bdx = dx64 * mask, dx32 * mask.float(), bdx * mask
         got_dx = nchw(xg.grad.cpu(), cin)
         wino_dx = conv._st.__dict__.get('wino_bwd') is not None  # (a forward-only Winograd layer takes the direct data gradient)
-        check(f'{tag} dx', got_dx, dx64, dx32, gamma(cout * k * k + 1) * absdx, wino_dx, report)
+        check(f'{tag} dx', got_dx, dx64, dx32, bdx, wino_dx, report)
     if dw_on:
         m = g_pre[:, 0].numel()
-        dw64 = torch.nn.grad.conv2d_weight(x64, wt.shape, g64, s, p)
-        dw32 = torch.nn.grad.conv2d_weight(x, wt.shape, g_pre, s, p)
-        absdw = torch.nn.grad.conv2d_weight(x64.abs(), wt.shape, g64.abs(), s, p)
-        check(f'{tag} dW', conv.weight.grad.cpu(), dw64, dw32, gamma(m) * absdw, False, report)
-        if bias:
-            check(f'{tag} db', conv.bias.grad.cpu(), g64.sum((0, 2, 3)), g_pre.sum((0, 2, 3)),
-                  gamma(m) * g64.abs().sum((0, 2, 3)), False, report)
+        dw64, dw32, bdw = conv_refs('dW', x, g_pre, x.shape, wt.shape, s, p, up, None, rounded['dW'], u)
+        if prefill:  # one more term per element: the sum lands on what the buffer held
+            dw64, dw32, bdw = dw64 + w0.double(), dw32 + w0, gamma(m + 1, u) * (bdw / gamma(m, u) + w0.double().abs())
+        check(f'{tag} dW', conv.weight.grad.cpu(), dw64, dw32, bdw, False, report)
+        if bias:  # (the bias gradient sums the fp32 output gradient itself: nothing is rounded to bf16)
+            g64 = g_pre.double()
+            db64, db32, bdb = g64.sum((0, 2, 3)), g_pre.sum((0, 2, 3)), gamma(m, u) * g64.abs().sum((0, 2, 3))
+            if prefill:
+                db64, db32, bdb = db64 + b0.double(), db32 + b0, gamma(m + 1, u) * (bdb / gamma(m, u) + b0.double().abs())
+            check(f'{tag} db', conv.bias.grad.cpu(), db64, db32, bdb, False, report)
 
 
 def tower_reference(x, blocks, gy, dtype):

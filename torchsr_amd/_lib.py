@@ -154,6 +154,7 @@ _SIGS = {
     'srx_plan_cus': (_I, []),
     'srx_occupy_cus': (_I, [_I, _I, _P, _I, _P]),
     'srx_prof_start': (_I, [_I]),
+    'srx_prof_start_aux': (_I, [_I]),
     'srx_prof_stop': (_I, []),
     'srx_prof_get': (_I, [_I, C.c_char_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     'srx_nchw_to_nhwc': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),

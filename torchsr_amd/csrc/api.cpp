@@ -124,9 +124,11 @@ std::mutex g_prof_mu;
 std::vector<ProfRec> g_prof;
 int g_prof_n = 0;
 bool g_prof_on = false;
+bool g_prof_aux = false;  // also record the helper launches behind a conv kernel (srx_prof_start_aux)
 }  // namespace
 
 bool srx_prof_on() { return g_prof_on; }
+bool srx_prof_aux() { return g_prof_on && g_prof_aux; }
 
 bool srx_prof_take(const char* name, double flops, hipEvent_t* e0, hipEvent_t* e1) {
   std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -151,7 +153,17 @@ extern "C" int srx_prof_start(int max_launches) {
   }
   g_prof_n = 0;
   g_prof_on = true;
+  g_prof_aux = false;
   return SRX_OK;
+}
+
+extern "C" int srx_prof_start_aux(int max_launches) {
+  const int rc = srx_prof_start(max_launches);
+  if (rc == SRX_OK) {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    g_prof_aux = true;
+  }
+  return rc;
 }
 
 extern "C" int srx_prof_stop(void) {

@@ -42,6 +42,7 @@ extern "C" int srx_plan_cus(void);
 
 // api.cpp: optional per-launch event timing (srx_prof_start / srx_prof_stop / srx_prof_get)
 bool srx_prof_on();
+bool srx_prof_aux();  // records asked for with srx_prof_start_aux: the helper launches (slab reductions) too
 bool srx_prof_take(const char* name, double flops, hipEvent_t* e0, hipEvent_t* e1);
 // launch `kernel`; with the profiler on, as a dispatch that carries its own start / stop events
 #define SRX_LAUNCH_PROF(name, flops, kernel, grid, block, lds, st, ...)                              \
@@ -51,6 +52,12 @@ bool srx_prof_take(const char* name, double flops, hipEvent_t* e0, hipEvent_t* e
       hipExtLaunchKernelGGL(kernel, grid, block, (std::uint32_t)(lds), st, e0__, e1__, 0, __VA_ARGS__); \
     else                                                                                             \
       hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);                                 \
+  } while (0)
+// a helper launch behind a conv kernel: recorded only by srx_prof_start_aux, so that srx_prof_start's records stay the conv kernels
+#define SRX_LAUNCH_PROF_AUX(name, kernel, grid, block, lds, st, ...)                                 \
+  do {                                                                                               \
+    if (srx_prof_aux()) SRX_LAUNCH_PROF(name, 0.0, kernel, grid, block, lds, st, __VA_ARGS__);       \
+    else hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);                              \
   } while (0)
 
 // thin.hip: 3-channel-side convolutions on v_mfma_f32_4x4x1 (internal, called from gconv.hip, wgrad.hip and convpack.hip)

@@ -1024,13 +1024,13 @@ static int wgrad_multi_impl(const srx_conv2d_t* d, int nprob, int per_out, const
   }
   if (srx_dev().old_wgrad_reduce || (size_t)g.K * sizeof(float) > 48 * 1024) {
     const int64_t n = (int64_t)d->Cout * g.K;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)srx_cdiv(n, 256), (unsigned)nout), dim3(256), 0, st, ws,
-                       nsplit * per_out, a.Cnw, a.Kw, g.K, g.Ck, d->Cout, d->Cin, d->KH, d->KW, g.cps, outs, accumulate,
-                       a.bslab);
+    SRX_LAUNCH_PROF_AUX("wgrad_reduce_kernel", wgrad_reduce_kernel, dim3((unsigned)srx_cdiv(n, 256), (unsigned)nout), dim3(256), 0, st, ws,
+                    nsplit * per_out, a.Cnw, a.Kw, g.K, g.Ck, d->Cout, d->Cin, d->KH, d->KW, g.cps, outs, accumulate,
+                    a.bslab);
   } else {
-    hipLaunchKernelGGL(wgrad_reduce_rows_kernel, dim3((unsigned)d->Cout, (unsigned)nout), dim3(256), (size_t)g.K * sizeof(float), st, ws,
-                       nsplit * per_out, a.Cnw, a.Kw, g.K, g.Ck, d->Cout, d->Cin, d->KH, d->KW, g.cps, outs, accumulate,
-                       a.bslab);
+    SRX_LAUNCH_PROF_AUX("wgrad_reduce_rows_kernel", wgrad_reduce_rows_kernel, dim3((unsigned)d->Cout, (unsigned)nout), dim3(256),
+                    (size_t)g.K * sizeof(float), st, ws, nsplit * per_out, a.Cnw, a.Kw, g.K, g.Ck, d->Cout, d->Cin, d->KH, d->KW, g.cps,
+                    outs, accumulate, a.bslab);
   }
   SRX_CHECK_LAUNCH("wgrad_reduce_kernel");
   return SRX_OK;
