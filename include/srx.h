@@ -86,6 +86,17 @@ int srx_nchw_to_nhwc(const float* src, float* dst, int N, int C, int H, int W, i
 /* NHWC [N][H][W][Cs] -> NCHW [N][C][H][W]; also `torch.flatten(out, 1)` in NCHW
  * order for the discriminator head (srgan/discriminator.py:86). */
 int srx_nhwc_to_nchw(const float* src, float* dst, int N, int C, int H, int W, int Cs, void* stream);
+/* One of the eight flips / transposes of an image (the dihedral group), with scaling and accumulation -- the geometry of
+ * the self-ensemble of test.upscale(self_ensemble=n), `torchsr test --self-ensemble`; no reference counterpart
+ * (torchsr/test.py:57-62 runs the generator once).  src: [planes][H][W] (NCHW with planes = N * C); k in 0..7 -- bit 0
+ * transpose, bit 1 horizontal flip, bit 2 vertical flip, the transpose first: source element (y, x) goes to (u, v) = (x, y)
+ * in a dst of [planes][H' = W][W' = H] with bit 0, else (y, x) in [planes][H' = H][W' = W]; then v = W' - 1 - v with
+ * bit 1 and u = H' - 1 - u with bit 2;
+ *   dst[p][u][v] = alpha * src[p][y][x] + beta * dst[p][u][v]   (one fma; beta == 0: dst is not read).
+ * The inverse of k is k itself without bit 0 and k with bits 1 and 2 swapped with it.  src and dst must not overlap;
+ * alpha, beta finite.  Any H, W, 64-bit offsets throughout (planes * H * W may pass 2^31). */
+int srx_dihedral_planes(const float* src, float* dst, int64_t planes, int H, int W, int k, float alpha, float beta,
+                        void* stream);
 
 /* ------------------------------------------------------------------ conv2d */
 /* One nn.Conv2d instance: srgan/residual.py:27,64,67; srgan/generator.py:38,48,58;

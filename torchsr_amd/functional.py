@@ -456,6 +456,41 @@ def flatten_nchw(x: Tensor) -> Tensor:
     return to_nchw(x).reshape(x.shape[0], -1)
 
 
+def dihedral_inverse(k: int) -> int:
+    """The group element that undoes ``dihedral(., k)``.  ``k``: bit 0 transpose, bit 1 horizontal flip, bit 2 vertical flip,
+    the transpose applied first.  Flips are their own inverses and commute; a transpose turns a horizontal flip into a
+    vertical one, ``(V^c H^b Tr)^-1 = Tr H^b V^c = V^b H^c Tr``: with bit 0 set, bits 1 and 2 change places."""
+    if not isinstance(k, int) or not 0 <= k <= 7:
+        raise ValueError(f'dihedral_inverse: k must be an int in 0..7, got {k!r}')
+    return k if not k & 1 else 1 | (k & 2) << 1 | (k & 4) >> 1
+
+
+def dihedral(x: Tensor, k: int, out: Optional[Tensor] = None, alpha: float = 1.0, beta: float = 0.0) -> Tensor:
+    """``out = alpha * T_k(x) + beta * out`` on an NCHW tensor, ``T_k`` one of the eight flips / transposes of the last two
+    dimensions (``srx_dihedral_planes``; ``dihedral_inverse`` names the bits).  ``out`` is allocated when None (``beta``
+    must then be 0: there is nothing to add to) and is [N, C, W, H] for a transposing ``k``.  Inference only."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError('dihedral: inference-only (no backward); run it under torch.no_grad()')
+    if not isinstance(k, int) or not 0 <= k <= 7:
+        raise ValueError(f'dihedral: k must be an int in 0..7, got {k!r}')
+    if x.dim() != 4:
+        raise ValueError(f'dihedral: expected an NCHW tensor, got shape {tuple(x.shape)}')
+    x = _chk(x, 'dihedral.input')
+    n, c, h, w = x.shape
+    shape = (n, c, w, h) if k & 1 else (n, c, h, w)
+    if out is None:
+        if beta != 0.0:
+            raise ValueError('dihedral: beta != 0 needs the tensor to add to (out=)')
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        if _chk(out, 'dihedral.out') is not out:
+            raise RuntimeError('dihedral: out must be contiguous')
+        if tuple(out.shape) != shape or out.device != x.device:
+            raise ValueError(f'dihedral: k = {k} maps {tuple(x.shape)} to {shape}, out is {tuple(out.shape)} on {out.device}')
+    call('srx_dihedral_planes', _p(x), _p(out), n * c, h, w, k, float(alpha), float(beta), _stream())
+    return out
+
+
 # --------------------------------------------------------------------------- conv2d
 class ConvState:
     """Per-layer host state: geometry descriptors and packed weight copies."""

@@ -35,7 +35,8 @@ def load_generator_state(path: str) -> OrderedDict:
 
 @torch.no_grad()
 def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
-            max_tile_pixels: int = MAX_TILE_PIXELS, scale: int = 4, precision: str = None, staged: bool = True) -> Tensor:
+            max_tile_pixels: int = MAX_TILE_PIXELS, scale: int = 4, precision: str = None, staged: bool = True,
+            self_ensemble: int = 0) -> Tensor:
     """``generator(low_res)`` in eval mode, tiled when the image is large.  ``low_res``: [N,3,h,w].
 
     ``precision``: ``'fp32'`` (exact; the reference's ``test`` runs no autocast, test.py:57-62), ``'bf16'`` (bf16
@@ -44,7 +45,18 @@ def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
     accumulation in every conv, the 64-channel activations stored as fp16; a non-finite output, i.e. an overflow of
     fp16's +-65504, raises ``FloatingPointError``); ``None`` keeps whatever the generator's convs are set to.  The setting
     is restored afterwards.  ``staged=False`` forces the halo tiling for a generator that offers the two-stage interface
-    (``_upscale_staged``)."""
+    (``_upscale_staged``).
+
+    ``self_ensemble``: 0 / False: off.  8 / True: the geometric self-ensemble (the "+" variants of EDSR / RCAN / ESRGAN) --
+    the generator runs on the 8 flips / transposes of the image, every result is mapped back and the 8 are averaged; 4: the
+    flips only (all four variants keep the input's shape).  ``n`` generator forwards, each with every other argument as
+    given; no new weights.  See ``_upscale_ensemble``."""
+    if isinstance(self_ensemble, bool):
+        self_ensemble = 8 if self_ensemble else 0
+    if not isinstance(self_ensemble, int) or self_ensemble not in (0, 4, 8):
+        raise ValueError(f'upscale: self_ensemble must be 0 / False, 4, or 8 / True, got {self_ensemble!r}')
+    if self_ensemble:
+        return _upscale_ensemble(generator, low_res, halo, max_tile_pixels, scale, precision, staged, self_ensemble)
     from . import _dev
     from .functional import PRECISION_F16
     from .layers import Conv2d, set_conv_precision
@@ -99,6 +111,28 @@ def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
     return out
 
 
+def _upscale_ensemble(generator: torch.nn.Module, low_res: Tensor, halo, max_tile_pixels: int, scale: int, precision,
+                      staged: bool, n: int) -> Tensor:
+    """Geometric self-ensemble: ``mean_k T_k^-1(upscale(T_k(low_res)))`` over the group elements ``k`` (``F.dihedral``: bit 0
+    transpose, bit 1 horizontal flip, bit 2 vertical flip) -- all 8, or the 4 without a transpose.  The variants run one after
+    another, ``k`` ascending, each through ``upscale`` itself: tiling, the staged trunk, the precision set / restore and the
+    fp16 overflow check apply per variant, and an exception from one of them propagates (no partial sum is returned).  One
+    kernel per variant maps the result back, scales it and adds it to the sum (csrc/dihedral.hip).
+    The result is bit-reproducible: the order of the sum is fixed, and 1 / n is a power of two, so ``y / n`` is exact and
+    the kernel's fma ``(1 / n) * y + acc`` rounds once, to the same bits as a multiply followed by an add."""
+    from . import functional as F
+    acc = None
+    for k in range(0, 8, 8 // n):  # n = 4: k = 0, 2, 4, 6
+        x_k = low_res if k == 0 else F.dihedral(low_res, k)
+        y_k = upscale(generator, x_k, halo, max_tile_pixels, scale, precision, staged)
+        if acc is None:
+            nb, c, h, w = low_res.shape
+            acc = torch.empty((nb, y_k.shape[1], h * scale, w * scale), dtype=torch.float32, device=y_k.device)
+        F.dihedral(y_k, F.dihedral_inverse(k), out=acc, alpha=1.0 / n, beta=0.0 if k == 0 else 1.0)
+        del x_k, y_k
+    return acc
+
+
 def _upscale_staged(generator: torch.nn.Module, low_res: Tensor, max_out_pixels: int, scale: int) -> Tensor:
     """Large image, generator with a two-stage inference interface (SRGAN): the low-resolution trunk -- 33 of the 36
     convs, receptive field radius 38 pixels -- runs ONCE on the whole image (its largest tensor, h*w*256 floats, stays
@@ -131,6 +165,7 @@ def test(args: Namespace, model: object, device) -> None:
     generator.load_state_dict(load_generator_state(f'{args.model.lower()}-gan-best.pth'))
     image = np.asarray(Image.open(args.image).convert('RGB'), dtype='float32') / 255.0
     low_res = torch.from_numpy(image).permute(2, 0, 1).unsqueeze(0).contiguous().to(device)
-    super_res = upscale(generator, low_res, precision=getattr(args, 'precision', None) or 'fp32')
+    super_res = upscale(generator, low_res, precision=getattr(args, 'precision', None) or 'fp32',
+                        self_ensemble=getattr(args, 'self_ensemble', 0) or 0)
     head, tail = os.path.split(args.image)
     save_image(super_res, os.path.join(head, f'upres-{tail}'))

@@ -126,6 +126,10 @@ def parse_args(argv=None) -> Namespace:
                       help='conv arithmetic of the generator forward: exact fp32 (the reference runs no autocast here), '
                            'bf16 products with fp32 accumulation, or fp16 products and fp16-stored activations with fp32 '
                            'accumulation (SRGAN only; an fp16 overflow is reported, not written)')
+    test.add_argument('--self-ensemble', type=int, nargs='?', const=8, default=0, choices=(4, 8),
+                      help='geometric self-ensemble: run the generator on the 8 flips / transposes of the image (4: the '
+                           'flips only), map every result back and average them.  Costs N generator forwards instead of '
+                           'one; needs no other weights; combines with every --precision and either --model')
     return parser.parse_args(argv)
 
 
