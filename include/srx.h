@@ -97,6 +97,21 @@ int srx_nhwc_to_nchw(const float* src, float* dst, int N, int C, int H, int W, i
  * alpha, beta finite.  Any H, W, 64-bit offsets throughout (planes * H * W may pass 2^31). */
 int srx_dihedral_planes(const float* src, float* dst, int64_t planes, int H, int W, int k, float alpha, float beta,
                         void* stream);
+/* Separable resize of fp32 planes with the weight tables as operands -- the `outscale` of test.upscale, `torchsr test
+ * --outscale` (functional.resize_bicubic_aa; the tables of functional.resample_tables make it the antialiased Keys bicubic
+ * the training data is reduced with); no reference counterpart (torchsr/test.py:57-62 writes the x4 result).
+ * src: [planes][H][W] -> dst: [planes][OH][OW], any mix of reduction and enlargement per axis.  Per axis (y: n_in = H,
+ * n_out = OH; x: n_in = W, n_out = OW) start[n_out] (int32) and weight[n_out][K] (fp32, rows padded with 0), all in device memory:
+ *   tmp[p][oy][x]  = sum_t weight_y[oy][t] * src[p][min(start_y[oy] + t, H - 1)][x]     t = 0 .. Ky - 1
+ *   dst[p][oy][ox] = sum_t weight_x[ox][t] * tmp[p][oy][min(start_x[ox] + t, W - 1)]    t = 0 .. Kx - 1
+ * in fp32, fmas in ascending t from 0 (two launches, no atomics: the same bits from every call, a plane's bits whatever
+ * the other planes are).  Every start is clamped to [0, n_in - 1]: no table content reads outside src.
+ * ws: the workspace tmp, ws_floats >= planes * OH * W.  1 <= Ky, Kx <= 66 (a 16:1 reduction); H * W, OH * OW and OH * W
+ * < 2^31, 64-bit plane bases (planes * H * W may pass 2^31); src, dst and ws 4-byte aligned (16-byte accesses when W % 4 == 0
+ * and src and ws are 16-byte aligned) and disjoint. */
+int srx_resample_planes(const float* src, float* dst, int64_t planes, int H, int W, int OH, int OW, const int* start_y,
+                        const float* weight_y, int Ky, const int* start_x, const float* weight_x, int Kx, float* ws,
+                        size_t ws_floats, void* stream);
 
 /* ------------------------------------------------------------------ conv2d */
 /* One nn.Conv2d instance: srgan/residual.py:27,64,67; srgan/generator.py:38,48,58;

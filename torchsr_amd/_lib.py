@@ -12,7 +12,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('SRX_LIB') or os.path.join(CSRC, 'libsrx_hip.so')  # SRX_LIB: developer A/B builds on one GPU box
-SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip']
+SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip', 'resample.hip']
 # headers the sources include, relative to CSRC: part of the build's digest and of every object's cache key
 HEADERS = ['srx_common.h', 'conv_host.h', os.path.join('..', '..', 'include', 'srx.h')]
 
@@ -160,6 +160,7 @@ _SIGS = {
     'srx_nchw_to_nhwc': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     'srx_nhwc_to_nchw': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     'srx_dihedral_planes': (_I, [_P, _P, _L, _I, _I, _I, _F, _F, _P]),
+    'srx_resample_planes': (_I, [_P, _P, _L, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _Z, _P]),
     'srx_conv2d_packed_fwd_floats': (_Z, [_D]),
     'srx_conv2d_packed_bwd_floats': (_Z, [_D]),
     'srx_conv2d_fwd_ws_floats': (_Z, [_D]),

@@ -491,6 +491,90 @@ def dihedral(x: Tensor, k: int, out: Optional[Tensor] = None, alpha: float = 1.0
     return out
 
 
+RESAMPLE_MAX_REDUCTION = 16  # n_in <= 16 * n_out: at most 4 * 16 + 2 = 66 taps (srx_resample_planes' limit)
+
+
+def resample_tables(n_in: int, n_out: int, dtype='float32'):
+    """``(start, weight, K)`` of one axis of the antialiased Keys bicubic (a = -0.5) -- PIL's ``BICUBIC``,
+    ``F.interpolate(mode='bicubic', antialias=True, align_corners=False)``, the filter ``srx_bicubic_down`` reduces the
+    training data with -- from ``n_in`` to ``n_out`` samples: output ``i`` is ``sum_t weight[i, t] * in[start[i] + t]``.
+    ``start``: int32 ``[n_out]``; ``weight``: ``[n_out, K]``, ``K`` the largest tap count, rows padded with 0.
+
+    With ``scale = n_in / n_out``, ``support = 2 * max(scale, 1)`` and ``inv = 1 / max(scale, 1)`` the taps of output ``i``
+    are ``lo <= j < hi``, ``c = scale * (i + 0.5)``, ``lo = max(0, int(c - support + 0.5))``, ``hi = min(n_in, int(c +
+    support + 0.5))``, weighted ``keys((j - c + 0.5) * inv)`` over their sum.  Built in fp64 with numpy, each row normalised
+    in fp64 and rounded once to ``dtype`` (``'float64'``: not at all).  ``n_in == n_out`` is the identity."""
+    import numpy as np
+    for name, v in (('n_in', n_in), ('n_out', n_out)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f'resample_tables: {name} must be a positive int, got {v!r}')
+    if n_in > RESAMPLE_MAX_REDUCTION * n_out:
+        raise ValueError(f'resample_tables: {n_in} -> {n_out} reduces by more than {RESAMPLE_MAX_REDUCTION}:1')
+    scale = n_in / n_out
+    support, inv = (2.0 * scale, 1.0 / scale) if scale >= 1.0 else (2.0, 1.0)
+    c = scale * (np.arange(n_out, dtype=np.float64) + 0.5)
+    lo = np.maximum(0, np.trunc(c - support + 0.5).astype(np.int64))
+    hi = np.minimum(n_in, np.trunc(c + support + 0.5).astype(np.int64))
+    k = int((hi - lo).max())
+    j = lo[:, None] + np.arange(k, dtype=np.int64)[None, :]
+    x = np.abs((j - c[:, None] + 0.5) * inv)
+    w = np.where(x < 1.0, ((1.5 * x - 2.5) * x) * x + 1.0, np.where(x < 2.0, (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5, 0.0))
+    w = np.where(j < hi[:, None], w, 0.0)
+    w = w / w.sum(axis=1, keepdims=True)
+    return lo.astype(np.int32), np.ascontiguousarray(w.astype(dtype)), k
+
+
+_resample_cache = {}
+
+
+def _resample_device_tables(n_in: int, n_out: int, device: torch.device):
+    """``resample_tables`` on ``device`` (start int32, weight fp32), built and copied once per (n_in, n_out, device)."""
+    key = (n_in, n_out, torch.device(device))
+    hit = _resample_cache.get(key)
+    if hit is None:
+        start, weight, k = resample_tables(n_in, n_out)
+        hit = _resample_cache[key] = (torch.from_numpy(start).to(device), torch.from_numpy(weight).to(device), k)
+    return hit
+
+
+def resize_bicubic_aa(x: Tensor, size: Tuple[int, int], out: Optional[Tensor] = None) -> Tensor:
+    """An NCHW tensor resized to ``size = (OH, OW)`` with the antialiased Keys bicubic of ``resample_tables`` -- any mix of
+    reduction (up to 16:1) and enlargement per axis -- in one ``srx_resample_planes`` call: two fp32 dot products per
+    output, bit-reproducible.  ``size == (H, W)`` is the identity: ``x`` itself (copied into ``out`` when given), no launch.
+    Inference only."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError('resize_bicubic_aa: inference-only (no backward); run it under torch.no_grad()')
+    if x.dim() != 4:
+        raise ValueError(f'resize_bicubic_aa: expected an NCHW tensor, got shape {tuple(x.shape)}')
+    try:
+        oh, ow = size
+    except (TypeError, ValueError):
+        raise ValueError(f'resize_bicubic_aa: size must be (OH, OW), got {size!r}') from None
+    n, c, h, w = x.shape
+    for name, v in (('OH', oh), ('OW', ow), ('H', h), ('W', w), ('N * C', n * c)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f'resize_bicubic_aa: {name} must be a positive int, got {v!r}')
+    if h > RESAMPLE_MAX_REDUCTION * oh or w > RESAMPLE_MAX_REDUCTION * ow:  # before anything touches the device
+        raise ValueError(f'resize_bicubic_aa: {(h, w)} -> {(oh, ow)} reduces an axis by more than {RESAMPLE_MAX_REDUCTION}:1')
+    x = _chk(x, 'resize_bicubic_aa.input')
+    shape = (n, c, oh, ow)
+    if out is not None:
+        if _chk(out, 'resize_bicubic_aa.out') is not out:
+            raise RuntimeError('resize_bicubic_aa: out must be contiguous')
+        if tuple(out.shape) != shape or out.device != x.device:
+            raise ValueError(f'resize_bicubic_aa: the result is {shape} on {x.device}, out is {tuple(out.shape)} on {out.device}')
+    if (oh, ow) == (h, w):
+        return x if out is None else out.copy_(x)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    sy, wy, ky = _resample_device_tables(h, oh, x.device)
+    sx, wx, kx = _resample_device_tables(w, ow, x.device)
+    nws = n * c * oh * w
+    ws = _ws(nws, x)
+    call('srx_resample_planes', _p(x), _p(out), n * c, h, w, oh, ow, _p(sy), _p(wy), ky, _p(sx), _p(wx), kx, _p(ws), nws, _stream())
+    return out
+
+
 # --------------------------------------------------------------------------- conv2d
 class ConvState:
     """Per-layer host state: geometry descriptors and packed weight copies."""

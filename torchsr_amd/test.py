@@ -36,7 +36,7 @@ def load_generator_state(path: str) -> OrderedDict:
 @torch.no_grad()
 def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
             max_tile_pixels: int = MAX_TILE_PIXELS, scale: int = 4, precision: str = None, staged: bool = True,
-            self_ensemble: int = 0) -> Tensor:
+            self_ensemble: int = 0, outscale: float = None) -> Tensor:
     """``generator(low_res)`` in eval mode, tiled when the image is large.  ``low_res``: [N,3,h,w].
 
     ``precision``: ``'fp32'`` (exact; the reference's ``test`` runs no autocast, test.py:57-62), ``'bf16'`` (bf16
@@ -50,7 +50,19 @@ def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
     ``self_ensemble``: 0 / False: off.  8 / True: the geometric self-ensemble (the "+" variants of EDSR / RCAN / ESRGAN) --
     the generator runs on the 8 flips / transposes of the image, every result is mapped back and the 8 are averaged; 4: the
     flips only (all four variants keep the input's shape).  ``n`` generator forwards, each with every other argument as
-    given; no new weights.  See ``_upscale_ensemble``."""
+    given; no new weights.  See ``_upscale_ensemble``.
+
+    ``outscale``: the total factor from ``low_res`` to the result.  ``None`` or ``scale``: the generator's own result, this
+    path untouched.  Any other positive number: the generator still runs at x ``scale``, and its full result -- tiles or
+    strips assembled, the ensemble averaged, the fp16 check passed -- is resampled ONCE to ``(int(h * outscale + 0.5),
+    int(w * outscale + 0.5))`` (at least 1) with the antialiased bicubic the training data is reduced with
+    (``F.resize_bicubic_aa``, csrc/resample.hip).  A reduction of the x ``scale`` result by more than 16:1 is refused."""
+    if outscale is not None:
+        size = _outscale_size(low_res, outscale, scale)
+        if size is not None:
+            from . import functional as F
+            full = upscale(generator, low_res, halo, max_tile_pixels, scale, precision, staged, self_ensemble)
+            return F.resize_bicubic_aa(full, size)
     if isinstance(self_ensemble, bool):
         self_ensemble = 8 if self_ensemble else 0
     if not isinstance(self_ensemble, int) or self_ensemble not in (0, 4, 8):
@@ -111,6 +123,24 @@ def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
     return out
 
 
+def _outscale_size(low_res: Tensor, outscale, scale: int):
+    """The size ``upscale(outscale=)`` resamples the x ``scale`` result to; None when ``outscale`` is ``scale`` itself.
+    ``ValueError`` for what the resampler would refuse -- here, before the generator runs."""
+    import math
+    if isinstance(outscale, bool) or not isinstance(outscale, (int, float)) or not math.isfinite(outscale) or not outscale > 0:
+        raise ValueError(f'upscale: outscale must be a finite positive number, got {outscale!r}')
+    if outscale == scale:
+        return None
+    h, w = int(low_res.shape[-2]), int(low_res.shape[-1])
+    oh, ow = max(1, int(h * outscale + 0.5)), max(1, int(w * outscale + 0.5))
+    if h * scale > 16 * oh or w * scale > 16 * ow:
+        raise ValueError(f'upscale: outscale = {outscale!r} reduces the x{scale} result {(h * scale, w * scale)} to {(oh, ow)}, '
+                         f'more than 16:1 along an axis')
+    if oh * ow >= 2 ** 31 or oh * w * scale >= 2 ** 31:
+        raise ValueError(f'upscale: outscale = {outscale!r} gives planes of {(oh, ow)}: 2^31 elements or more')
+    return oh, ow
+
+
 def _upscale_ensemble(generator: torch.nn.Module, low_res: Tensor, halo, max_tile_pixels: int, scale: int, precision,
                       staged: bool, n: int) -> Tensor:
     """Geometric self-ensemble: ``mean_k T_k^-1(upscale(T_k(low_res)))`` over the group elements ``k`` (``F.dihedral``: bit 0
@@ -166,6 +196,6 @@ def test(args: Namespace, model: object, device) -> None:
     image = np.asarray(Image.open(args.image).convert('RGB'), dtype='float32') / 255.0
     low_res = torch.from_numpy(image).permute(2, 0, 1).unsqueeze(0).contiguous().to(device)
     super_res = upscale(generator, low_res, precision=getattr(args, 'precision', None) or 'fp32',
-                        self_ensemble=getattr(args, 'self_ensemble', 0) or 0)
+                        self_ensemble=getattr(args, 'self_ensemble', 0) or 0, outscale=getattr(args, 'outscale', None))
     head, tail = os.path.split(args.image)
     save_image(super_res, os.path.join(head, f'upres-{tail}'))

@@ -130,6 +130,11 @@ def parse_args(argv=None) -> Namespace:
                       help='geometric self-ensemble: run the generator on the 8 flips / transposes of the image (4: the '
                            'flips only), map every result back and average them.  Costs N generator forwards instead of '
                            'one; needs no other weights; combines with every --precision and either --model')
+    test.add_argument('--outscale', type=positive_float, default=None, metavar='FLOAT',
+                      help='total factor from the image to the result (default: the model\'s 4).  The model always runs at '
+                           'x4; its result is then resampled once, on the GPU, with the antialiased bicubic filter the '
+                           'training data was reduced with (2: a 4K picture from a 1080p one).  Combines with every '
+                           '--precision, --self-ensemble and either --model')
     return parser.parse_args(argv)
 
 
