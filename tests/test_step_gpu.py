@@ -476,9 +476,9 @@ def test_pack_tables_take_over_after_the_first_step(dev):
         for m in model.modules():
             if isinstance(m, Conv2d):  # the copies a layer's kernels read are current: the direct packs, the Winograd-domain ones, or both
                 key, st = m._st.pack_key(m.weight), m._st
-                assert st.wpk_fwd is not None or st.__dict__.get('wino_fwd') is not None
-                assert st.wpk_fwd is None or st._key == key
-                assert st.__dict__.get('wino_fwd') is None or st._wino_key == key
+                assert st.wpk_fwd is not None or st.wino_fwd is not None
+                assert st.wpk_fwd is None or st.direct.key == key
+                assert st.wino_fwd is None or st.wino.key == key
     assert t.psnr_optimizer.pack_table is t.gen_optimizer.pack_table
 
 

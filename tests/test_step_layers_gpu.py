@@ -149,7 +149,7 @@ def run_conv_case(case, dev, report, precision='fp32', u=U, prefill=0.0):
         torch.cuda.synchronize()
     finally:
         F.direct_grads[0] = was
-    wino = conv._st.__dict__.get('wino_fwd') is not None
+    wino = conv._st.wino_fwd is not None
     tag = case['id']
 
     pre64, pre32, by = conv_refs('y', x, wt, x.shape, wt.shape, s, p, up, b, rounded['y'], u)
@@ -187,7 +187,7 @@ def run_conv_case(case, dev, report, precision='fp32', u=U, prefill=0.0):
             mask = (x > 0).double() if in_act == 'relu' else torch.where(x > 0, 1.0, 0.2).double()
             dx64, dx32, bdx = dx64 * mask, dx32 * mask.float(), bdx * mask
         got_dx = nchw(xg.grad.cpu(), cin)
-        wino_dx = conv._st.__dict__.get('wino_bwd') is not None  # (a forward-only Winograd layer takes the direct data gradient)
+        wino_dx = conv._st.wino_bwd is not None  # (a forward-only Winograd layer takes the direct data gradient)
         check(f'{tag} dx', got_dx, dx64, dx32, bdx, wino_dx, report)
     if dw_on:
         m = g_pre[:, 0].numel()
@@ -300,7 +300,7 @@ def run_stack_case(case, dev, report):
     gy = torch.randn((n, cout, h, w), generator=g)
     fs.backward(nhwc(gy, cout).to(dev))
     torch.cuda.synchronize()
-    wino = conv._st.__dict__.get('wino_fwd') is not None
+    wino = conv._st.wino_fwd is not None
     pre64, pre32 = TF.conv2d(x.double(), wt.double(), b.double(), 1, 1), TF.conv2d(x, wt, b, 1, 1)
     got_y = torch.cat([nchw(fs.detach().cpu(), cout), nchw(ft.cpu(), cout)])
     absconv = TF.conv2d(x.double().abs(), wt.double().abs(), b.double().abs(), 1, 1)
@@ -309,7 +309,7 @@ def run_stack_case(case, dev, report):
     dx64 = torch.nn.grad.conv2d_input((n, cin, h, w), wt.double(), g_pre.double(), 1, 1)
     dx32 = torch.nn.grad.conv2d_input((n, cin, h, w), wt, g_pre, 1, 1)
     absdx = torch.nn.grad.conv2d_input((n, cin, h, w), wt.double().abs(), g_pre.double().abs(), 1, 1)
-    check(f"{case['id']} dx", nchw(src.grad.cpu(), cin), dx64, dx32, gamma(cout * 9) * absdx, conv._st.__dict__.get('wino_bwd') is not None, report)
+    check(f"{case['id']} dx", nchw(src.grad.cpu(), cin), dx64, dx32, gamma(cout * 9) * absdx, conv._st.wino_bwd is not None, report)
 
 
 def run_case(case, dev, report):

@@ -6,11 +6,13 @@ host code -- the autograd Functions and launchers of torchsr_amd/functional.py -
 ``_lib.call`` and every module-level alias of it in the package are wrapped (as tests/step_layers.py::record_op_calls does, but for
 every entry point, the conv ones included).  One line per call: the name, then per argument -- by the declared ctypes signature --
 the value of an int / int64 / size_t / float, the fields of a conv descriptor, and for any other pointer only whether it is null.
-Each case runs once, eagerly (no hipGraph), from one seed, at the smallest sizes the step tests use (batch 2, their trainer
-settings, their golden inputs): an SRGAN step, an ESRGAN step in fp32 and one under autocast (bf16-storage VGG stack, fused dense
-blocks), the VGG loss forward and backward alone, and Generator inference in fp32, bf16 and fp16.  Sizing calls made on the
-library handle directly (``*_ws_floats``) are not traced; the sizes they return are (``nws`` arguments).  A swapped pair of
-non-null pointers is invisible here: the numerical tests cover that.
+Each case runs eagerly (no hipGraph), from one seed, at the smallest sizes the step tests use (batch 2, their trainer settings,
+their golden inputs): three SRGAN steps, three ESRGAN steps in fp32 and three under autocast (bf16-storage VGG stack, fused dense
+blocks) -- the first packs lazily per layer, the later ones after the pack tables took over --, the VGG loss forward and backward
+alone, and Generator inference in fp32, bf16 and fp16: a first call, a second (every pack current) and a third after an in-place
+update of one weight that changes no value (that layer's repack and nothing else).  The digest of the library's sources is the
+first line.  Sizing calls made on the library handle directly (``*_ws_floats``) are not traced; the sizes they return are
+(``nws`` arguments).  A swapped pair of non-null pointers is invisible here: the numerical tests cover that.
 """
 import ctypes as C
 import os
@@ -93,11 +95,13 @@ def main():
         g = np.load(os.path.join(GOLDEN, gold))
         lr, hr = torch.from_numpy(g['low_res']).to(dev), torch.from_numpy(g['high_res']).to(dev)
         t = trainer(cls, dev, tag, disable_amp)
-        traced(out, what, lambda: t.gan_step(lr, hr))
+        for i in (1, 2, 3):
+            traced(out, '%s, step %d' % (what, i), lambda: t.gan_step(lr, hr))
 
-    step(SRGANTrainer, 'srgan', 'srgan_steps.npz', True, 'SRGAN step, fp32')
-    step(ESRGANTrainer, 'esrgan', 'esrgan.npz', True, 'ESRGAN step, fp32')
-    step(ESRGANTrainer, 'esrgan', 'esrgan.npz', False, 'ESRGAN step, autocast')
+    out.append('# library sources ' + _lib.source_digest())
+    step(SRGANTrainer, 'srgan', 'srgan_steps.npz', True, 'SRGAN, fp32')
+    step(ESRGANTrainer, 'esrgan', 'esrgan.npz', True, 'ESRGAN, fp32')
+    step(ESRGANTrainer, 'esrgan', 'esrgan.npz', False, 'ESRGAN, autocast')
 
     vgg = VGGLoss(weights='random').to(dev)
     src, tgt = torch.rand(2, 3, 32, 48, device=dev).requires_grad_(True), torch.rand(2, 3, 32, 48, device=dev)
@@ -106,11 +110,16 @@ def main():
     gen = Generator().to(dev)
     low = torch.rand(2, 3, 24, 24, device=dev)
     for precision in ('fp32', 'bf16', 'fp16'):
-        traced(out, 'Generator inference, ' + precision, lambda: upscale(gen, low, precision=precision))
+        traced(out, 'Generator inference, %s, first call' % precision, lambda: upscale(gen, low, precision=precision))
+        traced(out, 'Generator inference, %s, second call' % precision, lambda: upscale(gen, low, precision=precision))
+        with torch.no_grad():
+            gen.conv1[0].weight.mul_(1.0)
+        traced(out, 'Generator inference, %s, after an in-place update of conv1' % precision,
+               lambda: upscale(gen, low, precision=precision))
 
     with open(sys.argv[1], 'w') as f:
         f.write('\n'.join(out) + '\n')
-    print('%d calls in %d cases written to %s' % (sum(not ln.startswith('#') for ln in out), sum(ln.startswith('#') for ln in out),
+    print('%d calls in %d cases written to %s' % (sum(not ln.startswith('#') for ln in out), sum(ln.startswith('#') for ln in out) - 1,
                                                   sys.argv[1]))
 
 

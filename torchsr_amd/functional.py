@@ -229,15 +229,10 @@ def conv2d_bf16in(conv, x: Tensor) -> Tensor:
         # storage type too: a bf16 call after an fp16 one must not read fp16 weights
         sfx = 'f16' if f16 else 'bf16'
         key = st.pack_key(conv.weight) + (None if b is None else (b.data_ptr(), conv.bias._version), x.dtype)
-        if conv.__dict__.get('_t9_key') != key:
-            wpk = conv.__dict__.get('_t9_wpk')
-            if wpk is None or wpk.device != x.device:
-                wpk = conv.__dict__['_t9_wpk'] = torch.empty(_lib.lib().srx_conv9x9_c64_thin_bf16_packed_bytes(), dtype=torch.uint8,
-                                                             device=x.device)
-            call(f'srx_conv9x9_c64_thin_{sfx}_pack', _p(_chk(conv.weight.detach(), 'conv2d.weight')), _p(b), st.cout, _p(wpk),
-                 _stream())
-            conv.__dict__['_t9_key'] = key
-        call(f'srx_conv9x9_c64_thin_{sfx}_fwd', n, h, w, _p(x), _p(conv.__dict__['_t9_wpk']), _p(y), _stream())
+        st.thin9.ensure(key, x.device, False, lambda: (_lib.lib().srx_conv9x9_c64_thin_bf16_packed_bytes(), 0, torch.uint8),
+                        lambda fwd, bwd, _: call(f'srx_conv9x9_c64_thin_{sfx}_pack', _p(_chk(conv.weight.detach(), 'conv2d.weight')),
+                                                 _p(b), st.cout, _p(fwd), _stream()))
+        call(f'srx_conv9x9_c64_thin_{sfx}_fwd', n, h, w, _p(x), _p(st.thin9.fwd), _p(y), _stream())
         return y
     d = st.desc(n, h, w)
     st.pack(conv.weight, d)
@@ -576,6 +571,35 @@ def resize_bicubic_aa(x: Tensor, size: Tuple[int, int], out: Optional[Tensor] = 
 
 
 # --------------------------------------------------------------------------- conv2d
+class WeightPack:
+    """One packed layout of a layer's (or a chain of layers') weights: the forward buffer, the optional backward one, the key
+    they were built from and, where the layout has one, the descriptor they were built with -- all ``None`` until built.
+    ``ensure`` is THE rule for "is this copy current, and if not, what is allocated and packed"; it runs no device code of
+    its own.  Once a buffer exists a repack writes into the same storage (pack tables and captured graphs hold its address)."""
+    __slots__ = ('fwd', 'bwd', 'key', 'desc')
+
+    def __init__(self):
+        self.fwd = self.bwd = self.key = self.desc = None
+
+    def ensure(self, key, device, need_bwd: bool, size, pack, desc=None) -> None:
+        """``size() -> (fwd elements, bwd elements, dtype)``, asked only when the copies are not current; ``pack(fwd, bwd,
+        bwd_only)`` writes the buffers it is given -- ``bwd_only``: ``fwd`` is current, only a backward copy is being added."""
+        fresh = key == self.key and self.fwd is not None
+        if fresh and (self.bwd is not None or not need_bwd):
+            return
+        n_fwd, n_bwd, dtype = size()
+        if self.fwd is None or self.fwd.device != device or self.fwd.numel() != n_fwd or self.fwd.dtype != dtype:
+            self.fwd, self.bwd, fresh = torch.empty(n_fwd, dtype=dtype, device=device), None, False
+        if need_bwd and self.bwd is None:
+            self.bwd = torch.empty(n_bwd, dtype=dtype, device=device)
+        pack(self.fwd, self.bwd, fresh)
+        self.key, self.desc = key, desc
+
+    def stamp(self, key) -> None:
+        """Record ``key`` without packing: someone else (``PackTable.run``) has just rewritten the buffers from it."""
+        self.key = key
+
+
 class ConvState:
     """Per-layer host state: geometry descriptors and packed weight copies."""
 
@@ -589,9 +613,10 @@ class ConvState:
         self.model_epoch = [0]  # replaced by the owning FlatParams' counter
         self.precision = 0  # 1: bf16 products in the forward / stride-1 data gradient; 3: fp16 inference (srx_conv2d_t::precision)
         # (3 reaches srx_conv2d_* only for the <= 4-channel input conv; the 64-channel layers run the _f16 chain entry points)
-        self.wpk_fwd = None
-        self.wpk_bwd = None
-        self._key = None
+        # the packed copies of the weights, one slot per kernel family that reads its own layout
+        self.direct, self.wino, self.bf16s, self.thin9 = WeightPack(), WeightPack(), WeightPack(), WeightPack()
+        # the slots' buffers under the names their readers use: aliases, set again after every ``ensure`` of the slot
+        self.wpk_fwd = self.wpk_bwd = self.wino_fwd = self.wino_bwd = self.bf16s_fwd = self.bf16s_bwd = None
         self.fused_only = False  # set while the layer runs inside a fused multi-conv kernel that has its own weight stream
 
     def desc(self, n, h, w) -> Conv2dDesc:
@@ -603,20 +628,18 @@ class ConvState:
             self._descs[(n, h, w, self.precision)] = d
         return d
 
+    def _out_hw(self, h, w):
+        uf = 2 if self.up == 2 else 1
+        return (uf * h + 2 * self.pad - self.k) // self.stride + 1, (uf * w + 2 * self.pad - self.k) // self.stride + 1
+
     def out_rows(self, n, h, w) -> int:
         """Rows of the output matrix (pixels the conv computes; before any PixelShuffle)."""
-        uf = 2 if self.up == 2 else 1
-        ho = (uf * h + 2 * self.pad - self.k) // self.stride + 1
-        wo = (uf * w + 2 * self.pad - self.k) // self.stride + 1
+        ho, wo = self._out_hw(h, w)
         return n * ho * wo
 
     def out_shape(self, n, h, w):
-        uf = 2 if self.up == 2 else 1
-        ho = (uf * h + 2 * self.pad - self.k) // self.stride + 1
-        wo = (uf * w + 2 * self.pad - self.k) // self.stride + 1
-        if self.shuffle:
-            return (n, 2 * ho, 2 * wo, self.cout_s)
-        return (n, ho, wo, self.cout_s)
+        ho, wo = self._out_hw(h, w)
+        return (n, 2 * ho, 2 * wo, self.cout_s) if self.shuffle else (n, ho, wo, self.cout_s)
 
     def pack_key(self, weight: Tensor):
         """What the packed copies were made from: the tensor, its in-place version, the global epoch (bumped
@@ -626,65 +649,44 @@ class ConvState:
             return (weight.data_ptr(), weight._version, -1, -1, self.precision)
         return (weight.data_ptr(), weight._version, _pack_epoch[0], self.model_epoch[0], self.precision)
 
-    def pack(self, weight: Tensor, d: Conv2dDesc, force: bool = False) -> None:
-        """(Re)build the packed copies when the master OIHW weight changed.
-
-        ``weight`` is the module's Parameter: its ``_version`` catches in-place torch updates,
-        the optimiser epoch catches raw-pointer updates by ``srx_adam_step`` (frozen parameters
-        such as VGG19's never repack)."""
-        key = self.pack_key(weight)
-        if not force and key == self._key and self.wpk_fwd is not None:
-            return
-        dref = C.byref(d)
-        if self.wpk_fwd is None or self.wpk_fwd.device != weight.device:
-            self.wpk_fwd = torch.empty(_lib.lib().srx_conv2d_packed_fwd_floats(dref), dtype=torch.float32,
-                                       device=weight.device)
-            self.wpk_bwd = torch.empty(max(_lib.lib().srx_conv2d_packed_bwd_floats(dref), 4), dtype=torch.float32,
-                                       device=weight.device)
-        w = _chk(weight.detach(), 'conv2d.weight')
-        call('srx_conv2d_pack', dref, _p(w), _p(self.wpk_fwd), _p(self.wpk_bwd), _stream())
-        self._key = key
-        self.last_desc = d
+    def pack(self, weight: Tensor, d: Conv2dDesc) -> None:
+        """(Re)build the packed copies of the direct kernels when the master OIHW weight changed.  ``weight`` is the module's
+        Parameter: its ``_version`` catches in-place torch updates, the optimiser epoch catches raw-pointer updates by
+        ``srx_adam_step`` (frozen parameters such as VGG19's never repack)."""
+        dref, L = C.byref(d), _lib.lib
+        self.direct.ensure(
+            self.pack_key(weight), weight.device, True,
+            lambda: (L().srx_conv2d_packed_fwd_floats(dref), max(L().srx_conv2d_packed_bwd_floats(dref), 4), torch.float32),
+            lambda fwd, bwd, _: call('srx_conv2d_pack', dref, _p(_chk(weight.detach(), 'conv2d.weight')), _p(fwd), _p(bwd), _stream()),
+            d)
+        self.wpk_fwd, self.wpk_bwd = self.direct.fwd, self.direct.bwd
 
     def pack_wino(self, weight: Tensor, d: Conv2dDesc, need_bwd: bool) -> None:
         """The Winograd-domain weights (``srx_wino_pack``: U = G g G^T of the layer and, for its data gradient, of the
         transposed / tap-flipped layer), rebuilt when the master weight changed -- same key as ``pack``."""
-        key = self.pack_key(weight)
-        fresh = key == self.__dict__.get('_wino_key')
-        if fresh and (self.__dict__.get('wino_bwd') is not None or not need_bwd):
-            return
         dref = C.byref(d)
-        n = _lib.lib().srx_wino_packed_floats(dref)
-        w = _chk(weight.detach(), 'conv2d.weight')
-        if not fresh or self.__dict__.get('wino_fwd') is None:
-            if self.__dict__.get('wino_fwd') is None or self.wino_fwd.device != weight.device:
-                self.wino_fwd = torch.empty(n, dtype=torch.float32, device=weight.device)
-                self.wino_bwd = None
-            call('srx_wino_pack', dref, _p(w), _p(self.wino_fwd), 0, _stream())
-            if self.wino_bwd is not None:
-                call('srx_wino_pack', dref, _p(w), _p(self.wino_bwd), 1, _stream())
-        if need_bwd and self.wino_bwd is None:
-            self.wino_bwd = torch.empty(n, dtype=torch.float32, device=weight.device)
-            call('srx_wino_pack', dref, _p(w), _p(self.wino_bwd), 1, _stream())
-        self._wino_key = key
-        self._wino_desc = d
+
+        def run(fwd, bwd, bwd_only):
+            w = _chk(weight.detach(), 'conv2d.weight')
+            if not bwd_only:
+                call('srx_wino_pack', dref, _p(w), _p(fwd), 0, _stream())
+            if bwd is not None:
+                call('srx_wino_pack', dref, _p(w), _p(bwd), 1, _stream())
+
+        self.wino.ensure(self.pack_key(weight), weight.device, need_bwd,
+                         lambda: (_lib.lib().srx_wino_packed_floats(dref),) * 2 + (torch.float32,), run, d)
+        self.wino_fwd, self.wino_bwd = self.wino.fwd, self.wino.bwd
 
     def pack_bf16s(self, weight: Tensor, d: Conv2dDesc, need_bwd: bool) -> None:
-        """bf16 weight copies of a layer inside a bf16-storage stack (``srx_conv3x3_bf16s_pack``), same key as ``pack``."""
-        key = self.pack_key(weight)
-        have = self.__dict__.get('bf16s_fwd')
-        if key == self.__dict__.get('_bf16s_key') and have is not None and (self.__dict__.get('bf16s_bwd') is not None or not need_bwd):
-            return
+        """bf16 weight copies of a layer inside a bf16-storage stack (``srx_conv3x3_bf16s_pack``: one kernel writes both, so
+        adding a backward copy rewrites the forward one with the same values), same key as ``pack``."""
         dref = C.byref(d)
-        n = _lib.lib().srx_conv3x3_bf16s_packed_bytes(dref) // 2
-        if have is None or have.device != weight.device:
-            self.bf16s_fwd = torch.empty(n, dtype=torch.bfloat16, device=weight.device)
-            self.bf16s_bwd = None
-        if need_bwd and self.__dict__.get('bf16s_bwd') is None:
-            self.bf16s_bwd = torch.empty(n, dtype=torch.bfloat16, device=weight.device)
-        w = _chk(weight.detach(), 'conv2d.weight')
-        call('srx_conv3x3_bf16s_pack', dref, _p(w), _p(self.bf16s_fwd), _p(self.bf16s_bwd), _stream())
-        self._bf16s_key = key
+        self.bf16s.ensure(
+            self.pack_key(weight), weight.device, need_bwd,
+            lambda: (_lib.lib().srx_conv3x3_bf16s_packed_bytes(dref) // 2,) * 2 + (torch.bfloat16,),
+            lambda fwd, bwd, _: call('srx_conv3x3_bf16s_pack', dref, _p(_chk(weight.detach(), 'conv2d.weight')), _p(fwd), _p(bwd),
+                                     _stream()), d)
+        self.bf16s_fwd, self.bf16s_bwd = self.bf16s.fwd, self.bf16s.bwd
 
 
 def wino_forward_only_ok(st: ConvState, d: Conv2dDesc) -> bool:
@@ -727,17 +729,15 @@ class PackTable:
         every = [(c._st, c.weight) for c in self.convs if c.weight.requires_grad and not c._st.fused_only]
         # a layer is ready once it has run: it then has its direct packs (gconv / thin / row-tile kernels), its Winograd-domain
         # copies (wino.hip: such a layer needs no direct pack at all), or both (it took both paths at different sizes)
-        direct = [(st, wt) for st, wt in every if st.wpk_fwd is not None and getattr(st, 'last_desc', None) is not None]
-        wino = [(st, wt) for st, wt in every if st.__dict__.get('wino_fwd') is not None]
-        seen = {id(st) for st, _ in direct} | {id(st) for st, _ in wino}
-        if not direct or any(id(st) not in seen for st, _ in every):
+        direct = [(st, wt) for st, wt in every if st.direct.fwd is not None]
+        wino = [(st, wt) for st, wt in every if st.wino.fwd is not None]
+        if not direct or any(st.direct.fwd is None and st.wino.fwd is None for st, _ in every):
             return False
-        items = direct
-        n = len(items)
-        descs = (Conv2dDesc * n)(*[st.last_desc for st, _ in items])
+        items, n = direct, len(direct)
+        descs = (Conv2dDesc * n)(*[st.direct.desc for st, _ in items])
         arr = lambda ptrs: (C.c_void_p * n)(*ptrs)  # noqa: E731
-        w, f, b = (arr([wt.data_ptr() for _, wt in items]), arr([st.wpk_fwd.data_ptr() for st, _ in items]),
-                   arr([st.wpk_bwd.data_ptr() for st, _ in items]))
+        w, f, b = (arr([wt.data_ptr() for _, wt in items]), arr([st.direct.fwd.data_ptr() for st, _ in items]),
+                   arr([st.direct.bwd.data_ptr() for st, _ in items]))
         nbytes = _lib.lib().srx_pack_table_bytes(n + len(wino))
         host = torch.empty(nbytes, dtype=torch.uint8)
         nrec, maxn = C.c_int(0), C.c_longlong(0)
@@ -745,10 +745,10 @@ class PackTable:
         # layers that run on Winograd: their transformed weights are refreshed by the same launch
         self.wino_items = wino
         for st, wt in self.wino_items:
-            dref = C.byref(st._wino_desc)
-            call('srx_pack_table_add_wino', host.data_ptr(), C.byref(nrec), C.byref(maxn), dref, wt.data_ptr(), st.wino_fwd.data_ptr(), 0)
-            if st.wino_bwd is not None:
-                call('srx_pack_table_add_wino', host.data_ptr(), C.byref(nrec), C.byref(maxn), dref, wt.data_ptr(), st.wino_bwd.data_ptr(), 1)
+            dref = C.byref(st.wino.desc)
+            call('srx_pack_table_add_wino', host.data_ptr(), C.byref(nrec), C.byref(maxn), dref, wt.data_ptr(), st.wino.fwd.data_ptr(), 0)
+            if st.wino.bwd is not None:
+                call('srx_pack_table_add_wino', host.data_ptr(), C.byref(nrec), C.byref(maxn), dref, wt.data_ptr(), st.wino.bwd.data_ptr(), 1)
         self.table = host.to(items[0][1].device)
         self.items, self.nrec, self.maxn = items, nrec.value, maxn.value
         self.fused_sig = self._fused_signature()
@@ -757,8 +757,8 @@ class PackTable:
 
     def _fused_signature(self):
         """what decides the table's records: which convs are left out (fused dense blocks) and which carry Winograd copies"""
-        return tuple((bool(c._st.fused_only), c._st.wpk_fwd is not None, c._st.__dict__.get('wino_fwd') is not None,
-                      c._st.__dict__.get('wino_bwd') is not None) for c in self.convs)
+        return tuple((bool(c._st.fused_only), c._st.direct.fwd is not None, c._st.wino.fwd is not None, c._st.wino.bwd is not None)
+                     for c in self.convs)
 
     def run(self) -> bool:
         """False (and nothing done) until every layer is ready: the lazy per-layer path still covers that."""
@@ -773,9 +773,9 @@ class PackTable:
             return False
         call('srx_pack_table_run', self.table.data_ptr(), self.nrec, self.maxn, _stream())
         for st, wt in self.items:
-            st._key = st.pack_key(wt)
+            st.direct.stamp(st.pack_key(wt))
         for st, wt in self.wino_items:
-            st._wino_key = st.pack_key(wt)
+            st.wino.stamp(st.pack_key(wt))
         return True
 
 
@@ -1856,6 +1856,7 @@ class FoldedConv:
         self.conv, self.bn, self.prelu = conv, bn, prelu
         self._key = None
         self.st = None
+        self.pack16 = WeightPack()  # the weights of the 16-bit-native chain (csrc/c64.hip)
 
     def _sources(self):
         ts = [self.conv.weight, self.conv.bias]
@@ -1910,13 +1911,9 @@ class FoldedConv:
         n, h, w, cs = x.shape
         if cs != 64:
             raise RuntimeError(f'folded_conv: {sfx} input has {cs} channels, the layer expects 64')
-        if self.__dict__.get('_key16') != (self._key, dt):  # (keyed by the storage type: fp16 and bf16 packs differ)
-            nbytes = _lib.lib().srx_conv3x3_c64_bf16_packed_bytes(st.cout)
-            wpk = self.__dict__.get('_wpk16')
-            if wpk is None or wpk.numel() != nbytes or wpk.device != x.device:
-                wpk = self._wpk16 = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            call(f'srx_conv3x3_c64_{sfx}_pack', _p(self.w), _p(self.b), None, st.cout, st.shuffle, _p(wpk), _stream())
-            self._key16 = (self._key, dt)
+        self.pack16.ensure(  # (keyed by the storage type too: fp16 and bf16 packs differ)
+            (self._key, dt), x.device, False, lambda: (_lib.lib().srx_conv3x3_c64_bf16_packed_bytes(st.cout), 0, torch.uint8),
+            lambda fwd, bwd, _: call(f'srx_conv3x3_c64_{sfx}_pack', _p(self.w), _p(self.b), None, st.cout, st.shuffle, _p(fwd), _stream()))
         y = torch.empty(st.out_shape(n, h, w), dtype=dt, device=x.device)
         slope = 1.0 if st.act == ACT_NONE else (0.0 if st.act == ACT_RELU else st.slope)
         r = None
@@ -1924,7 +1921,7 @@ class FoldedConv:
             r = _chk16(residual, 'folded_conv.residual', dt)
             if r.shape != y.shape:
                 raise RuntimeError('folded_conv: residual must have the output shape')
-        call(f'srx_conv3x3_c64_{sfx}_fwd', n, h, w, st.cout, st.shuffle, _p(x), _p(self._wpk16), float(slope), _p(r), _p(y),
+        call(f'srx_conv3x3_c64_{sfx}_fwd', n, h, w, st.cout, st.shuffle, _p(x), _p(self.pack16.fwd), float(slope), _p(r), _p(y),
              y.shape[3], _stream())
         return y
 
@@ -2065,38 +2062,38 @@ class RDBPack:
     ``srx_rdb_pack`` launch for all blocks, re-run when any weight changed (the same staleness key as ``ConvState.pack``)."""
 
     def __init__(self):
-        self.buf = self.buf_bwd = self.table = None
-        self._key = None
-        self._has_bwd = False
+        self.pack = WeightPack()
+        self.table = None  # the masters' addresses, in device memory
         self.per_block = 0
 
     def ensure(self, states, masters, need_bwd: bool = False) -> None:
         ws = [w for row in masters for w in row]
         key = (ws[0].data_ptr(), len(ws), _pack_epoch[0], states[0][0].model_epoch[0], sum(w._version for w in ws))
-        if key == self._key and (self._has_bwd or not need_bwd):
-            return
         dev = ws[0].device
-        if self.table is None or self.table.numel() != len(ws) or self.table.device != dev:
-            self.per_block = int(_lib.lib().srx_rdb_packed_bytes())
-            self.table = torch.tensor([w.data_ptr() for w in ws], dtype=torch.int64).to(dev)
-            self.buf = torch.empty(len(states) * self.per_block, dtype=torch.uint8, device=dev)
-            self._ptrs = [w.data_ptr() for w in ws]
-        elif self._ptrs != [w.data_ptr() for w in ws]:
-            self.table.copy_(torch.tensor([w.data_ptr() for w in ws], dtype=torch.int64))
-            self._ptrs = [w.data_ptr() for w in ws]
-        call('srx_rdb_pack', _p(self.table), len(states), _p(self.buf), _stream())
-        self._has_bwd = bool(need_bwd)
-        if need_bwd:  # the transposed, tap-flipped streams of the data-gradient chain (srx_rdb_bwd)
-            if self.buf_bwd is None or self.buf_bwd.numel() != self.buf.numel() or self.buf_bwd.device != dev:
-                self.buf_bwd = torch.empty_like(self.buf)
-            call('srx_rdb_pack_bwd', _p(self.table), len(states), _p(self.buf_bwd), _stream())
-        self._key = key
+
+        def size():
+            self.per_block = self.per_block or int(_lib.lib().srx_rdb_packed_bytes())
+            return (len(states) * self.per_block,) * 2 + (torch.uint8,)
+
+        def run(fwd, bwd, bwd_only):
+            ptrs = [w.data_ptr() for w in ws]
+            if self.table is None or self.table.numel() != len(ws) or self.table.device != dev:
+                self.table = torch.tensor(ptrs, dtype=torch.int64).to(dev)
+            elif self._ptrs != ptrs:
+                self.table.copy_(torch.tensor(ptrs, dtype=torch.int64))
+            self._ptrs = ptrs
+            if not bwd_only:
+                call('srx_rdb_pack', _p(self.table), len(states), _p(fwd), _stream())
+            if bwd is not None:  # the transposed, tap-flipped streams of the data-gradient chain (srx_rdb_bwd)
+                call('srx_rdb_pack_bwd', _p(self.table), len(states), _p(bwd), _stream())
+
+        self.pack.ensure(key, dev, need_bwd, size, run)
 
     def block_ptr(self, i: int) -> int:
-        return self.buf.data_ptr() + i * self.per_block
+        return self.pack.fwd.data_ptr() + i * self.per_block
 
     def bwd_ptr(self, i: int) -> int:
-        return self.buf_bwd.data_ptr() + i * self.per_block
+        return self.pack.bwd.data_ptr() + i * self.per_block
 
 
 def rdb_fused_ok(states, wb_row, c0: int) -> bool:

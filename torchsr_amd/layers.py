@@ -63,12 +63,6 @@ class Conv2d(nn.Conv2d):
         y, part = F.conv2d(x, _w(self.weight), _w(self.bias), self._st, want_stats, self.weight, in_act, act_bwd_folded)
         return (y, part) if want_stats else y
 
-    def repack(self) -> None:
-        """Refresh the packed weight copies after an optimiser step (needs a known input shape)."""
-        st = self._st
-        if st._descs:
-            st.pack(self.weight, next(iter(st._descs.values())), force=True)
-
     def __deepcopy__(self, memo):
         new = Conv2d(self.in_channels, self.out_channels, self.kernel_size[0], self.stride[0], self.padding[0],
                      self.bias is not None, self._st.act, self._st.slope, self._st.shuffle, self._st.up)
@@ -124,11 +118,5 @@ class Marker(nn.Module):
         return x
 
 
-def repack_module(module: nn.Module) -> None:
-    for m in module.modules():
-        if isinstance(m, Conv2d):
-            m.repack()
-
-
-__all__ = ['no_weight_grad', 'Conv2d', 'BatchNorm2d', 'PReLU', 'LeakyReLU', 'Linear', 'Marker', 'repack_module', 'ACT_NONE',
+__all__ = ['no_weight_grad', 'Conv2d', 'BatchNorm2d', 'PReLU', 'LeakyReLU', 'Linear', 'Marker', 'ACT_NONE',
            'ACT_RELU', 'ACT_LRELU']

@@ -404,8 +404,7 @@ class SRGANTrainer:
 
     def _table_generations(self):
         """(re)build counters of the pack tables a captured step replays (functional.PackTable.generation)"""
-        return tuple(getattr(opt, 'pack_table', None).generation if getattr(opt, 'pack_table', None) is not None else -1
-                     for opt in (self.gen_optimizer, self.disc_optimizer))
+        return tuple(-1 if opt.pack_table is None else opt.pack_table.generation for opt in (self.gen_optimizer, self.disc_optimizer))
 
     def _end_step(self) -> None:
         if self._eager_steps > 0:
