@@ -469,6 +469,32 @@ int srx_crop_flip_u8(const void* const* imgs, const int32_t* meta, float* out_nc
 int srx_bicubic_down(const float* in_nchw, float* out_nchw, int N, int C, int H, int W, int scale, int quantize,
                      void* stream);
 
+/* ------------------------------------------ blind degradation (degrade.hip) */
+/* The first-order degradation model of BSRGAN / Real-ESRGAN around srx_bicubic_down: blur, resize, noise, JPEG
+ * ('Blind degradation').  Images are float NCHW in [0, 1] with 3 channels; per-sample parameters are DEVICE
+ * arrays, read by the kernels, which are safe for any value they find there.
+ *
+ * Each sample correlated with its own normalised Gaussian: out[y][x] = sum_ij w[i][j] in[y + i - r][x + j - r], r = ksize / 2,
+ * w[i][j] ~ exp(-v' S^-1 v / 2), v = (j - r, i - r), S = R(theta) diag(sigma_x^2, sigma_y^2) R(theta)', sum w = 1; borders are
+ * reflected (-k -> k, as F.pad(mode='reflect')).  parm: float [N][4] = {sigma_x, sigma_y, theta, unused}; ksize: int32 [N],
+ * 0 (the sample is copied) or odd in 1..21 -- any other value is clamped: <= 0 to 0, even to the next odd, > 21 to 21.
+ * Refused: C != 3, H <= 10 or W <= 10 (a 21-tap reflect needs 11 rows), out == in, N > 65535. */
+int srx_blur_aniso(const float* in_nchw, float* out_nchw, const float* parm, const int32_t* ksize, int N, int C, int H,
+                   int W, void* stream);
+/* out[n][c][p] = in[n][c][p] + sigma[n] z_c, p = y W + x.  Philox4x32-10 with counter (p, n, 0, 0) and key (seed_lo, seed_hi)
+ * gives r0..r3; u_k = ((r_k >> 8) + 0.5) 2^-24; z_0 = sqrt(-2 ln u_0) cos(2 pi u_1), z_1 = sqrt(-2 ln u_0) sin(2 pi u_1),
+ * z_2 = sqrt(-2 ln u_2) cos(2 pi u_3); gray[n] != 0: all three channels get z_0.  Stateless: the same seed gives the same bits.
+ * sigma: float [N]; gray: int32 [N]; [N][3][H][W]; quantize != 0 clamps to [0, 1] and rounds to 8 bits. */
+int srx_add_gaussian_noise(const float* in_nchw, float* out_nchw, const float* sigma, const int32_t* gray, uint32_t seed_lo,
+                           uint32_t seed_hi, int N, int H, int W, int quantize, void* stream);
+/* What a baseline JPEG codec at quality[n] (int32 [N], libjpeg's scale) does to the pixels of a 4:4:4 image: 8-bit samples,
+ * libjpeg's integer RGB -> YCbCr, orthonormal 8 x 8 DCT, the Annex K tables scaled by libjpeg's rule, rounding, the inverse
+ * transform (decoded samples unrounded), float YCbCr -> RGB, / 255, clamp.  No chroma subsampling; entropy coding is
+ * lossless and left out.  A quality outside 1..100 copies the sample.  [N][3][H][W], H and W multiples of 8 (others are
+ * refused), N <= 65535; quantize != 0 rounds the result to 8 bits. */
+int srx_jpeg_sim(const float* in_nchw, float* out_nchw, const int32_t* quality, int N, int H, int W, int quantize,
+                 void* stream);
+
 /* -------------------------------------------------------------- batch norm */
 /* nn.BatchNorm2d(C), eps 1e-5, momentum 0.1 (srgan/residual.py:65,68;
  * srgan/generator.py:49; srgan/discriminator.py:36-60).

@@ -16,6 +16,7 @@ from torch.utils.data import DataLoader, Dataset
 from torch.utils.data.distributed import DistributedSampler
 
 SUPPORTED_IMAGES = ('.jpg', '.jpeg', '.png', '.bmp')  # dataset.py:29
+DEGRADATIONS = ('bicubic', 'blind')  # how DeviceLoader makes a low-resolution train batch ('Blind degradation')
 
 
 def _image_dataset(directory: str) -> List[str]:
@@ -87,8 +88,13 @@ class DeviceLoader:
     """
 
     def __init__(self, images, device, batch_size: int, crop_size: int, upscale_factor: int, test: bool, seed: int,
-                 multiplier: int = 1, rank: int = 0, world_size: int = 1):
+                 multiplier: int = 1, rank: int = 0, world_size: int = 1, degradation: str = 'bicubic'):
         from . import _lib
+        if degradation not in DEGRADATIONS:
+            raise ValueError(f'DeviceLoader: degradation must be one of {DEGRADATIONS}, got {degradation!r}')
+        if degradation == 'blind' and (crop_size <= 10 or crop_size % upscale_factor or (crop_size // upscale_factor) % 8):
+            raise ValueError(f'DeviceLoader: blind degradation needs a crop of more than 10 pixels whose low-resolution side is '
+                             f'a multiple of 8 (JPEG blocks), got crop {crop_size} / {upscale_factor}')
         self._lib = _lib
         self.device, self.batch, self.crop, self.up, self.test = device, batch_size, crop_size, upscale_factor, test
         self.images = [self._fit(im).to(device) for im in images]          # uint8 [H][W][3]
@@ -96,6 +102,11 @@ class DeviceLoader:
         self.order = [i for _ in range(multiplier) for i in range(len(self.images))]
         self.rank, self.world = rank, world_size
         self.rng = random.Random(seed * 7919 + rank)
+        # ``blind`` train batches only: the degradation parameters and the noise seeds come from a stream of their own, so
+        # the crop / flip stream above -- and with it every high-resolution batch -- is the same in both modes
+        self.degradation = degradation
+        self.deg_rng = random.Random(seed * 15485863 + rank + 982451653)
+        self.last_degradation = None
         self.epoch = 0
 
     def _fit(self, im: torch.Tensor) -> torch.Tensor:
@@ -122,27 +133,83 @@ class DeviceLoader:
         # one batch shape, so the last partial TRAIN batch is dropped; the eager test pass keeps it (:345-360)
         return -(-n // self.batch) if self.test else n // self.batch
 
-    def __iter__(self):
+    def _draw_meta(self, idx):
+        """``srx_crop_flip_u8``'s rows {H, W, top, left, hflip, vflip} of the samples ``idx``, drawn from the crop / flip stream."""
+        meta = []
+        for i in idx:
+            h, w = self.sizes[i]
+            top, left = self.rng.randint(0, h - self.crop), self.rng.randint(0, w - self.crop)
+            hflip = 0 if self.test else int(self.rng.random() < 0.5)
+            vflip = 0 if self.test else int(self.rng.random() < 0.5)
+            meta.append([h, w, top, left, hflip, vflip])
+        return meta
+
+    def _draw_degradation(self, n: int) -> dict:
+        """The ``blind`` parameters of a batch of ``n`` samples, drawn on the host from the degradation stream: the first-order
+        recipe of Real-ESRGAN without its sinc and Poisson branches.  Numpy arrays, laid out as the kernels read them:
+        ``parm`` float32 [n][4] = {sigma_x, sigma_y, theta, 0}, ``ksize`` int32 [n], ``sigma_n`` float32 [n], ``gray`` int32 [n],
+        ``quality`` int32 [n]; and ``seed``, the batch's 64-bit noise seed."""
+        import math
+        import numpy as np
+        rng = self.deg_rng
+        parm, ksize = np.zeros((n, 4), dtype=np.float32), np.zeros(n, dtype=np.int32)
+        sigma_n, gray, quality = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        for i in range(n):
+            ksize[i] = 2 * rng.randint(3, 10) + 1                       # odd, 7 .. 21
+            if rng.random() < 0.5:                                      # isotropic
+                sx = sy = rng.uniform(0.2, 3.0)
+                theta = 0.0
+            else:
+                sx, sy = rng.uniform(0.2, 3.0), rng.uniform(0.2, 3.0)
+                theta = -math.pi + 2.0 * math.pi * rng.random()         # [-pi, pi)
+            parm[i, :3] = sx, sy, theta
+            sigma_n[i] = rng.uniform(1.0, 30.0) / 255.0
+            gray[i] = int(rng.random() < 0.4)
+            quality[i] = rng.randint(30, 95)
+        return {'parm': parm, 'ksize': ksize, 'sigma_n': sigma_n, 'gray': gray, 'quality': quality, 'seed': rng.getrandbits(64)}
+
+    def _plan(self):
+        """Host side of one epoch: per batch the sample indices, the crop / flip rows and -- ``blind`` train batches only, and
+        after the rows, from the other stream -- the degradation parameters (else None)."""
         order = list(self.order)
         if not self.test:
             random.Random(self.epoch * 104729 + 17).shuffle(order)  # same permutation on every rank
         self.epoch += 1
         order = self._shard(order)
-        call, dev = self._lib.call, self.device
         for b in range(len(self)):
             idx = order[b * self.batch:(b + 1) * self.batch]
-            meta = []
-            for i in idx:
-                h, w = self.sizes[i]
-                top, left = self.rng.randint(0, h - self.crop), self.rng.randint(0, w - self.crop)
-                hflip = 0 if self.test else int(self.rng.random() < 0.5)
-                vflip = 0 if self.test else int(self.rng.random() < 0.5)
-                meta.append([h, w, top, left, hflip, vflip])
+            meta = self._draw_meta(idx)
+            blind = self.degradation == 'blind' and not self.test   # the test set stays bicubic: PSNR comparable across runs
+            yield idx, meta, self._draw_degradation(len(idx)) if blind else None
+
+    def _degrade(self, hr, deg, stream):
+        """``blind``: blur -> bicubic x1/scale (unquantised) -> Gaussian noise -> 8 bits -> JPEG -> 8 bits."""
+        call, dev, n = self._lib.call, self.device, hr.shape[0]
+        lc = self.crop // self.up
+        on_dev = {k: torch.from_numpy(deg[k]).to(dev) for k in ('parm', 'ksize', 'sigma_n', 'gray', 'quality')}
+        blurred = torch.empty_like(hr)
+        call('srx_blur_aniso', hr.data_ptr(), blurred.data_ptr(), on_dev['parm'].data_ptr(), on_dev['ksize'].data_ptr(),
+             n, 3, self.crop, self.crop, stream)
+        lr = torch.empty((n, 3, lc, lc), dtype=torch.float32, device=dev)
+        call('srx_bicubic_down', blurred.data_ptr(), lr.data_ptr(), n, 3, self.crop, self.crop, self.up, 0, stream)
+        noisy = torch.empty_like(lr)
+        call('srx_add_gaussian_noise', lr.data_ptr(), noisy.data_ptr(), on_dev['sigma_n'].data_ptr(), on_dev['gray'].data_ptr(),
+             deg['seed'] & 0xFFFFFFFF, deg['seed'] >> 32, n, lc, lc, 1, stream)
+        call('srx_jpeg_sim', noisy.data_ptr(), lr.data_ptr(), on_dev['quality'].data_ptr(), n, lc, lc, 1, stream)
+        return lr
+
+    def __iter__(self):
+        call, dev = self._lib.call, self.device
+        for idx, meta, deg in self._plan():
             ptrs = torch.tensor([self.images[i].data_ptr() for i in idx], dtype=torch.int64).to(dev)
             meta_t = torch.tensor(meta, dtype=torch.int32).to(dev)
             stream = torch.cuda.current_stream().cuda_stream
             hr = torch.empty((len(idx), 3, self.crop, self.crop), dtype=torch.float32, device=dev)
             call('srx_crop_flip_u8', ptrs.data_ptr(), meta_t.data_ptr(), hr.data_ptr(), len(idx), self.crop, stream)
+            if deg is not None:
+                self.last_degradation = deg
+                yield self._degrade(hr, deg, stream), hr
+                continue
             lc = self.crop // self.up
             lr = torch.empty((len(idx), 3, lc, lc), dtype=torch.float32, device=dev)
             call('srx_bicubic_down', hr.data_ptr(), lr.data_ptr(), len(idx), 3, self.crop, self.crop, self.up, 1, stream)
@@ -162,9 +229,10 @@ def _decode(path: str) -> torch.Tensor:
 
 def initialize_device_datasets(train_directory: str, device, batch_size: int = 64, crop_size: int = 96,
                                upscale_factor: int = 4, dataset_multiplier: int = 1, distributed: bool = False,
-                               seed: int = 0, rank: int = 0, world_size: int = 1):
+                               seed: int = 0, rank: int = 0, world_size: int = 1, degradation: str = 'bicubic'):
     """``initialize_datasets`` with the augmentation on the device (``--device-data``).  ``synthetic:N`` draws N
-    seeded random 2*crop x 2*crop images."""
+    seeded random 2*crop x 2*crop images.  ``degradation='blind'`` degrades the TRAIN batches' low-resolution side with blur,
+    noise and JPEG (``--degradation``); the test loader stays bicubic."""
     if train_directory.startswith('synthetic:'):
         n = int(train_directory.split(':')[1])
         g = torch.Generator().manual_seed(seed)
@@ -180,7 +248,7 @@ def initialize_device_datasets(train_directory: str, device, batch_size: int = 6
     if not distributed:
         rank, world_size = 0, 1
     train = DeviceLoader(images[n_test:] or images, device, batch_size, crop_size, upscale_factor, False, seed,
-                         dataset_multiplier, rank, world_size)
+                         dataset_multiplier, rank, world_size, degradation=degradation)
     # dataset.py:343-360: the test set is multiplied like the train set, sharded over the ranks, nothing dropped
     test = DeviceLoader(images[:n_test], device, batch_size, crop_size, upscale_factor, True, seed + 1,
                         dataset_multiplier, rank, world_size)

@@ -113,6 +113,12 @@ def parse_args(argv=None) -> Namespace:
     train.add_argument('--no-graphs', action='store_true', help='run the step eagerly instead of as a hipGraph')
     train.add_argument('--device-data', action='store_true',
                        help='keep the decoded images in HBM and crop / flip / bicubic-downsample on the GPU')
+    train.add_argument('--degradation', type=str, default='bicubic', choices=('bicubic', 'blind'),
+                       help='how a low-resolution training image is made from its crop.  bicubic: the antialiased bicubic x1/4 '
+                            'alone.  blind: anisotropic Gaussian blur, bicubic x1/4, Gaussian noise and JPEG compression with '
+                            'parameters drawn per sample (the first-order model of BSRGAN / Real-ESRGAN), all on the GPU.  '
+                            'blind needs --device-data: the host DataLoader path has no blind degradation.  The per-epoch '
+                            'test set stays bicubic')
     train.add_argument('--clip-grad-norm', type=positive_float, default=None, metavar='FLOAT',
                        help='clip the global l2 norm of each model\'s gradient to FLOAT before its Adam step '
                             '(torch.nn.utils.clip_grad_norm_, computed on the GPU inside the captured step; default: off)')
@@ -135,7 +141,10 @@ def parse_args(argv=None) -> Namespace:
                            'x4; its result is then resampled once, on the GPU, with the antialiased bicubic filter the '
                            'training data was reduced with (2: a 4K picture from a 1080p one).  Combines with every '
                            '--precision, --self-ensemble and either --model')
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.function == 'train' and args.degradation == 'blind' and not args.device_data:
+        parser.error('--degradation blind needs --device-data (the host DataLoader path has no blind degradation)')
+    return args
 
 
 def main(argv=None) -> None:
@@ -182,7 +191,8 @@ def main(argv=None) -> None:
         train_loader, test_loader, train_len, test_len = initialize_device_datasets(
             args.train_dir, device, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=4,
             dataset_multiplier=args.dataset_multiplier, distributed=distributed, seed=args.seed,
-            rank=max(int(args.rank), 0) if distributed else 0, world_size=int(args.world_size) if distributed else 1)
+            rank=max(int(args.rank), 0) if distributed else 0, world_size=int(args.world_size) if distributed else 1,
+            degradation=args.degradation)
     else:
         train_loader, test_loader, train_len, test_len = initialize_datasets(
             args.train_dir, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=4,
