@@ -481,6 +481,16 @@ int srx_bicubic_down(const float* in_nchw, float* out_nchw, int N, int C, int H,
  * Refused: C != 3, H <= 10 or W <= 10 (a 21-tap reflect needs 11 rows), out == in, N > 65535. */
 int srx_blur_aniso(const float* in_nchw, float* out_nchw, const float* parm, const int32_t* ksize, int N, int C, int H,
                    int W, void* stream);
+/* Each sample correlated with a kernel given as an operand -- the second-order model's sinc, generalised Gaussian and plateau
+ * kernels ('Second-order degradation'): out[n][c][y][x] = sum_ij w_n[i][j] in[n][c][y + i - r][x + j - r], r = ks / 2,
+ * borders reflected as srx_blur_aniso's.  weights: DEVICE float [N][21][21]; sample n's ks x ks kernel sits centred in its slot
+ * (rows and columns 10 - r .. 10 + r) and only that window is read.  The weights are used as given: neither normalised nor
+ * clamped (sinc weights are negative in places).  ksize: int32 [N], clamped like srx_blur_aniso's; 0 copies the sample.
+ * quantize != 0 clamps the result (a copied sample too) to [0, 1] and rounds it to 8 bits as srx_add_gaussian_noise does.
+ * fmas in ascending (i, j), no atomics, no device state: the same bits from every call.
+ * Refused: null pointers, C != 3, H <= 10 or W <= 10, out == in, N outside 1..65535. */
+int srx_filter2d(const float* in_nchw, float* out_nchw, const float* weights, const int32_t* ksize, int N, int C, int H, int W,
+                 int quantize, void* stream);
 /* out[n][c][p] = in[n][c][p] + sigma[n] z_c, p = y W + x.  Philox4x32-10 with counter (p, n, 0, 0) and key (seed_lo, seed_hi)
  * gives r0..r3; u_k = ((r_k >> 8) + 0.5) 2^-24; z_0 = sqrt(-2 ln u_0) cos(2 pi u_1), z_1 = sqrt(-2 ln u_0) sin(2 pi u_1),
  * z_2 = sqrt(-2 ln u_2) cos(2 pi u_3); gray[n] != 0: all three channels get z_0.  Stateless: the same seed gives the same bits.

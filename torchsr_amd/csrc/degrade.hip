@@ -1,5 +1,6 @@
 // Blind degradation of the training data on the device ('Blind degradation'): the first-order model of
-// BSRGAN / Real-ESRGAN -- blur, resize, sensor noise, JPEG -- around augment.hip's srx_bicubic_down.  Three kernels over a
+// BSRGAN / Real-ESRGAN -- blur, resize, sensor noise, JPEG -- around augment.hip's srx_bicubic_down, and the table-driven
+// filter of its second-order model ('Second-order degradation').  Four kernels over a
 // batch of float NCHW images in [0, 1]; every per-sample parameter is read on the device, so each kernel is safe for any
 // value it finds there (a kernel size outside the legal set is clamped into it, a quality outside 1..100 passes through).
 #include "srx_common.h"
@@ -90,6 +91,67 @@ __global__ __launch_bounds__(256) void blur_aniso_kernel(const float* __restrict
     const float acc[4] = {a0, a1, a2, a3};
     for (int e = 0; e < 4; ++e)
       if (tx0 + lx + e < W) dst[(size_t)y * W + tx0 + lx + e] = acc[e];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ per-sample 2-D filter
+// out[n][c][y][x] = sum_ij w_n[i][j] in[n][c][y + i - r][x + j - r] with the weights as an operand: sample n's ks x ks kernel sits
+// centred in its 21 x 21 slot of ``weights`` and is used as given (sinc kernels have negative lobes), nothing outside that
+// window is read.  blur_aniso_kernel's tiling and order of fmas; the weight phase is a load.  grid (tiles, C, N), 256 threads.
+__device__ __forceinline__ float filter_quantize(float v) { return rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f) * (1.0f / 255.0f); }
+
+__global__ __launch_bounds__(256) void filter2d_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                       const float* __restrict__ weights, const int* __restrict__ ksize,
+                                                       int C, int H, int W, int tiles_x, int quantize) {
+  __shared__ float wl[kBlurMaxK * kBlurMaxK];
+  __shared__ float tile[kBlurPitch * kBlurPitch];
+  const int n = blockIdx.z, c = blockIdx.y, t = threadIdx.x;
+  const int ty0 = (int)(blockIdx.x / tiles_x) * kBlurTile, tx0 = (int)(blockIdx.x % tiles_x) * kBlurTile;
+  const int ks = blur_legal_ksize(ksize[n]), r = ks >> 1;
+  const float* src = in + ((size_t)n * C + c) * H * W;
+  float* dst = out + ((size_t)n * C + c) * H * W;
+  const int lx = (t & 7) * 4, ly = t >> 3;
+  const int y = ty0 + ly;
+  if (ks == 0) {  // the sample passes through: bit for bit, or rounded to 8 bits
+    if (y < H)
+      for (int e = 0; e < 4; ++e)
+        if (tx0 + lx + e < W) {
+          const float v = src[(size_t)y * W + tx0 + lx + e];
+          dst[(size_t)y * W + tx0 + lx + e] = quantize ? filter_quantize(v) : v;
+        }
+    return;
+  }
+  // the centred ks x ks window of the sample's slot, once per workgroup
+  const float* slot = weights + (size_t)n * (kBlurMaxK * kBlurMaxK) + (kBlurMaxK / 2 - r) * (kBlurMaxK + 1);
+  for (int i = t; i < ks * ks; i += 256) {
+    const int ti = i / ks, tj = i - ti * ks;
+    wl[i] = slot[ti * kBlurMaxK + tj];
+  }
+  // the tile and its halo of r pixels, reflected at the plane's borders
+  const int ext = kBlurTile + 2 * r;
+  for (int i = t; i < ext * ext; i += 256) {
+    const int py = i / ext, px = i - py * ext;
+    tile[py * kBlurPitch + px] = src[(size_t)blur_reflect(ty0 - r + py, H) * W + blur_reflect(tx0 - r + px, W)];
+  }
+  __syncthreads();
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  for (int i = 0; i < ks; ++i) {
+    const float* row = tile + (ly + i) * kBlurPitch + lx;  // columns lx .. lx + ks + 2 <= ext - 1
+    const float* wr = wl + i * ks;
+    float v0 = row[0], v1 = row[1], v2 = row[2];
+    for (int j = 0; j < ks; ++j) {
+      const float v3 = row[j + 3], w = wr[j];
+      a0 = fmaf(w, v0, a0);
+      a1 = fmaf(w, v1, a1);
+      a2 = fmaf(w, v2, a2);
+      a3 = fmaf(w, v3, a3);
+      v0 = v1, v1 = v2, v2 = v3;
+    }
+  }
+  if (y < H) {
+    const float acc[4] = {a0, a1, a2, a3};
+    for (int e = 0; e < 4; ++e)
+      if (tx0 + lx + e < W) dst[(size_t)y * W + tx0 + lx + e] = quantize ? filter_quantize(acc[e]) : acc[e];
   }
 }
 
@@ -261,6 +323,21 @@ extern "C" int srx_blur_aniso(const float* in_nchw, float* out_nchw, const float
   hipLaunchKernelGGL(blur_aniso_kernel, dim3((unsigned)tiles, C, N), dim3(256), 0, srx_stream(stream), in_nchw, out_nchw,
                      parm, ksize, C, H, W, (int)tiles_x);
   SRX_CHECK_LAUNCH("blur_aniso_kernel");
+  return SRX_OK;
+}
+
+extern "C" int srx_filter2d(const float* in_nchw, float* out_nchw, const float* weights, const int32_t* ksize, int N, int C,
+                            int H, int W, int quantize, void* stream) {
+  SRX_REQUIRE(in_nchw && out_nchw && weights && ksize, "filter2d: null pointer");
+  SRX_REQUIRE(in_nchw != out_nchw, "filter2d: the output must not be the input");
+  SRX_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0, "filter2d: bad shape");
+  SRX_REQUIRE(C == 3, "filter2d: C = %d, the images have 3 channels", C);
+  SRX_REQUIRE(H > 10 && W > 10, "filter2d: %d x %d planes: a 21-tap reflect needs 11 rows and columns", H, W);
+  const int64_t tiles_x = srx_cdiv(W, kBlurTile), tiles = tiles_x * srx_cdiv(H, kBlurTile);
+  SRX_REQUIRE(tiles <= 0x7fffffff && (int64_t)H * W <= 0x7fffffff, "filter2d: planes too large");
+  hipLaunchKernelGGL(filter2d_kernel, dim3((unsigned)tiles, C, N), dim3(256), 0, srx_stream(stream), in_nchw, out_nchw,
+                     weights, ksize, C, H, W, (int)tiles_x, quantize);
+  SRX_CHECK_LAUNCH("filter2d_kernel");
   return SRX_OK;
 }
 

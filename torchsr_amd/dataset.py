@@ -16,7 +16,11 @@ from torch.utils.data import DataLoader, Dataset
 from torch.utils.data.distributed import DistributedSampler
 
 SUPPORTED_IMAGES = ('.jpg', '.jpeg', '.png', '.bmp')  # dataset.py:29
-DEGRADATIONS = ('bicubic', 'blind')  # how DeviceLoader makes a low-resolution train batch ('Blind degradation')
+# how DeviceLoader makes a low-resolution train batch ('Blind degradation' and 'Second-order degradation')
+DEGRADATIONS = ('bicubic', 'blind', 'blind2')
+BLIND2_KINDS = ('iso', 'aniso', 'generalized-iso', 'generalized-aniso', 'plateau-iso', 'plateau-aniso')
+BLIND2_KIND_CDF = (0.45, 0.70, 0.82, 0.85, 0.97, 1.0)  # probabilities 0.45, 0.25, 0.12, 0.03, 0.12, 0.03
+BLIND2_MODES = ('area', 'bilinear', 'bicubic')
 
 
 def _image_dataset(directory: str) -> List[str]:
@@ -92,9 +96,17 @@ class DeviceLoader:
         from . import _lib
         if degradation not in DEGRADATIONS:
             raise ValueError(f'DeviceLoader: degradation must be one of {DEGRADATIONS}, got {degradation!r}')
-        if degradation == 'blind' and (crop_size <= 10 or crop_size % upscale_factor or (crop_size // upscale_factor) % 8):
+        if degradation in ('blind', 'blind2') and (crop_size <= 10 or crop_size % upscale_factor or (crop_size // upscale_factor) % 8):
             raise ValueError(f'DeviceLoader: blind degradation needs a crop of more than 10 pixels whose low-resolution side is '
                              f'a multiple of 8 (JPEG blocks), got crop {crop_size} / {upscale_factor}')
+        if degradation == 'blind2':
+            # the sizes _draw_degradation2 can draw: the final filter needs more than 10 low-resolution rows, and no resize may
+            # reduce by more than 16:1 (functional.resize) -- the largest first size over the smallest second one
+            lc = crop_size // upscale_factor
+            s1_max, s2_min = 8 * int(1.5 * crop_size / 8 + 0.5), max(16, 8 * int(0.3 * lc / 8 + 0.5))
+            if lc <= 10 or s1_max > 16 * s2_min:
+                raise ValueError(f'DeviceLoader: blind2 degradation needs a low-resolution side of more than 10 pixels and resizes of '
+                                 f'at most 16:1; crop {crop_size} / {upscale_factor} can draw {s1_max} -> {s2_min}')
         self._lib = _lib
         self.device, self.batch, self.crop, self.up, self.test = device, batch_size, crop_size, upscale_factor, test
         self.images = [self._fit(im).to(device) for im in images]          # uint8 [H][W][3]
@@ -102,7 +114,7 @@ class DeviceLoader:
         self.order = [i for _ in range(multiplier) for i in range(len(self.images))]
         self.rank, self.world = rank, world_size
         self.rng = random.Random(seed * 7919 + rank)
-        # ``blind`` train batches only: the degradation parameters and the noise seeds come from a stream of their own, so
+        # ``blind`` / ``blind2`` train batches only: the degradation parameters and the noise seeds come from a stream of their own, so
         # the crop / flip stream above -- and with it every high-resolution batch -- is the same in both modes
         self.degradation = degradation
         self.deg_rng = random.Random(seed * 15485863 + rank + 982451653)
@@ -168,9 +180,96 @@ class DeviceLoader:
             quality[i] = rng.randint(30, 95)
         return {'parm': parm, 'ksize': ksize, 'sigma_n': sigma_n, 'gray': gray, 'quality': quality, 'seed': rng.getrandbits(64)}
 
+    def _draw_kernel(self, sigma_hi: float):
+        """One blur kernel of the second-order recipe from the degradation stream: ``(kind, ksize, weights)``, the weights
+        float64 [ksize][ksize].  Draw order: the size; one uniform (< 0.1: sinc, then its cutoff); else one uniform for the
+        kind, then sigma_x, for the anisotropic kinds sigma_y and theta, for the generalised and plateau kinds beta."""
+        import math
+        from .degradation import kernel_weights
+        rng = self.deg_rng
+        ks = 2 * rng.randint(3, 10) + 1                                 # odd, 7 .. 21
+        if rng.random() < 0.1:
+            omega = rng.uniform(math.pi / 3 if ks < 13 else math.pi / 5, math.pi)
+            return 'sinc', ks, kernel_weights('sinc', ks, omega_c=omega)
+        u = rng.random()
+        kind = BLIND2_KINDS[next(i for i, c in enumerate(BLIND2_KIND_CDF) if u < c)]
+        sx = sy = rng.uniform(0.2, sigma_hi)
+        theta = 0.0
+        if kind.endswith('aniso'):
+            sy = rng.uniform(0.2, sigma_hi)
+            theta = -math.pi + 2.0 * math.pi * rng.random()             # [-pi, pi)
+        if kind.startswith('generalized'):
+            return kind, ks, kernel_weights('generalized', ks, sx, sy, theta, beta=rng.uniform(0.5, 4.0))
+        if kind.startswith('plateau'):
+            return kind, ks, kernel_weights('plateau', ks, sx, sy, theta, beta=rng.uniform(1.0, 2.0))
+        return kind, ks, kernel_weights('gauss', ks, sx, sy, theta)
+
+    def _draw_degradation2(self, n: int) -> dict:
+        """The ``blind2`` parameters of a batch of ``n`` samples, drawn on the host from the degradation stream: the second-order
+        recipe of Real-ESRGAN (x4plus options) without its Poisson branch.  One fixed order.  Per BATCH first, so that the
+        batch stays rectangular: the first resize (one uniform for up / down / keep, the factor unless kept, the mode), the
+        second resize likewise, the final resize's mode, the final order.  Then per SAMPLE: the first kernel
+        (``_draw_kernel(3.0)``), sigma, grey flag and JPEG quality of the first pass; one uniform (< 0.2: no second blur), else
+        the second kernel (``_draw_kernel(1.5)``); sigma and grey flag of the second pass; one uniform (< 0.8: the final sinc,
+        then its size and cutoff, else the pulse); the final JPEG quality.  Last the two 64-bit noise seeds.
+
+        Numpy arrays, laid out as the kernels read them: ``weights`` float32 [3][n][21][21] (K1, K2, K3 of ``srx_filter2d``),
+        ``ksize`` int32 [3][n] (0: no filter), ``sigma_n`` float32 [2][n], ``gray`` int32 [2][n], ``quality`` int32 [2][n]; and
+        ``sizes`` (S1, S2, crop / scale), ``modes`` (three of ``BLIND2_MODES``), ``order`` ('A' or 'B'), ``seed1``, ``seed2``,
+        ``kinds`` (three lists of names, what each kernel is)."""
+        import math
+        import numpy as np
+        from .degradation import KERNEL_SLOT, kernel_slot, kernel_weights
+        rng = self.deg_rng
+        lc = self.crop // self.up
+
+        def factor(p_up, p_down, up_hi, down_lo):
+            u = rng.random()
+            if u < p_up:
+                return rng.uniform(1.0, up_hi)
+            return rng.uniform(down_lo, 1.0) if u < p_up + p_down else 1.0
+
+        s1 = factor(0.2, 0.7, 1.5, 0.15)
+        mode1 = BLIND2_MODES[rng.randrange(3)]
+        s2 = factor(0.3, 0.4, 1.2, 0.3)
+        mode2 = BLIND2_MODES[rng.randrange(3)]
+        mode3 = BLIND2_MODES[rng.randrange(3)]
+        order = 'A' if rng.random() < 0.5 else 'B'
+        # multiples of 8: srx_jpeg_sim takes whole blocks (Real-ESRGAN pads instead)
+        sizes = (max(16, 8 * int(self.crop * s1 / 8 + 0.5)), max(16, 8 * int(lc * s2 / 8 + 0.5)), lc)
+        weights, ksize = np.zeros((3, n, KERNEL_SLOT, KERNEL_SLOT), dtype=np.float32), np.zeros((3, n), dtype=np.int32)
+        sigma_n, gray, quality = np.zeros((2, n), dtype=np.float32), np.zeros((2, n), dtype=np.int32), np.zeros((2, n), dtype=np.int32)
+        kinds = [[], [], []]
+
+        def put(stage, i, kind, ks, w):
+            kinds[stage].append(kind)
+            ksize[stage, i] = ks
+            kernel_slot(w, out=weights[stage, i])
+
+        for i in range(n):
+            put(0, i, *self._draw_kernel(3.0))
+            sigma_n[0, i] = rng.uniform(1.0, 30.0) / 255.0
+            gray[0, i] = int(rng.random() < 0.4)
+            quality[0, i] = rng.randint(30, 95)
+            if rng.random() < 0.2:
+                put(1, i, 'skip', 0, None)
+            else:
+                put(1, i, *self._draw_kernel(1.5))
+            sigma_n[1, i] = rng.uniform(1.0, 25.0) / 255.0
+            gray[1, i] = int(rng.random() < 0.4)
+            if rng.random() < 0.8:
+                ks = 2 * rng.randint(3, 10) + 1
+                put(2, i, 'sinc', ks, kernel_weights('sinc', ks, omega_c=rng.uniform(math.pi / 3, math.pi)))
+            else:
+                put(2, i, 'pulse', 0, None)
+            quality[1, i] = rng.randint(30, 95)
+        return {'weights': weights, 'ksize': ksize, 'sigma_n': sigma_n, 'gray': gray, 'quality': quality, 'sizes': sizes,
+                'modes': (mode1, mode2, mode3), 'order': order, 'seed1': rng.getrandbits(64), 'seed2': rng.getrandbits(64),
+                'kinds': kinds}
+
     def _plan(self):
-        """Host side of one epoch: per batch the sample indices, the crop / flip rows and -- ``blind`` train batches only, and
-        after the rows, from the other stream -- the degradation parameters (else None)."""
+        """Host side of one epoch: per batch the sample indices, the crop / flip rows and -- ``blind`` and ``blind2`` train batches
+        only, and after the rows, from the other stream -- the degradation parameters (else None)."""
         order = list(self.order)
         if not self.test:
             random.Random(self.epoch * 104729 + 17).shuffle(order)  # same permutation on every rank
@@ -180,7 +279,8 @@ class DeviceLoader:
             idx = order[b * self.batch:(b + 1) * self.batch]
             meta = self._draw_meta(idx)
             blind = self.degradation == 'blind' and not self.test   # the test set stays bicubic: PSNR comparable across runs
-            yield idx, meta, self._draw_degradation(len(idx)) if blind else None
+            blind2 = self.degradation == 'blind2' and not self.test
+            yield idx, meta, self._draw_degradation(len(idx)) if blind else self._draw_degradation2(len(idx)) if blind2 else None
 
     def _degrade(self, hr, deg, stream):
         """``blind``: blur -> bicubic x1/scale (unquantised) -> Gaussian noise -> 8 bits -> JPEG -> 8 bits."""
@@ -198,6 +298,39 @@ class DeviceLoader:
         call('srx_jpeg_sim', noisy.data_ptr(), lr.data_ptr(), on_dev['quality'].data_ptr(), n, lc, lc, 1, stream)
         return lr
 
+    def _degrade2(self, hr, deg, stream):
+        """``blind2``: filter -> resize -> noise -> JPEG, twice, the second JPEG and the final sinc filter around the resize to
+        the low-resolution size in either order ('Second-order degradation')."""
+        from . import functional as F
+        call, dev, n = self._lib.call, self.device, hr.shape[0]
+        weights = torch.from_numpy(deg['weights']).to(dev)  # the three tables in one copy
+        ksize, sigma_n, gray, quality = (torch.from_numpy(deg[k]).to(dev) for k in ('ksize', 'sigma_n', 'gray', 'quality'))
+        (s1, s2, lc), modes = deg['sizes'], deg['modes']
+
+        def filt(x, stage, quantize):
+            out = torch.empty_like(x)
+            call('srx_filter2d', x.data_ptr(), out.data_ptr(), weights[stage].data_ptr(), ksize[stage].data_ptr(), n, 3,
+                 x.shape[2], x.shape[3], quantize, stream)
+            return out
+
+        def noise(x, stage, seed):
+            out = torch.empty_like(x)
+            call('srx_add_gaussian_noise', x.data_ptr(), out.data_ptr(), sigma_n[stage].data_ptr(), gray[stage].data_ptr(),
+                 seed & 0xFFFFFFFF, seed >> 32, n, x.shape[2], x.shape[3], 1, stream)
+            return out
+
+        def jpeg(x, stage):
+            out = torch.empty_like(x)
+            call('srx_jpeg_sim', x.data_ptr(), out.data_ptr(), quality[stage].data_ptr(), n, x.shape[2], x.shape[3], 1, stream)
+            return out
+
+        with torch.no_grad():
+            x = jpeg(noise(F.resize(filt(hr, 0, 0), (s1, s1), modes[0]), 0, deg['seed1']), 0)
+            x = noise(F.resize(filt(x, 1, 0), (s2, s2), modes[1]), 1, deg['seed2'])
+            if deg['order'] == 'A':
+                return jpeg(filt(F.resize(x, (lc, lc), modes[2]), 2, 0), 1)
+            return filt(F.resize(jpeg(x, 1), (lc, lc), modes[2]), 2, 1)
+
     def __iter__(self):
         call, dev = self._lib.call, self.device
         for idx, meta, deg in self._plan():
@@ -208,7 +341,7 @@ class DeviceLoader:
             call('srx_crop_flip_u8', ptrs.data_ptr(), meta_t.data_ptr(), hr.data_ptr(), len(idx), self.crop, stream)
             if deg is not None:
                 self.last_degradation = deg
-                yield self._degrade(hr, deg, stream), hr
+                yield (self._degrade2 if self.degradation == 'blind2' else self._degrade)(hr, deg, stream), hr
                 continue
             lc = self.crop // self.up
             lr = torch.empty((len(idx), 3, lc, lc), dtype=torch.float32, device=dev)
@@ -232,7 +365,7 @@ def initialize_device_datasets(train_directory: str, device, batch_size: int = 6
                                seed: int = 0, rank: int = 0, world_size: int = 1, degradation: str = 'bicubic'):
     """``initialize_datasets`` with the augmentation on the device (``--device-data``).  ``synthetic:N`` draws N
     seeded random 2*crop x 2*crop images.  ``degradation='blind'`` degrades the TRAIN batches' low-resolution side with blur,
-    noise and JPEG (``--degradation``); the test loader stays bicubic."""
+    noise and JPEG (``--degradation``), ``'blind2'`` with the second-order recipe; the test loader stays bicubic."""
     if train_directory.startswith('synthetic:'):
         n = int(train_directory.split(':')[1])
         g = torch.Generator().manual_seed(seed)

@@ -570,6 +570,113 @@ def resize_bicubic_aa(x: Tensor, size: Tuple[int, int], out: Optional[Tensor] = 
     return out
 
 
+RESIZE_MODES = ('area', 'bilinear', 'bicubic')
+
+
+def resize_tables(n_in: int, n_out: int, mode: str, dtype='float32'):
+    """``(start, weight, K)`` of one axis, in ``resample_tables``' format, of the three resizes Real-ESRGAN's degradation draws
+    from: ``F.interpolate(mode=..., align_corners=False, antialias=False)`` from ``n_in`` to ``n_out`` samples.  With
+    ``src = (i + 0.5) * n_in / n_out - 0.5``:
+
+    ``'area'`` (adaptive average pooling): taps ``lo <= j < hi``, ``lo = i * n_in // n_out``, ``hi = ceil((i + 1) * n_in /
+    n_out)`` in integer arithmetic, each weighted ``1 / (hi - lo)``.
+    ``'bilinear'``: ``src = max(src, 0)``, ``i0 = min(floor(src), n_in - 1)``, taps ``i0, i0 + 1`` weighted ``1 - l, l`` with
+    ``l = src - i0``; the resampler's own ``min(start + t, n_in - 1)`` is the upper clamp.
+    ``'bicubic'``: Keys with a = -0.75 (torch's value; ``resample_tables`` has PIL's -0.5) on the taps ``floor(src) - 1 .. + 2``,
+    each index clamped to ``[0, n_in - 1]``; ``start`` is the first clamped index and weights whose clamped indices coincide
+    are added into one tap (the resampler clamps at the upper border only).
+
+    Built in fp64 with numpy and rounded once to ``dtype``.  ``n_in == n_out`` is the identity in every mode."""
+    import numpy as np
+    for name, v in (('n_in', n_in), ('n_out', n_out)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f'resize_tables: {name} must be a positive int, got {v!r}')
+    if mode not in RESIZE_MODES:
+        raise ValueError(f'resize_tables: mode must be one of {RESIZE_MODES}, got {mode!r}')
+    if n_in > RESAMPLE_MAX_REDUCTION * n_out:
+        raise ValueError(f'resize_tables: {n_in} -> {n_out} reduces by more than {RESAMPLE_MAX_REDUCTION}:1')
+    i = np.arange(n_out, dtype=np.int64)
+    src = (i + 0.5) * (n_in / n_out) - 0.5
+    if mode == 'area':
+        start = (i * n_in) // n_out
+        count = -((-(i + 1) * n_in) // n_out) - start
+        k = int(count.max())
+        w = np.where(np.arange(k)[None, :] < count[:, None], 1.0 / count[:, None], 0.0)
+    elif mode == 'bilinear':
+        src = np.maximum(src, 0.0)
+        start = np.minimum(np.floor(src).astype(np.int64), n_in - 1)
+        lam = src - start
+        k, w = 2, np.stack([1.0 - lam, lam], axis=1)
+    else:
+        a = -0.75
+        f = np.floor(src)
+        t = src - f
+        inner = lambda x: ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0      # noqa: E731  |x| <= 1
+        outer = lambda x: ((a * x - 5.0 * a) * x + 8.0 * a) * x - 4.0 * a  # noqa: E731  1 < |x| < 2
+        taps = np.stack([outer(t + 1.0), inner(t), inner(1.0 - t), outer(2.0 - t)], axis=1)
+        idx = np.clip(f.astype(np.int64)[:, None] - 1 + np.arange(4)[None, :], 0, n_in - 1)
+        start = idx[:, 0]
+        k, w = 4, np.zeros((n_out, 4), dtype=np.float64)
+        for tap in range(4):
+            np.add.at(w, (i, idx[:, tap] - start), taps[:, tap])
+    if k > 4 * RESAMPLE_MAX_REDUCTION + 2:
+        raise ValueError(f'resize_tables: {n_in} -> {n_out} ({mode}) needs {k} taps, srx_resample_planes takes 66')
+    return start.astype(np.int32), np.ascontiguousarray(w.astype(dtype)), k
+
+
+_resize_cache = {}
+
+
+def _resize_device_tables(n_in: int, n_out: int, mode: str, device: torch.device):
+    """``resize_tables`` on ``device`` (start int32, weight fp32), built and copied once per (n_in, n_out, mode, device)."""
+    key = (n_in, n_out, mode, torch.device(device))
+    hit = _resize_cache.get(key)
+    if hit is None:
+        start, weight, k = resize_tables(n_in, n_out, mode)
+        hit = _resize_cache[key] = (torch.from_numpy(start).to(device), torch.from_numpy(weight).to(device), k)
+    return hit
+
+
+def resize(x: Tensor, size: Tuple[int, int], mode: str, out: Optional[Tensor] = None) -> Tensor:
+    """An NCHW tensor resized to ``size = (OH, OW)`` as ``F.interpolate(x, size, mode=mode, align_corners=False)`` does without
+    antialiasing, ``mode`` one of ``'area'``, ``'bilinear'``, ``'bicubic'`` (``resize_tables``) -- the resizes of the
+    second-order degradation -- in one ``srx_resample_planes`` call: bit-reproducible.  ``size == (H, W)`` is the identity:
+    ``x`` itself (copied into ``out`` when given), no launch.  No backward."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError('resize: no backward; run it under torch.no_grad()')
+    if x.dim() != 4:
+        raise ValueError(f'resize: expected an NCHW tensor, got shape {tuple(x.shape)}')
+    if mode not in RESIZE_MODES:
+        raise ValueError(f'resize: mode must be one of {RESIZE_MODES}, got {mode!r}')
+    try:
+        oh, ow = size
+    except (TypeError, ValueError):
+        raise ValueError(f'resize: size must be (OH, OW), got {size!r}') from None
+    n, c, h, w = x.shape
+    for name, v in (('OH', oh), ('OW', ow), ('H', h), ('W', w), ('N * C', n * c)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f'resize: {name} must be a positive int, got {v!r}')
+    if h > RESAMPLE_MAX_REDUCTION * oh or w > RESAMPLE_MAX_REDUCTION * ow:  # before anything touches the device
+        raise ValueError(f'resize: {(h, w)} -> {(oh, ow)} reduces an axis by more than {RESAMPLE_MAX_REDUCTION}:1')
+    x = _chk(x, 'resize.input')
+    shape = (n, c, oh, ow)
+    if out is not None:
+        if _chk(out, 'resize.out') is not out:
+            raise RuntimeError('resize: out must be contiguous')
+        if tuple(out.shape) != shape or out.device != x.device:
+            raise ValueError(f'resize: the result is {shape} on {x.device}, out is {tuple(out.shape)} on {out.device}')
+    if (oh, ow) == (h, w):
+        return x if out is None else out.copy_(x)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    sy, wy, ky = _resize_device_tables(h, oh, mode, x.device)
+    sx, wx, kx = _resize_device_tables(w, ow, mode, x.device)
+    nws = n * c * oh * w
+    ws = _ws(nws, x)
+    call('srx_resample_planes', _p(x), _p(out), n * c, h, w, oh, ow, _p(sy), _p(wy), ky, _p(sx), _p(wx), kx, _p(ws), nws, _stream())
+    return out
+
+
 # --------------------------------------------------------------------------- conv2d
 class WeightPack:
     """One packed layout of a layer's (or a chain of layers') weights: the forward buffer, the optional backward one, the key

@@ -113,11 +113,13 @@ def parse_args(argv=None) -> Namespace:
     train.add_argument('--no-graphs', action='store_true', help='run the step eagerly instead of as a hipGraph')
     train.add_argument('--device-data', action='store_true',
                        help='keep the decoded images in HBM and crop / flip / bicubic-downsample on the GPU')
-    train.add_argument('--degradation', type=str, default='bicubic', choices=('bicubic', 'blind'),
+    train.add_argument('--degradation', type=str, default='bicubic', choices=('bicubic', 'blind', 'blind2'),
                        help='how a low-resolution training image is made from its crop.  bicubic: the antialiased bicubic x1/4 '
                             'alone.  blind: anisotropic Gaussian blur, bicubic x1/4, Gaussian noise and JPEG compression with '
                             'parameters drawn per sample (the first-order model of BSRGAN / Real-ESRGAN), all on the GPU.  '
-                            'blind needs --device-data: the host DataLoader path has no blind degradation.  The per-epoch '
+                            'blind2: the second-order model of Real-ESRGAN -- Gaussian, generalised, plateau and sinc kernels, '
+                            'resizes by random factors and modes, noise and JPEG, the chain applied twice, then a final sinc '
+                            'filter.  blind and blind2 need --device-data: the host DataLoader path has neither.  The per-epoch '
                             'test set stays bicubic')
     train.add_argument('--clip-grad-norm', type=positive_float, default=None, metavar='FLOAT',
                        help='clip the global l2 norm of each model\'s gradient to FLOAT before its Adam step '
@@ -142,8 +144,8 @@ def parse_args(argv=None) -> Namespace:
                            'training data was reduced with (2: a 4K picture from a 1080p one).  Combines with every '
                            '--precision, --self-ensemble and either --model')
     args = parser.parse_args(argv)
-    if args.function == 'train' and args.degradation == 'blind' and not args.device_data:
-        parser.error('--degradation blind needs --device-data (the host DataLoader path has no blind degradation)')
+    if args.function == 'train' and args.degradation in ('blind', 'blind2') and not args.device_data:
+        parser.error(f'--degradation {args.degradation} needs --device-data (the host DataLoader path has no blind degradation)')
     return args
 
 
