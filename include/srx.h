@@ -56,9 +56,16 @@ int srx_build_info(char* buf, size_t n);
 int srx_device_cus(void);
 /* Compute units the launch plans may count on = srx_device_cus() less `k` reserved ones (0..128).  Data-parallel training
  * overlaps the gradient all-reduce (torchsr/srgan/trainer.py:142-157: DistributedDataParallel) with the backward pass, and
- * RCCL's channel workgroups then hold CUs: a grid cut for exactly 256 CUs runs two rounds on 248.  Set ONCE, before any
- * model is built (row counts of BatchNorm partial tables and workspace sizes follow the plans); also SRX_RESERVED_CUS at
- * load time.  srx_plan_cus() returns the count the plans use. */
+ * RCCL's channel workgroups then hold CUs: a grid cut for exactly 256 CUs runs two rounds on 248.  May be set and reset at
+ * any time between calls (ddp.GradBuckets does so inside every step, around its communication windows); also
+ * SRX_RESERVED_CUS at load time.  Every plan-dependent size -- the *_ws_floats queries, the row counts of BatchNorm partial
+ * tables (srx_conv2d_stat_rows, srx_conv2d_bwd_data_bn_rows, srx_wino_stat_rows), srx_conv2d_plan / srx_wino_plan /
+ * srx_conv3x3_c64_bf16_plan -- follows the count of the moment, and a launch plans with the count at ITS call (the packed
+ * weight sizes and layouts depend on the layer alone).  What callers must keep: query the sizes a launch needs in the same
+ * call sequence as that launch, with no srx_set_reserved_cus in between, as functional.py does (it asks right before each
+ * launch and keeps no size across calls); a size queried under another reservation may be too small for the launch or
+ * describe a table of other rows.  A replayed hipGraph keeps the plans it was captured with.  srx_plan_cus() returns the
+ * count the plans use. */
 int srx_set_reserved_cus(int k);
 int srx_plan_cus(void);
 /* Measurement aid (bench.py's data-parallel rehearsal; no reference counterpart): occupies `k` compute units -- k workgroups that each

@@ -1,0 +1,98 @@
+"""Launch forms that real runs reach and the step-size tables (step_layers.py) do not: the 48-pixel row tile, persistent inference
+workgroups that walk several work items, and the plans the planners cut when compute units are reserved for a collective's
+channel kernels (srx_set_reserved_cus: ddp.GradBuckets opens such a window inside every data-parallel step).
+
+Data only.  test_plan_forms_cpu.py holds every case to the form it is here for through the host-only planners (a planner change
+that makes a case vacuous fails there, without a GPU); test_plan_forms_gpu.py runs the launches against fp64.  All plans below are
+those of a 256-CU part -- what srx_plan_cus() reports on the MI355X and, by default, without a GPU."""
+
+CUS = 256
+
+# ------------------------------------------------------------------------------------------------------------ 1. row tile, 48 pixels
+# 3x3 / 64 -> 64 / stride 1 / fp32 layers (rowtile.hip).  tile_pixels() takes 48 when M / 36 > plan CUs >= M / 48:
+# (N, H, W, NB = patch-load batches per thread (the kernel's first template argument), reserved CUs).  With nothing reserved 11 520
+# pixels are 320 tiles of 36 or 240 of 48; at the reference batch (9216 pixels: 256 tiles of 36) any reservation from 8 to 64 CUs
+# moves the plan to 192 tiles of 48 -- the form every data-parallel SRGAN step runs inside its communication windows.
+ROW_TILE_48 = [(20, 24, 24, 1, 0), (5, 48, 48, 2, 0), (16, 24, 24, 1, 8)]
+ROW_TILE_PIXELS = 48
+
+
+def row_tile_desc(n, h, w, act=0, slope=0.0):
+    """Conv2dDesc fields of the row-tile layer."""
+    return (n, h, w, 64, 64, 64, 64, 3, 3, 1, 1, 0, act, slope, 0, 0)
+
+
+# ------------------------------------------------------------------------------------------- 2. persistent kernels, several items each
+# c64.hip (bf16 and fp16): a workgroup walks item = blockIdx.x, += gridDim.x over (image, column strip, row chunk), gridDim.x =
+# min(items, plan CUs / (Cout / 64)).  The chunk planner never makes more items than workgroups while N x strips fits the grid,
+# so only N x strips > grid sends a workgroup through the loop twice.  min_chunks / min_strips: what the case is there for on top.
+C64_MULTI_ITEM = [
+    dict(id='260x5x9.c64.res', shape=(260, 5, 9), cout=64, shuffle=0, res=True, min_chunks=1, min_strips=1),      # 260 items on 256
+    dict(id='70x6x20.c256.shuffle', shape=(70, 6, 20), cout=256, shuffle=2, res=False, min_chunks=1, min_strips=1),  # 70 items on 64
+    # 3 chunks x 2 strips per image, 774 items on 256 workgroups: 256 = 42 x 6 + 4, so a workgroup's next item is another image,
+    # the other strip (128 + 2 columns: a ragged one) and another chunk
+    dict(id='129x15x130.c64.res', shape=(129, 15, 130), cout=64, shuffle=0, res=True, min_chunks=3, min_strips=2),
+]
+# thin9.hip (bf16 and fp16) has no plan query; its grid is min(items, plan CUs) and items >= N x ceil(W / 128), so
+# N x ceil(W / 128) > 256 forces several items per workgroup whatever chunk height the planner takes.  (N, H, W, Cout);
+# H = 5 is shorter than the 9-row window, H = 12 longer than the ring of 10 output rows.
+THIN9_STRIP = 128
+THIN9_MULTI_ITEM = [(260, 5, 7, 3), (260, 12, 7, 3)]
+# 130 x ceil(40 / 128) = 130 strips on 256 workgroups: one item each under today's planner (its span model prefers one 12-row
+# chunk per strip), so this shape is NOT a multi-item case and the host-only test does not claim it; it runs on the GPU with the others
+THIN9_OTHER = [(130, 12, 40, 3)]
+
+# ----------------------------------------------------------------------------------------------------- 3. plans under a reservation
+# desc: Conv2dDesc fields (N, H, W, Cin, Cin_s, Cout, Cout_s, KH, KW, stride, pad, shuffle, act, slope, up, precision); k: reserved
+# CUs; fields: what must differ from the plan with nothing reserved; plan0 / plan: the planner's answer at 0 and at k CUs reserved.
+# gconv plans (srx_conv2d_plan): [BM, BN, tail split, workgroups, KS, multi]; Winograd (srx_wino_plan): [BN, channel splits,
+# workgroups, tile blocks, chunks per workgroup, parts per tile of the last round]; c64: [rows per chunk, chunks, strips].
+GCONV_FIELDS = {'tile': 0, 'split': 2, 'workgroups': 3, 'ks': 4}
+WINO_FIELDS = {'bn': 0, 'zsplit': 1, 'workgroups': 2}
+
+
+def _conv(n, h, w, cin, cout, k, prec=0, cin_s=None):
+    return (n, h, w, cin, cin_s or cin, cout, cout, k, k, 1, k // 2, 0, 0, 0.0, 0, prec)
+
+
+# the dense block's conv2 (esrgan/residual.py:82): 96 of the 192-strided buffer's channels -> 32
+_DENSE2 = (4, 32, 32, 96, 192, 32, 32, 3, 3, 1, 1, 0, 0, 0.0, 0, 0)
+# 3 -> 64, 9 x 9 with the image stored in 8-channel pixels: at Cin_s = 4 srx_conv2d_bwd_data hands the layer to the 3-channel
+# kernel (thin.hip, one plan at these sizes whatever is reserved) and the K-split tail below never runs
+_IMG9 = _conv(1, 96, 96, 3, 64, 9, cin_s=8)
+
+RESERVED_GCONV = [
+    dict(id='fwd.4x32x32.96of192to32.k8', which=0, desc=_DENSE2, k=8, fields=('split', 'workgroups'),
+         plan0=[64, 32, 4, 256, 2, 0], plan=[64, 32, 3, 192, 2, 0]),
+    dict(id='dgrad.1x96x96.3to64.9x9.k8', which=1, desc=_IMG9, k=8, fields=('split',),
+         plan0=[64, 32, 7, 1008, 2, 0], plan=[64, 32, 5, 720, 2, 0]),
+    dict(id='dgrad.1x96x96.3to64.9x9.k32', which=1, desc=_IMG9, k=32, fields=('split',),
+         plan0=[64, 32, 7, 1008, 2, 0], plan=[64, 32, 3, 432, 2, 0]),
+    dict(id='dgrad.1x96x96.3to64.9x9.k64', which=1, desc=_IMG9, k=64, fields=('split',),
+         plan0=[64, 32, 7, 1008, 2, 0], plan=[64, 32, 4, 576, 2, 0]),
+    dict(id='dgrad.3x40x40.64to256.k32', which=1, desc=_conv(3, 40, 40, 64, 256, 3), k=32, fields=('tile', 'workgroups'),
+         plan0=[128, 64, 6, 228, 1, 0], plan=[144, 64, 6, 204, 1, 0]),
+    dict(id='dgrad.3x40x40.64to256.k64', which=1, desc=_conv(3, 40, 40, 64, 256, 3), k=64, fields=('split', 'workgroups'),
+         plan0=[128, 64, 6, 228, 1, 0], plan=[128, 64, 5, 190, 1, 0]),
+    dict(id='dgrad.4x24x24.128to256.bf16.k64', which=1, desc=_conv(4, 24, 24, 128, 256, 3, prec=1), k=64,
+         fields=('tile', 'split', 'workgroups', 'ks'), plan0=[64, 64, 3, 216, 2, 0], plan=[128, 64, 5, 180, 1, 0]),
+]
+# Winograd F(2x2, 3x3), forward and data gradient: 64-column workgroups with every tile's channels split three ways (and a
+# workspace) become 32-column workgroups without a split (and without a workspace)
+RESERVED_WINO = [
+    dict(id='wino.4x24x24.256to256.k64', desc=_conv(4, 24, 24, 256, 256, 3), k=64, fields=('bn', 'zsplit', 'workgroups'),
+         plan0=[64, 3, 216, 18, 3, 1], plan=[32, 1, 144, 18, 8, 1], ws0=1769472, ws=0),
+]
+# the bf16 / fp16 inference conv: chunk geometry of one 300 x 200 frame
+RESERVED_C64 = [dict(id='c64.1x300x200.k64', shape=(1, 300, 200), cout=64, k=64, plan0=[3, 100, 2], plan=[4, 75, 2])]
+# weight gradients through srx_conv2d_bwd_weight_multi (two problems): the row splits move with the CUs, and with them the
+# workspace (ws0 / ws: srx_conv2d_bwd_weight_multi_ws_floats at 0 / k reserved)
+RESERVED_WGRAD = [
+    dict(id='wgrad.2x32x32.64to64.k32', desc=_conv(2, 32, 32, 64, 64, 3), nprob=2, k=32, ws0=960128, ws=812416),
+    dict(id='wgrad.2x32x32.64to64.k64', desc=_conv(2, 32, 32, 64, 64, 3), nprob=2, k=64, ws0=960128, ws=738560),
+    dict(id='wgrad.3x40x40.64to256.k8', desc=_conv(3, 40, 40, 64, 256, 3), nprob=2, k=8, ws0=2067968, ws=2954240),
+]
+
+
+def by_id(cases):
+    return [c['id'] for c in cases]

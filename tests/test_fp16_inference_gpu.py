@@ -70,7 +70,8 @@ def test_f32_to_f16_rounds_to_nearest_even_and_back_exactly(dev):
     (3, 9, 33, 128, 0, False, -0.5, 128),     # Cout 128; a slope outside [0, 1]
     (1, 20, 45, 256, 2, False, 0.25, 64),     # sub-pixel layer: PixelShuffle(2) in the store
     (2, 13, 70, 64, 0, True, 1.0, 96),        # output channel stride > 64 (channels 64..95 untouched), ragged H and W
-    (1, 300, 200, 64, 0, True, 0.25, 64),     # several row chunks per column strip
+    (1, 300, 200, 64, 0, True, 0.25, 64),     # several row chunks per column strip (one item per workgroup; several:
+                                              # test_plan_forms_gpu.py)
 ])
 def test_fp16_conv3x3_c64(dev, n, h, w, cout, shuffle, res, slope, y_cs):
     """``srx_conv3x3_c64_f16_fwd`` against fp64 of fp16-rounded x, W and addend: the kernel sums in fp32 and rounds ONCE to

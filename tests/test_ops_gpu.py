@@ -1328,7 +1328,8 @@ def test_bf16_weight_gradient_on_image_rows(dev, n, h, w, cin):
     (1, 37, 64, 64, 0, False),      # 2 x 2 segments (W <= 64), odd row count
     (3, 9, 33, 128, 0, False),      # two channel groups written into 128-channel pixels
     (1, 20, 45, 256, 2, False),     # sub-pixel layer: 256 channels, PixelShuffle(2) in the store
-    (1, 300, 200, 64, 0, True),     # several row chunks per column strip (persistent workgroups walk more than one item)
+    (1, 300, 200, 64, 0, True),     # several row chunks per column strip (200 items on 256 workgroups: one item each --
+                                    # several items per workgroup: test_plan_forms_gpu.py)
 ])
 def test_bf16_native_conv3x3_c64(dev, n, h, w, cout, shuffle, res):
     """``srx_conv3x3_c64_bf16_fwd`` (bf16 tensors in HBM, weights resident in registers, a rolling window of image rows in
