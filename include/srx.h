@@ -512,6 +512,21 @@ int srx_add_gaussian_noise(const float* in_nchw, float* out_nchw, const float* s
 int srx_jpeg_sim(const float* in_nchw, float* out_nchw, const int32_t* quality, int N, int H, int W, int quantize,
                  void* stream);
 
+/* ------------------------------------------------- sharpened targets (usm.hip) */
+/* Real-ESRGAN's USMSharp on float planes in [0, 1] ('Sharpened targets').  G is the separable correlation with
+ * g (x) g, g = taps (DEVICE float [ksize], used as given), borders reflected (-k -> k, as F.pad(mode='reflect')):
+ *   blur = G(in); res = in - blur; mask = |res| 255 > threshold ? 1 : 0; soft = G(mask);
+ *   out = in + soft (clamp(in + weight res, 0, 1) - in)
+ * the last line one fma, so that weight = 0 on inputs in [0, 1], and a threshold no residual reaches, give out == in bit for bit.
+ * in, out, blur, mask: [planes][H][W]; blur and mask are caller buffers that are left holding their planes (mask exactly 0.0 or
+ * 1.0).  Two launches; fmas in ascending tap order, horizontal pass first; no atomics, no device state: the same bits from
+ * every call.
+ * Refused before any launch: a null pointer; ksize even, < 3 or > 51; H or W <= ksize / 2 (the reflection needs ksize / 2 + 1
+ * samples); planes < 1; planes * H * W >= 2^31; a non-finite weight or threshold; out, blur or mask overlapping in or each
+ * other. */
+int srx_usm_sharpen(const float* in, float* out, float* blur, float* mask, const float* taps, int ksize, int64_t planes, int H,
+                    int W, float weight, float threshold, void* stream);
+
 /* -------------------------------------------------------------- batch norm */
 /* nn.BatchNorm2d(C), eps 1e-5, momentum 0.1 (srgan/residual.py:65,68;
  * srgan/generator.py:49; srgan/discriminator.py:36-60).

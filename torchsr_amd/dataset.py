@@ -92,7 +92,7 @@ class DeviceLoader:
     """
 
     def __init__(self, images, device, batch_size: int, crop_size: int, upscale_factor: int, test: bool, seed: int,
-                 multiplier: int = 1, rank: int = 0, world_size: int = 1, degradation: str = 'bicubic'):
+                 multiplier: int = 1, rank: int = 0, world_size: int = 1, gt_usm: bool = False, degradation: str = 'bicubic'):
         from . import _lib
         if degradation not in DEGRADATIONS:
             raise ValueError(f'DeviceLoader: degradation must be one of {DEGRADATIONS}, got {degradation!r}')
@@ -107,6 +107,11 @@ class DeviceLoader:
             if lc <= 10 or s1_max > 16 * s2_min:
                 raise ValueError(f'DeviceLoader: blind2 degradation needs a low-resolution side of more than 10 pixels and resizes of '
                                  f'at most 16:1; crop {crop_size} / {upscale_factor} can draw {s1_max} -> {s2_min}')
+        if not isinstance(gt_usm, bool):
+            raise ValueError(f'DeviceLoader: gt_usm must be a bool, got {gt_usm!r}')
+        if gt_usm and crop_size <= 25:
+            raise ValueError(f'DeviceLoader: gt_usm needs a crop of more than 25 pixels (the 51-tap unsharp mask reflects 25), '
+                             f'got crop {crop_size}')
         self._lib = _lib
         self.device, self.batch, self.crop, self.up, self.test = device, batch_size, crop_size, upscale_factor, test
         self.images = [self._fit(im).to(device) for im in images]          # uint8 [H][W][3]
@@ -117,6 +122,9 @@ class DeviceLoader:
         # ``blind`` / ``blind2`` train batches only: the degradation parameters and the noise seeds come from a stream of their own, so
         # the crop / flip stream above -- and with it every high-resolution batch -- is the same in both modes
         self.degradation = degradation
+        # train batches only: the crop is unsharp-masked (functional.usm_sharpen, Real-ESRGAN's defaults) before it is yielded AND
+        # before it is degraded; this draws from neither stream ('Sharpened targets')
+        self.gt_usm = gt_usm
         self.deg_rng = random.Random(seed * 15485863 + rank + 982451653)
         self.last_degradation = None
         self.epoch = 0
@@ -339,6 +347,10 @@ class DeviceLoader:
             stream = torch.cuda.current_stream().cuda_stream
             hr = torch.empty((len(idx), 3, self.crop, self.crop), dtype=torch.float32, device=dev)
             call('srx_crop_flip_u8', ptrs.data_ptr(), meta_t.data_ptr(), hr.data_ptr(), len(idx), self.crop, stream)
+            if self.gt_usm and not self.test:
+                from . import functional as F
+                with torch.no_grad():
+                    hr = F.usm_sharpen(hr)
             if deg is not None:
                 self.last_degradation = deg
                 yield (self._degrade2 if self.degradation == 'blind2' else self._degrade)(hr, deg, stream), hr
@@ -362,10 +374,13 @@ def _decode(path: str) -> torch.Tensor:
 
 def initialize_device_datasets(train_directory: str, device, batch_size: int = 64, crop_size: int = 96,
                                upscale_factor: int = 4, dataset_multiplier: int = 1, distributed: bool = False,
-                               seed: int = 0, rank: int = 0, world_size: int = 1, degradation: str = 'bicubic'):
+                               seed: int = 0, rank: int = 0, world_size: int = 1, gt_usm: bool = False,
+                               degradation: str = 'bicubic'):
     """``initialize_datasets`` with the augmentation on the device (``--device-data``).  ``synthetic:N`` draws N
     seeded random 2*crop x 2*crop images.  ``degradation='blind'`` degrades the TRAIN batches' low-resolution side with blur,
-    noise and JPEG (``--degradation``), ``'blind2'`` with the second-order recipe; the test loader stays bicubic."""
+    noise and JPEG (``--degradation``), ``'blind2'`` with the second-order recipe; ``gt_usm`` unsharp-masks the TRAIN batches'
+    high-resolution crop, which is then both the target and what is degraded (``--gt-usm``); the test loader stays bicubic and
+    unsharpened."""
     if train_directory.startswith('synthetic:'):
         n = int(train_directory.split(':')[1])
         g = torch.Generator().manual_seed(seed)
@@ -381,7 +396,7 @@ def initialize_device_datasets(train_directory: str, device, batch_size: int = 6
     if not distributed:
         rank, world_size = 0, 1
     train = DeviceLoader(images[n_test:] or images, device, batch_size, crop_size, upscale_factor, False, seed,
-                         dataset_multiplier, rank, world_size, degradation=degradation)
+                         dataset_multiplier, rank, world_size, degradation=degradation, gt_usm=gt_usm)
     # dataset.py:343-360: the test set is multiplied like the train set, sharded over the ranks, nothing dropped
     test = DeviceLoader(images[:n_test], device, batch_size, crop_size, upscale_factor, True, seed + 1,
                         dataset_multiplier, rank, world_size)

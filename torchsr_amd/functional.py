@@ -677,6 +677,71 @@ def resize(x: Tensor, size: Tuple[int, int], mode: str, out: Optional[Tensor] = 
     return out
 
 
+USM_MAX_KSIZE = 51  # srx_usm_sharpen's longest filter
+
+
+def _usm_check_filter(ksize, sigma) -> None:
+    import math
+    if isinstance(ksize, bool) or not isinstance(ksize, int) or ksize < 3 or ksize > USM_MAX_KSIZE or ksize % 2 == 0:
+        raise ValueError(f'usm: ksize must be an odd int in 3..{USM_MAX_KSIZE}, got {ksize!r}')
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not math.isfinite(sigma) or sigma <= 0:
+        raise ValueError(f'usm: sigma must be a positive finite number, got {sigma!r}')
+
+
+def usm_taps(ksize: int = 51, sigma: float = 8.0):
+    """The 1-D Gaussian of the unsharp mask: ``g[i] ~ exp(-(i - r)^2 / (2 sigma^2))``, ``i = 0 .. ksize - 1``, ``r = ksize // 2``,
+    normalised to sum 1 -- built in fp64 with numpy and rounded once to fp32.  The defaults are Real-ESRGAN's ``USMSharp``:
+    radius 50 made odd, and the sigma ``cv2.getGaussianKernel(51, 0)`` derives, ``0.3 * ((ksize - 1) / 2 - 1) + 0.8 = 8``.
+    ``sigma`` is always explicit and positive (OpenCV's fixed tables for small sizes with ``sigma <= 0`` are not restated)."""
+    import numpy as np
+    _usm_check_filter(ksize, sigma)
+    d = np.arange(ksize, dtype=np.float64) - ksize // 2
+    g = np.exp(-(d * d) / (2.0 * float(sigma) ** 2))
+    return (g / g.sum()).astype(np.float32)
+
+
+_usm_cache = {}
+
+
+def _usm_device_taps(ksize: int, sigma: float, device: torch.device) -> Tensor:
+    """``usm_taps`` on ``device``, built and copied once per (ksize, sigma, device)."""
+    key = (ksize, float(sigma), torch.device(device))
+    hit = _usm_cache.get(key)
+    if hit is None:
+        hit = _usm_cache[key] = torch.from_numpy(usm_taps(ksize, sigma)).to(device)
+    return hit
+
+
+def usm_sharpen(x: Tensor, ksize: int = 51, sigma: float = 8.0, weight: float = 0.5, threshold: float = 10.0,
+                return_stages: bool = False):
+    """Real-ESRGAN's ``USMSharp`` on an NCHW tensor in [0, 1], in one ``srx_usm_sharpen`` call (two launches): with ``G`` the
+    separable reflect-padded correlation with ``usm_taps(ksize, sigma)``, ``blur = G(x)``, ``mask = |x - blur| * 255 >
+    threshold``, ``soft = G(mask)``, ``out = x + soft * (clamp(x + weight * (x - blur), 0, 1) - x)``.  Returns a new tensor;
+    ``return_stages=True`` returns ``(out, blur, mask)``.  Bit-reproducible.  No backward."""
+    import math
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError('usm_sharpen: no backward; run it under torch.no_grad()')
+    if x.dim() != 4:
+        raise ValueError(f'usm_sharpen: expected an NCHW tensor, got shape {tuple(x.shape)}')
+    _usm_check_filter(ksize, sigma)
+    for name, v in (('weight', weight), ('threshold', threshold)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f'usm_sharpen: {name} must be a finite number, got {v!r}')
+    n, c, h, w = x.shape
+    if n * c < 1:
+        raise ValueError(f'usm_sharpen: empty batch, shape {tuple(x.shape)}')
+    if h <= ksize // 2 or w <= ksize // 2:
+        raise ValueError(f'usm_sharpen: {h} x {w} planes: a {ksize}-tap reflect needs {ksize // 2 + 1} rows and columns')
+    if n * c * h * w >= 1 << 31:
+        raise ValueError(f'usm_sharpen: {tuple(x.shape)} holds 2^31 elements or more')
+    x = _chk(x, 'usm_sharpen.input')
+    taps = _usm_device_taps(ksize, sigma, x.device)
+    out, blur, mask = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    call('srx_usm_sharpen', _p(x), _p(out), _p(blur), _p(mask), _p(taps), ksize, n * c, h, w, float(weight), float(threshold),
+         _stream())
+    return (out, blur, mask) if return_stages else out
+
+
 # --------------------------------------------------------------------------- conv2d
 class WeightPack:
     """One packed layout of a layer's (or a chain of layers') weights: the forward buffer, the optional backward one, the key

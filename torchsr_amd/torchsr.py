@@ -121,6 +121,12 @@ def parse_args(argv=None) -> Namespace:
                             'resizes by random factors and modes, noise and JPEG, the chain applied twice, then a final sinc '
                             'filter.  blind and blind2 need --device-data: the host DataLoader path has neither.  The per-epoch '
                             'test set stays bicubic')
+    train.add_argument('--gt-usm', action='store_true',
+                       help='sharpen every training target with Real-ESRGAN\'s unsharp mask (51-tap Gaussian, sigma 8, weight 0.5, '
+                            'threshold 10) on the GPU before it is used: the sharpened crop is the target of every loss and the '
+                            'input of the selected --degradation.  Needs --device-data.  There is one target per step, so the '
+                            'discriminator\'s real sample is the sharpened crop too: Real-ESRNet\'s gt_usm with gan_gt_usm: True, '
+                            'where Real-ESRGAN\'s x4plus options set gan_gt_usm: False.  The per-epoch test set is not sharpened')
     train.add_argument('--clip-grad-norm', type=positive_float, default=None, metavar='FLOAT',
                        help='clip the global l2 norm of each model\'s gradient to FLOAT before its Adam step '
                             '(torch.nn.utils.clip_grad_norm_, computed on the GPU inside the captured step; default: off)')
@@ -146,6 +152,8 @@ def parse_args(argv=None) -> Namespace:
     args = parser.parse_args(argv)
     if args.function == 'train' and args.degradation in ('blind', 'blind2') and not args.device_data:
         parser.error(f'--degradation {args.degradation} needs --device-data (the host DataLoader path has no blind degradation)')
+    if args.function == 'train' and args.gt_usm and not args.device_data:
+        parser.error('--gt-usm needs --device-data (the host DataLoader path has no unsharp mask)')
     return args
 
 
@@ -194,7 +202,7 @@ def main(argv=None) -> None:
             args.train_dir, device, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=4,
             dataset_multiplier=args.dataset_multiplier, distributed=distributed, seed=args.seed,
             rank=max(int(args.rank), 0) if distributed else 0, world_size=int(args.world_size) if distributed else 1,
-            degradation=args.degradation)
+            degradation=args.degradation, gt_usm=args.gt_usm)
     else:
         train_loader, test_loader, train_len, test_len = initialize_datasets(
             args.train_dir, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=4,
