@@ -504,6 +504,22 @@ int srx_filter2d(const float* in_nchw, float* out_nchw, const float* weights, co
  * sigma: float [N]; gray: int32 [N]; [N][3][H][W]; quantize != 0 clamps to [0, 1] and rounds to 8 bits. */
 int srx_add_gaussian_noise(const float* in_nchw, float* out_nchw, const float* sigma, const int32_t* gray, uint32_t seed_lo,
                            uint32_t seed_hi, int N, int H, int W, int quantize, void* stream);
+/* Signal-dependent (shot) noise, Real-ESRGAN's generate_poisson_noise_pt per sample ('Poisson noise').  With
+ * q = rint(clamp(x, 0, 1) 255) of a value x, vals = the number of distinct q over the sample's three channels rounded up to a
+ * power of two (1..256), k ~ Poisson(q vals / 255): out = in + scale[n] (k / vals - q / 255) -- q (float) times 1.0f / 255.0f,
+ * the difference and one fma, k / vals exact.  gray[n] != 0: q comes from the luma fadd(fadd(fmul(.299f, r), fmul(.587f, g)),
+ * fmul(.114f, b)) (each operation rounded once: the kernels switch contraction off there), vals counts the luma levels and one k per pixel feeds the three
+ * channels.  scale[n] == 0 copies the sample bit for bit.
+ * The draw: Philox4x32-10 with counter (p, n, 1, 0) and key (seed_lo, seed_hi) gives r0..r3, word c for channel c (word 0 for
+ * all three of a grey sample); k = first[v][q] + the number of entries of win[v][q][0..255] that are <= r >> 1, v = log2(vals).
+ * tables: DEVICE int32, first[9][256] followed by the uint32 thresholds win[9][256][256] -- what degradation.
+ * poisson_table_words() builds on the host in float64, so that no device float decides an integer.
+ * levels: DEVICE int32 [N][8], an OUTPUT: the call clears it, then sets bit q of sample n's 256-bit mask for every level q the
+ * sample holds (merged with atomicOr; a sample with scale 0 keeps an empty mask).  scale: float [N]; gray: int32 [N];
+ * [N][3][H][W]; quantize as in srx_add_gaussian_noise.  A clear and two launches; stateless: the same seed gives the same bits.
+ * Refused before anything is issued: a null pointer, N outside 1..65535, H or W < 1, H W >= 2^31. */
+int srx_add_poisson_noise(const float* in_nchw, float* out_nchw, const float* scale, const int32_t* gray, const int32_t* tables,
+                          int32_t* levels, uint32_t seed_lo, uint32_t seed_hi, int N, int H, int W, int quantize, void* stream);
 /* What a baseline JPEG codec at quality[n] (int32 [N], libjpeg's scale) does to the pixels of a 4:4:4 image: 8-bit samples,
  * libjpeg's integer RGB -> YCbCr, orthonormal 8 x 8 DCT, the Annex K tables scaled by libjpeg's rule, rounding, the inverse
  * transform (decoded samples unrounded), float YCbCr -> RGB, / 255, clamp.  No chroma subsampling; entropy coding is

@@ -1,6 +1,6 @@
 // Blind degradation of the training data on the device ('Blind degradation'): the first-order model of
 // BSRGAN / Real-ESRGAN -- blur, resize, sensor noise, JPEG -- around augment.hip's srx_bicubic_down, and the table-driven
-// filter of its second-order model ('Second-order degradation').  Four kernels over a
+// filter of its second-order model ('Second-order degradation'), and its Poisson noise ('Poisson noise').  Kernels over a
 // batch of float NCHW images in [0, 1]; every per-sample parameter is read on the device, so each kernel is safe for any
 // value it finds there (a kernel size outside the legal set is clamped into it, a quality outside 1..100 passes through).
 #include "srx_common.h"
@@ -207,6 +207,121 @@ __global__ void add_gaussian_noise_kernel(const float* __restrict__ in, float* _
   }
 }
 
+// ------------------------------------------------------------------------------------------------ Poisson noise, table-driven
+// Real-ESRGAN's generate_poisson_noise_pt per sample: q = the 8-bit level of a value (of its BT.601 luma when the sample is
+// grey), vals = the number of distinct q of the whole sample rounded up to a power of two, k ~ Poisson(q vals / 255),
+// out = in + scale (k / vals - q / 255).  Two kernels: which levels a sample holds, then one draw per value from host-made
+// threshold tables (degradation.poisson_table_words), so that no float decides an integer on the device.
+constexpr int kPoissonWindow = 256;                    // thresholds per packed row
+constexpr int kPoissonFirstWords = 9 * 256;            // first[9][256] in front of win[9][256][kPoissonWindow]
+
+// The three helpers below switch contraction off: hipcc's default would fuse their products and sums into fmas (the __f*_rn
+// intrinsics are plain operators to it), differently in each kernel that inlines them.  With it off every operation is rounded
+// once, both kernels get the same level for a value, and a float32 restatement gets the same bits.
+__device__ __forceinline__ int poisson_level(float v) {  // 0..255, NaN: 0
+#pragma clang fp contract(off)
+  return (int)rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f);
+}
+__device__ __forceinline__ float poisson_luma(float r, float g, float b) {
+#pragma clang fp contract(off)
+  const float pr = .299f * r, pg = .587f * g, pb = .114f * b;
+  return (pr + pg) + pb;
+}
+// k / vals - q / 255: k inv is exact (inv a power of two), the product with 1 / 255 and the difference are rounded once each
+__device__ __forceinline__ float poisson_offset(int k, float inv, int q) {
+#pragma clang fp contract(off)
+  const float a = (float)k * inv, t = (float)q * (1.0f / 255.0f);
+  return a - t;
+}
+
+// levels[n][8]: bit q of the 256-bit mask is set when some value of sample n has level q.  The caller cleared it.  A
+// workgroup collects its pixels' levels in LDS and merges at most 8 words.  grid (blocks, N), 256 threads.
+__global__ __launch_bounds__(256) void poisson_levels_kernel(const float* __restrict__ in, const float* __restrict__ scale,
+                                                             const int* __restrict__ gray, int* __restrict__ levels, int HW) {
+  __shared__ unsigned int mask[8];
+  const int n = blockIdx.y, t = threadIdx.x;
+  if (scale[n] == 0.f) return;  // the sample is copied: nothing reads its mask (the whole workgroup leaves)
+  if (t < 8) mask[t] = 0u;
+  __syncthreads();
+  const bool g = gray[n] != 0;
+  const float* src = in + (size_t)n * 3 * HW;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + t; p < HW; p += (int64_t)gridDim.x * 256) {
+    const float r = src[p], gg = src[p + (size_t)HW], b = src[p + 2 * (size_t)HW];
+    if (g) {
+      const int q = poisson_level(poisson_luma(r, gg, b));
+      atomicOr(&mask[q >> 5], 1u << (q & 31));
+    } else {
+      const int q0 = poisson_level(r), q1 = poisson_level(gg), q2 = poisson_level(b);
+      atomicOr(&mask[q0 >> 5], 1u << (q0 & 31));
+      atomicOr(&mask[q1 >> 5], 1u << (q1 & 31));
+      atomicOr(&mask[q2 >> 5], 1u << (q2 & 31));
+    }
+  }
+  __syncthreads();
+  if (t < 8 && mask[t]) atomicOr(reinterpret_cast<unsigned int*>(levels) + (size_t)n * 8 + t, mask[t]);
+}
+
+// the smallest k with u < T[level][k]: first + the number of the window's (non-decreasing) thresholds that are <= u
+__device__ __forceinline__ int poisson_draw(const int* __restrict__ tables, int v, int level, uint32_t r) {
+  const int rowi = v * 256 + level;
+  const uint32_t* row = reinterpret_cast<const uint32_t*>(tables) + kPoissonFirstWords + (size_t)rowi * kPoissonWindow;
+  const uint32_t u = r >> 1;
+  int lo = 0, hi = kPoissonWindow;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;  // <= 255
+    if (row[mid] <= u) lo = mid + 1; else hi = mid;
+  }
+  return tables[rowi] + lo;
+}
+
+// one thread per pixel; one Philox call per pixel: counter (p, n, 1, 0), key (seed_lo, seed_hi); word c feeds channel c, word 0
+// all three of a grey sample
+__global__ void add_poisson_noise_kernel(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ scale,
+                                         const int* __restrict__ gray, const int* __restrict__ tables,
+                                         const int* __restrict__ levels, uint32_t seed_lo, uint32_t seed_hi, int N, int HW,
+                                         int quantize) {
+  const int64_t total = (int64_t)N * HW;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int n = (int)(i / HW), p = (int)(i - (int64_t)n * HW);
+    const size_t base = (size_t)n * 3 * HW + p;
+    const float x[3] = {in[base], in[base + (size_t)HW], in[base + 2 * (size_t)HW]};
+    const float sc = scale[n];
+    if (sc == 0.f) {  // bit for bit
+#pragma unroll
+      for (int c = 0; c < 3; ++c) out[base + (size_t)c * HW] = x[c];
+      continue;
+    }
+    int count = 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) count += __popc((unsigned int)levels[(size_t)n * 8 + w]);
+    // vals = count rounded up to a power of two = 2^v, v in 0..8 (count is 1..256 for a sample the levels kernel has seen)
+    const int v = count <= 1 ? 0 : min(32 - __clz(count - 1), 8);
+    const float inv = 1.0f / (float)(1 << v);  // exact
+    uint32_t r[4];
+    philox4x32_10((uint32_t)p, (uint32_t)n, 1u, 0u, seed_lo, seed_hi, r);
+    const bool g = gray[n] != 0;
+    float noise[3];
+    if (g) {
+      const int q = poisson_level(poisson_luma(x[0], x[1], x[2]));
+      const int k = poisson_draw(tables, v, q, r[0]);
+      noise[0] = noise[1] = noise[2] = poisson_offset(k, inv, q);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int q = poisson_level(x[c]);
+        const int k = poisson_draw(tables, v, q, r[c]);
+        noise[c] = poisson_offset(k, inv, q);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float o = fmaf(sc, noise[c], x[c]);  // three roundings in all: q / 255, the difference, this one (k / vals is exact)
+      if (quantize) o = rintf(fminf(fmaxf(o, 0.f), 1.f) * 255.f) * (1.0f / 255.0f);
+      out[base + (size_t)c * HW] = o;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ JPEG, 4:4:4, no entropy coding
 // D[k][n] = c_k / 2 cos((2 n + 1) k pi / 16), c_0 = 1 / sqrt(2): the orthonormal 8-point DCT-II, rounded to fp32
 __constant__ float kDct[64] = {
@@ -349,6 +464,26 @@ extern "C" int srx_add_gaussian_noise(const float* in_nchw, float* out_nchw, con
   hipLaunchKernelGGL(add_gaussian_noise_kernel, dim3(grid_for((int64_t)N * H * W)), dim3(256), 0, srx_stream(stream),
                      in_nchw, out_nchw, sigma, gray, seed_lo, seed_hi, N, H * W, quantize);
   SRX_CHECK_LAUNCH("add_gaussian_noise_kernel");
+  return SRX_OK;
+}
+
+extern "C" int srx_add_poisson_noise(const float* in_nchw, float* out_nchw, const float* scale, const int32_t* gray,
+                                     const int32_t* tables, int32_t* levels, uint32_t seed_lo, uint32_t seed_hi, int N, int H,
+                                     int W, int quantize, void* stream) {
+  SRX_REQUIRE(in_nchw && out_nchw && scale && gray && tables && levels, "add_poisson_noise: null pointer");
+  SRX_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0, "add_poisson_noise: bad shape (N %d of 1..65535, %d x %d planes)", N, H, W);
+  SRX_REQUIRE((int64_t)H * W <= 0x7fffffff, "add_poisson_noise: planes too large");
+  hipStream_t st = srx_stream(stream);
+  const int HW = H * W;
+  if (hipMemsetAsync(levels, 0, (size_t)N * 8 * sizeof(int32_t), st) != hipSuccess)
+    SRX_FAIL(SRX_E_HIP, "add_poisson_noise: memset failed");
+  const int64_t per_sample = srx_cdiv(HW, 1024);  // four pixels per thread before a sample gets another workgroup
+  hipLaunchKernelGGL(poisson_levels_kernel, dim3((unsigned)(per_sample > 64 ? 64 : per_sample), N), dim3(256), 0, st, in_nchw,
+                     scale, gray, levels, HW);
+  SRX_CHECK_LAUNCH("poisson_levels_kernel");
+  hipLaunchKernelGGL(add_poisson_noise_kernel, dim3(grid_for((int64_t)N * HW)), dim3(256), 0, st, in_nchw, out_nchw, scale, gray,
+                     tables, levels, seed_lo, seed_hi, N, HW, quantize);
+  SRX_CHECK_LAUNCH("add_poisson_noise_kernel");
   return SRX_OK;
 }
 

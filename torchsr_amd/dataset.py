@@ -92,7 +92,8 @@ class DeviceLoader:
     """
 
     def __init__(self, images, device, batch_size: int, crop_size: int, upscale_factor: int, test: bool, seed: int,
-                 multiplier: int = 1, rank: int = 0, world_size: int = 1, gt_usm: bool = False, degradation: str = 'bicubic'):
+                 multiplier: int = 1, rank: int = 0, world_size: int = 1, gt_usm: bool = False, poisson_prob: float = 0.0,
+                 degradation: str = 'bicubic'):
         from . import _lib
         if degradation not in DEGRADATIONS:
             raise ValueError(f'DeviceLoader: degradation must be one of {DEGRADATIONS}, got {degradation!r}')
@@ -112,6 +113,11 @@ class DeviceLoader:
         if gt_usm and crop_size <= 25:
             raise ValueError(f'DeviceLoader: gt_usm needs a crop of more than 25 pixels (the 51-tap unsharp mask reflects 25), '
                              f'got crop {crop_size}')
+        if isinstance(poisson_prob, bool) or not isinstance(poisson_prob, (int, float)) or not 0.0 <= poisson_prob <= 1.0:
+            raise ValueError(f'DeviceLoader: poisson_prob must be a number in [0, 1], got {poisson_prob!r}')
+        if poisson_prob > 0 and degradation not in ('blind', 'blind2'):
+            raise ValueError(f'DeviceLoader: poisson_prob needs degradation blind or blind2 (bicubic adds no noise), got '
+                             f'{degradation!r}')
         self._lib = _lib
         self.device, self.batch, self.crop, self.up, self.test = device, batch_size, crop_size, upscale_factor, test
         self.images = [self._fit(im).to(device) for im in images]          # uint8 [H][W][3]
@@ -126,6 +132,10 @@ class DeviceLoader:
         # before it is degraded; this draws from neither stream ('Sharpened targets')
         self.gt_usm = gt_usm
         self.deg_rng = random.Random(seed * 15485863 + rank + 982451653)
+        # ``blind`` / ``blind2`` train batches with ``poisson_prob`` > 0 only: which samples get Poisson noise in place of the Gaussian
+        # one, and its scale, come from a third stream, so the two above are what they were ('Poisson noise')
+        self.poisson_prob = float(poisson_prob)
+        self.poi_rng = random.Random(seed * 32452843 + rank + 472882027) if self.poisson_prob > 0 else None
         self.last_degradation = None
         self.epoch = 0
 
@@ -166,7 +176,7 @@ class DeviceLoader:
 
     def _draw_degradation(self, n: int) -> dict:
         """The ``blind`` parameters of a batch of ``n`` samples, drawn on the host from the degradation stream: the first-order
-        recipe of Real-ESRGAN without its sinc and Poisson branches.  Numpy arrays, laid out as the kernels read them:
+        recipe of Real-ESRGAN without its sinc branch (its Poisson branch: ``_draw_poisson``).  Numpy arrays, laid out as the kernels read them:
         ``parm`` float32 [n][4] = {sigma_x, sigma_y, theta, 0}, ``ksize`` int32 [n], ``sigma_n`` float32 [n], ``gray`` int32 [n],
         ``quality`` int32 [n]; and ``seed``, the batch's 64-bit noise seed."""
         import math
@@ -214,7 +224,7 @@ class DeviceLoader:
 
     def _draw_degradation2(self, n: int) -> dict:
         """The ``blind2`` parameters of a batch of ``n`` samples, drawn on the host from the degradation stream: the second-order
-        recipe of Real-ESRGAN (x4plus options) without its Poisson branch.  One fixed order.  Per BATCH first, so that the
+        recipe of Real-ESRGAN (x4plus options); its Poisson branch is ``_draw_poisson``.  One fixed order.  Per BATCH first, so that the
         batch stays rectangular: the first resize (one uniform for up / down / keep, the factor unless kept, the mode), the
         second resize likewise, the final resize's mode, the final order.  Then per SAMPLE: the first kernel
         (``_draw_kernel(3.0)``), sigma, grey flag and JPEG quality of the first pass; one uniform (< 0.2: no second blur), else
@@ -275,9 +285,29 @@ class DeviceLoader:
                 'modes': (mode1, mode2, mode3), 'order': order, 'seed1': rng.getrandbits(64), 'seed2': rng.getrandbits(64),
                 'kinds': kinds}
 
+    def _draw_poisson(self, deg: dict) -> dict:
+        """The Poisson branch of a drawn batch, from the Poisson stream; ``deg`` is changed in place and returned.  One fixed order:
+        per SAMPLE, per noise STAGE of the recipe (one for ``blind``, two for ``blind2``): one uniform (< ``poisson_prob``: Poisson),
+        then the scale -- ``uniform(0.05, 3.0)`` in the first stage, ``uniform(0.05, 2.5)`` in the second -- which is drawn whether or
+        not Poisson was chosen, so the stream's position depends on no outcome.  ``deg`` gains ``poisson_scale``, float32 shaped like
+        ``sigma_n``: the scale where Poisson was chosen, else 0; there ``sigma_n`` becomes 0."""
+        import numpy as np
+        rng, sigma_n = self.poi_rng, deg['sigma_n']
+        scale = np.zeros(sigma_n.shape, dtype=np.float32)
+        sig, sc = sigma_n.reshape(-1, sigma_n.shape[-1]), scale.reshape(-1, sigma_n.shape[-1])   # views: [stages][n]
+        for i in range(sig.shape[1]):
+            for stage in range(sig.shape[0]):
+                chosen = rng.random() < self.poisson_prob
+                s = rng.uniform(0.05, 3.0 if stage == 0 else 2.5)
+                if chosen:
+                    sc[stage, i], sig[stage, i] = s, 0.0
+        deg['poisson_scale'] = scale
+        return deg
+
     def _plan(self):
         """Host side of one epoch: per batch the sample indices, the crop / flip rows and -- ``blind`` and ``blind2`` train batches
-        only, and after the rows, from the other stream -- the degradation parameters (else None)."""
+        only, and after the rows, from the other stream -- the degradation parameters (else None); with ``poisson_prob`` > 0 their
+        Poisson branch after them, from the third."""
         order = list(self.order)
         if not self.test:
             random.Random(self.epoch * 104729 + 17).shuffle(order)  # same permutation on every rank
@@ -288,10 +318,23 @@ class DeviceLoader:
             meta = self._draw_meta(idx)
             blind = self.degradation == 'blind' and not self.test   # the test set stays bicubic: PSNR comparable across runs
             blind2 = self.degradation == 'blind2' and not self.test
-            yield idx, meta, self._draw_degradation(len(idx)) if blind else self._draw_degradation2(len(idx)) if blind2 else None
+            deg = self._draw_degradation(len(idx)) if blind else self._draw_degradation2(len(idx)) if blind2 else None
+            yield idx, meta, self._draw_poisson(deg) if deg is not None and self.poi_rng is not None else deg
+
+    def _poisson(self, x, scale, gray_dev, seed, scale_dev=None):
+        """The Poisson half of a noise step: ``x`` with ``srx_add_poisson_noise(quantize=0)`` on the samples that drew it, under the
+        stage's seed; ``x`` itself -- and nothing is uploaded or launched -- when the batch has no ``poisson_scale`` (``scale`` is
+        None) or no sample of the stage drew Poisson.  The Gaussian call that follows adds exactly 0 to those samples (their sigma
+        is 0) and does the 8-bit rounding for all.  ``scale``: the stage's host array; ``gray_dev``: the grey flags on the device;
+        ``scale_dev``: the scales there, when the caller has already copied them."""
+        if scale is None or not scale.any():
+            return x
+        from . import functional as F
+        with torch.no_grad():
+            return F.add_poisson_noise(x, torch.from_numpy(scale).to(x.device) if scale_dev is None else scale_dev, gray_dev, seed)[0]
 
     def _degrade(self, hr, deg, stream):
-        """``blind``: blur -> bicubic x1/scale (unquantised) -> Gaussian noise -> 8 bits -> JPEG -> 8 bits."""
+        """``blind``: blur -> bicubic x1/scale (unquantised) -> Poisson or Gaussian noise -> 8 bits -> JPEG -> 8 bits."""
         call, dev, n = self._lib.call, self.device, hr.shape[0]
         lc = self.crop // self.up
         on_dev = {k: torch.from_numpy(deg[k]).to(dev) for k in ('parm', 'ksize', 'sigma_n', 'gray', 'quality')}
@@ -301,6 +344,7 @@ class DeviceLoader:
         lr = torch.empty((n, 3, lc, lc), dtype=torch.float32, device=dev)
         call('srx_bicubic_down', blurred.data_ptr(), lr.data_ptr(), n, 3, self.crop, self.crop, self.up, 0, stream)
         noisy = torch.empty_like(lr)
+        lr = self._poisson(lr, deg.get('poisson_scale'), on_dev['gray'], deg['seed'])
         call('srx_add_gaussian_noise', lr.data_ptr(), noisy.data_ptr(), on_dev['sigma_n'].data_ptr(), on_dev['gray'].data_ptr(),
              deg['seed'] & 0xFFFFFFFF, deg['seed'] >> 32, n, lc, lc, 1, stream)
         call('srx_jpeg_sim', noisy.data_ptr(), lr.data_ptr(), on_dev['quality'].data_ptr(), n, lc, lc, 1, stream)
@@ -314,6 +358,9 @@ class DeviceLoader:
         weights = torch.from_numpy(deg['weights']).to(dev)  # the three tables in one copy
         ksize, sigma_n, gray, quality = (torch.from_numpy(deg[k]).to(dev) for k in ('ksize', 'sigma_n', 'gray', 'quality'))
         (s1, s2, lc), modes = deg['sizes'], deg['modes']
+        pscale = deg.get('poisson_scale')
+        if pscale is not None and pscale.any():
+            pscale = (pscale, torch.from_numpy(pscale).to(dev))  # both stages in one copy, and only when a sample drew Poisson
 
         def filt(x, stage, quantize):
             out = torch.empty_like(x)
@@ -323,6 +370,8 @@ class DeviceLoader:
 
         def noise(x, stage, seed):
             out = torch.empty_like(x)
+            if isinstance(pscale, tuple):
+                x = self._poisson(x, pscale[0][stage], gray[stage], seed, pscale[1][stage])
             call('srx_add_gaussian_noise', x.data_ptr(), out.data_ptr(), sigma_n[stage].data_ptr(), gray[stage].data_ptr(),
                  seed & 0xFFFFFFFF, seed >> 32, n, x.shape[2], x.shape[3], 1, stream)
             return out
@@ -375,12 +424,13 @@ def _decode(path: str) -> torch.Tensor:
 def initialize_device_datasets(train_directory: str, device, batch_size: int = 64, crop_size: int = 96,
                                upscale_factor: int = 4, dataset_multiplier: int = 1, distributed: bool = False,
                                seed: int = 0, rank: int = 0, world_size: int = 1, gt_usm: bool = False,
-                               degradation: str = 'bicubic'):
+                               poisson_prob: float = 0.0, degradation: str = 'bicubic'):
     """``initialize_datasets`` with the augmentation on the device (``--device-data``).  ``synthetic:N`` draws N
     seeded random 2*crop x 2*crop images.  ``degradation='blind'`` degrades the TRAIN batches' low-resolution side with blur,
     noise and JPEG (``--degradation``), ``'blind2'`` with the second-order recipe; ``gt_usm`` unsharp-masks the TRAIN batches'
-    high-resolution crop, which is then both the target and what is degraded (``--gt-usm``); the test loader stays bicubic and
-    unsharpened."""
+    high-resolution crop, which is then both the target and what is degraded (``--gt-usm``); ``poisson_prob`` gives each sample of
+    each noise stage of ``blind`` / ``blind2`` Poisson noise with that probability in place of the Gaussian one
+    (``--poisson-noise-prob``); the test loader stays bicubic and unsharpened."""
     if train_directory.startswith('synthetic:'):
         n = int(train_directory.split(':')[1])
         g = torch.Generator().manual_seed(seed)
@@ -396,7 +446,7 @@ def initialize_device_datasets(train_directory: str, device, batch_size: int = 6
     if not distributed:
         rank, world_size = 0, 1
     train = DeviceLoader(images[n_test:] or images, device, batch_size, crop_size, upscale_factor, False, seed,
-                         dataset_multiplier, rank, world_size, degradation=degradation, gt_usm=gt_usm)
+                         dataset_multiplier, rank, world_size, degradation=degradation, gt_usm=gt_usm, poisson_prob=poisson_prob)
     # dataset.py:343-360: the test set is multiplied like the train set, sharded over the ranks, nothing dropped
     test = DeviceLoader(images[:n_test], device, batch_size, crop_size, upscale_factor, True, seed + 1,
                         dataset_multiplier, rank, world_size)

@@ -71,3 +71,65 @@ def kernel_slot(w, out=None) -> np.ndarray:
         o = KERNEL_SLOT // 2 - ks // 2
         slot[o:o + ks, o:o + ks] = w
     return slot
+
+
+# ------------------------------------------------------------------------------------------------ Poisson noise
+POISSON_VALS = (1, 2, 4, 8, 16, 32, 64, 128, 256)  # what the number of distinct 8-bit levels of a sample rounds up to
+POISSON_K = 512      # entries of a full threshold row: k = 0 .. 511
+POISSON_WINDOW = 256  # entries of a packed row; the part of a full row that is neither 0 nor 2^31 is under 200 entries wide
+
+
+@functools.lru_cache(maxsize=None)
+def _poisson_thresholds(vals: int) -> np.ndarray:
+    lg = np.array([math.lgamma(k + 1.0) for k in range(POISSON_K)], dtype=np.float64)
+    k = np.arange(POISSON_K, dtype=np.float64)
+    t = np.empty((256, POISSON_K), dtype=np.uint32)
+    for level in range(256):
+        lam = level * vals / 255                                  # float64 from the two integers
+        if level == 0:
+            pmf = np.zeros(POISSON_K, dtype=np.float64)
+            pmf[0] = 1.0
+        else:
+            pmf = np.exp(k * math.log(lam) - lam - lg)
+        cdf = np.cumsum(pmf)                                      # ascending k
+        tail = np.cumsum(pmf[::-1])[::-1] - pmf                   # sum over j > k, the small terms first
+        row = np.minimum(np.floor(cdf * 2.0 ** 31), 2.0 ** 31)
+        row[tail < 2.0 ** -32] = 2.0 ** 31
+        t[level] = row.astype(np.uint32)
+    t.setflags(write=False)
+    return t
+
+
+def poisson_thresholds(vals: int) -> np.ndarray:
+    """The sampler's table for one of ``POISSON_VALS``: uint32 ``T[256][512]``, ``T[level][k] = min(floor(CDF(k) 2^31), 2^31)`` of
+    the Poisson distribution with ``lambda = level * vals / 255``.  A draw is the smallest ``k`` with ``(r >> 1) < T[level][k]``,
+    ``r`` a uniform 32-bit word.  lambda is formed in float64 from the integers, the pmf is ``exp(k ln(lambda) - lambda -
+    lgamma(k + 1))`` and is summed in ascending ``k``; level 0 is the point mass at 0.  A float64 sum of the whole pmf ends one
+    ulp below 1 as often as on it, so a row would stall at ``2^31 - 1`` and a draw could run off its end: from the first ``k``
+    whose upper tail ``sum_{j > k} pmf(j)`` (summed from the far end) is below ``2^-32`` the entry IS ``2^31`` -- one count above
+    the exact floor, where ``r >> 1`` cannot tell the two apart by more than its own resolution.  Read-only; built once."""
+    if isinstance(vals, bool) or not isinstance(vals, (int, np.integer)) or int(vals) not in POISSON_VALS:
+        raise ValueError(f'poisson_thresholds: vals must be one of {POISSON_VALS}, got {vals!r}')
+    return _poisson_thresholds(int(vals))
+
+
+@functools.lru_cache(maxsize=None)
+def poisson_table_words() -> np.ndarray:
+    """The nine tables as ``srx_add_poisson_noise`` reads them, one int32 array: ``first[9][256]``, then the uint32 windows
+    ``win[9][256][256]`` (their bit patterns), ``v = log2(vals)``.  ``first[v][level]`` is the first ``k`` whose threshold is not
+    0 and ``win[v][level][j] = T[level][first + j]`` (``2^31`` past the row's end); every window ends on ``2^31``, so the
+    smallest ``k`` with ``(r >> 1) < T[level][k]`` is ``first`` plus the number of window entries that are ``<= r >> 1``."""
+    first = np.zeros((len(POISSON_VALS), 256), dtype=np.int32)
+    win = np.full((len(POISSON_VALS), 256, POISSON_WINDOW), 1 << 31, dtype=np.uint32)
+    for v, vals in enumerate(POISSON_VALS):
+        t = poisson_thresholds(vals)
+        for level in range(256):
+            k0 = int(np.argmax(t[level] > 0))
+            part = t[level, k0:k0 + POISSON_WINDOW]
+            first[v, level] = k0
+            win[v, level, :len(part)] = part
+    if not (win[:, :, -1] == 1 << 31).all():
+        raise AssertionError('poisson_table_words: a row does not reach 2^31 inside its window')
+    words = np.concatenate([first.reshape(-1), win.reshape(-1).view(np.int32)])
+    words.setflags(write=False)
+    return words

@@ -742,6 +742,56 @@ def usm_sharpen(x: Tensor, ksize: int = 51, sigma: float = 8.0, weight: float = 
     return (out, blur, mask) if return_stages else out
 
 
+_poisson_cache = {}
+
+
+def poisson_tables(device) -> Tensor:
+    """``degradation.poisson_table_words()`` on ``device`` (int32, 2.4 MB): the threshold tables ``srx_add_poisson_noise`` draws
+    from, built and copied once per device."""
+    key = torch.device(device)
+    if key.type == 'cuda' and key.index is None:
+        key = torch.device('cuda', torch.cuda.current_device())
+    hit = _poisson_cache.get(key)
+    if hit is None:
+        from .degradation import poisson_table_words
+        hit = _poisson_cache[key] = torch.from_numpy(poisson_table_words().copy()).to(key)
+    return hit
+
+
+def add_poisson_noise(x: Tensor, scale, gray, seed: int, quantize: bool = False):
+    """Real-ESRGAN's Poisson (shot) noise on an ``[N, 3, H, W]`` tensor in [0, 1], in one ``srx_add_poisson_noise`` call (a clear
+    and two launches): per sample, ``q`` the 8-bit level of a value, ``vals`` the number of distinct levels of the sample rounded
+    up to a power of two, ``k ~ Poisson(q * vals / 255)``, ``out = x + scale[n] * (k / vals - q / 255)``; ``gray[n] != 0`` takes
+    ``q`` from the BT.601 luma and gives the three channels one ``k`` per pixel; ``scale[n] == 0`` copies the sample.  ``scale``
+    (float32 ``[N]``) and ``gray`` (int32 ``[N]``) are tensors on ``x``'s device or anything ``torch.as_tensor`` takes; ``seed``
+    is the 64-bit Philox key (counter ``(pixel, sample, 1, 0)``: another stream than ``srx_add_gaussian_noise``'s with the same
+    seed).  ``quantize`` clamps to [0, 1] and rounds to 8 bits.  Returns ``(out, levels)``, ``levels`` int32 ``[N, 8]`` the
+    256-bit mask of the levels each sample holds.  Bit-reproducible.  No backward."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError('add_poisson_noise: no backward; run it under torch.no_grad()')
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f'add_poisson_noise: expected an [N, 3, H, W] tensor, got shape {tuple(x.shape)}')
+    n, _, h, w = x.shape
+    if n < 1 or n > 65535 or h < 1 or w < 1:
+        raise ValueError(f'add_poisson_noise: N must be in 1..65535 and the planes non-empty, got shape {tuple(x.shape)}')
+    if h * w >= 1 << 31:
+        raise ValueError(f'add_poisson_noise: {h} x {w} planes hold 2^31 elements or more')
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise ValueError(f'add_poisson_noise: seed must be an int in 0..2^64 - 1, got {seed!r}')
+    scale = torch.as_tensor(scale, dtype=torch.float32)
+    gray = torch.as_tensor(gray, dtype=torch.int32)
+    if tuple(scale.shape) != (n,) or tuple(gray.shape) != (n,):
+        raise ValueError(f'add_poisson_noise: scale and gray must have shape ({n},), got {tuple(scale.shape)} and {tuple(gray.shape)}')
+    x = _chk(x, 'add_poisson_noise.input')
+    scale, gray = scale.to(x.device).contiguous(), gray.to(x.device).contiguous()
+    tables = poisson_tables(x.device)
+    out = torch.empty_like(x)
+    levels = torch.empty((n, 8), dtype=torch.int32, device=x.device)
+    call('srx_add_poisson_noise', _p(x), _p(out), _p(scale), _p(gray), _p(tables), _p(levels), seed & 0xFFFFFFFF, seed >> 32,
+         n, h, w, int(bool(quantize)), _stream())
+    return out, levels
+
+
 # --------------------------------------------------------------------------- conv2d
 class WeightPack:
     """One packed layout of a layer's (or a chain of layers') weights: the forward buffer, the optional backward one, the key

@@ -46,6 +46,16 @@ def positive_float(value: str) -> float:
     return float_value
 
 
+def probability(value: str) -> float:
+    try:
+        float_value = float(value)
+    except (TypeError, ValueError):
+        raise ArgumentTypeError(f'invalid float value: \'{value}\'')
+    if not 0.0 <= float_value <= 1.0:  # (also NaN)
+        raise ArgumentTypeError('value must be a probability in [0, 1]!')
+    return float_value
+
+
 def get_device(args: Namespace) -> torch.device:
     """torchsr.py:69-98."""
     count = torch.cuda.device_count()
@@ -127,6 +137,10 @@ def parse_args(argv=None) -> Namespace:
                             'input of the selected --degradation.  Needs --device-data.  There is one target per step, so the '
                             'discriminator\'s real sample is the sharpened crop too: Real-ESRNet\'s gt_usm with gan_gt_usm: True, '
                             'where Real-ESRGAN\'s x4plus options set gan_gt_usm: False.  The per-epoch test set is not sharpened')
+    train.add_argument('--poisson-noise-prob', type=probability, default=0.0, metavar='FLOAT',
+                       help='with --device-data and --degradation blind or blind2: the probability with which a sample of a '
+                            'noise stage gets signal-dependent Poisson (shot) noise, the noise of dark photos, in place of the '
+                            'stage\'s Gaussian noise.  Real-ESRGAN uses 0.5; the default 0 leaves the degradation as it was')
     train.add_argument('--clip-grad-norm', type=positive_float, default=None, metavar='FLOAT',
                        help='clip the global l2 norm of each model\'s gradient to FLOAT before its Adam step '
                             '(torch.nn.utils.clip_grad_norm_, computed on the GPU inside the captured step; default: off)')
@@ -150,6 +164,9 @@ def parse_args(argv=None) -> Namespace:
                            'training data was reduced with (2: a 4K picture from a 1080p one).  Combines with every '
                            '--precision, --self-ensemble and either --model')
     args = parser.parse_args(argv)
+    if args.function == 'train' and args.poisson_noise_prob > 0 and not (args.device_data and args.degradation in ('blind', 'blind2')):
+        parser.error('--poisson-noise-prob replaces the Gaussian noise of a blind degradation: add --device-data and '
+                     '--degradation blind or --degradation blind2')
     if args.function == 'train' and args.degradation in ('blind', 'blind2') and not args.device_data:
         parser.error(f'--degradation {args.degradation} needs --device-data (the host DataLoader path has no blind degradation)')
     if args.function == 'train' and args.gt_usm and not args.device_data:
@@ -202,7 +219,7 @@ def main(argv=None) -> None:
             args.train_dir, device, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=4,
             dataset_multiplier=args.dataset_multiplier, distributed=distributed, seed=args.seed,
             rank=max(int(args.rank), 0) if distributed else 0, world_size=int(args.world_size) if distributed else 1,
-            degradation=args.degradation, gt_usm=args.gt_usm)
+            degradation=args.degradation, gt_usm=args.gt_usm, poisson_prob=args.poisson_noise_prob)
     else:
         train_loader, test_loader, train_len, test_len = initialize_datasets(
             args.train_dir, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=4,
