@@ -175,9 +175,11 @@ int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out);
 
 /* Plan overrides for tests and tile experiments (no reference counterpart).  They hold for every later call of this process until
  * reset with zeros (srx_wgrad_force: (-1, 0)); the environment seeds them at load (SRX_FORCE_PLAN="BM,BN,split,ks", SRX_S2_MODE bit 0,
- * SRX_NO_WGRAD_LIN, SRX_WGRAD_NSPLIT).  srx_conv2d_plan and the workspace queries report what a forced call runs.  A forced form a
+ * SRX_NO_WGRAD_LIN, SRX_WGRAD_NSPLIT, SRX_THIN_FWD_ROWS).  srx_conv2d_plan, srx_thin_plan and the workspace queries report what a
+ * forced call runs.  A forced form a
  * layer has no kernel for (tile not instantiated at the layer's arithmetic, BN not dividing the padded columns, 144 rows with bf16
- * products, the fused kernel on a layer it cannot run, more row splits than the rows allow) is refused with SRX_E_UNSUPPORTED and
+ * products, the fused kernel on a layer it cannot run, more row splits than the rows allow, 4 rows per wave on a 3-channel output
+ * layer with bf16 products) is refused with SRX_E_UNSUPPORTED and
  * a message when that layer is planned or called, before anything is launched.
  * srx_conv2d_force_plan: every gconv_kernel / gconv_multi_kernel plan (not the whole-frame calls above 2^24 pixels) is BM x BN
  *   (BM = 144: the 128 + 16 row tile), every tile K-split `split` ways where the output is linear (strided / shuffled outputs run
@@ -185,10 +187,25 @@ int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out);
  * srx_conv2d_force_s2: strided data gradients -- mode 0 the cost model, 1 always gconv_multi_kernel (tile from the model or
  *   srx_conv2d_force_plan), 2 always gconv_s2f_kernel on tile BM x BN ((2, 0, 0): the model's fused tile).
  * srx_wgrad_force: fp32 weight gradients -- lin 0: never the LIN form of wgrad_dma_kernel, 1 / -1: wherever it is eligible (the
- *   default); nsplit > 0: that many row splits (whole 32-row chunks of at least 128 rows), 0: the model's. */
+ *   default); nsplit > 0: that many row splits (whole 32-row chunks of at least 128 rows), 0: the model's.
+ * srx_thin_force_rows: the 3-channel output kernel (forward of the 64 -> <= 4 channel layers, data gradient of the <= 4 -> 64
+ *   ones) -- 3, 4 or 6 output rows per wave, i.e. tiles of 12, 16 or 24 rows x 32 pixels; 0: the model's (6 from four tiles of
+ *   24 rows per plan CU on, else 3).  Any other value is refused (SRX_THIN_FWD_ROWS: ignored with a line on stderr); the
+ *   kernel with bf16 products (precision = 2) exists with 3 and 6 rows. */
 int srx_conv2d_force_plan(int bm, int bn, int split, int ks);
 int srx_conv2d_force_s2(int mode, int bm, int bn);
 int srx_wgrad_force(int lin, int nsplit);
+int srx_thin_force_rows(int rows);
+
+/* Launch plan of the kernels with a <= 4-channel side (thin.hip), computed by the function the launches themselves plan with;
+ * host code only.  which = 0 forward of a 64 -> <= 4 channel layer, 1 data gradient of a <= 4 -> 64 channel layer (both
+ * thin_fwd2_kernel / thin_fwd2_bf16_kernel): out[4] = {rows per wave R, row tiles of 4 R rows, column tiles of 32 pixels,
+ * workgroups}.  2 weight gradient of either (thin_wgrad_kernel): out[5] = {groups of kernel rows, segments of 16 pixels of one
+ * image row, segments per wave range, ranges that hold a segment, workgroups per group = slabs the reduction sums}; the launch
+ * has groups x slabs workgroups of four wave ranges, the ranges past the fourth entry are empty.  3 forward of a 3x3 <= 4 -> 64
+ * channel layer (first3x3_fwd_kernel): out[2] = {tiles of 32 pixels, workgroups}; a wave walks tile = 4 workgroup + wave, += 4
+ * workgroups.  SRX_E_UNSUPPORTED when the layer does not take that path, or is forced to a form it has no kernel for. */
+int srx_thin_plan(const srx_conv2d_t* d, int which, int* out);
 
 /* OIHW master weights -> packed forward ([Cout_p][K_p], K=(kh,kw,ci)) and, when
  * wpk_bwd != NULL, packed data-gradient operands (per stride-parity class,

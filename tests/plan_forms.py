@@ -1,9 +1,11 @@
 """Launch forms that real runs reach and the step-size tables (step_layers.py) do not: the 48-pixel row tile, persistent inference
 workgroups that walk several work items, and the plans the planners cut when compute units are reserved for a collective's
-channel kernels (srx_set_reserved_cus: ddp.GradBuckets opens such a window inside every data-parallel step).
+channel kernels (srx_set_reserved_cus: ddp.GradBuckets opens such a window inside every data-parallel step); and every launch
+form of the kernels with a 3-channel side (thin.hip, section 4).
 
 Data only.  test_plan_forms_cpu.py holds every case to the form it is here for through the host-only planners (a planner change
-that makes a case vacuous fails there, without a GPU); test_plan_forms_gpu.py runs the launches against fp64.  All plans below are
+that makes a case vacuous fails there, without a GPU); test_plan_forms_gpu.py and test_thin_forms_gpu.py run the launches against
+fp64.  All plans below are
 those of a 256-CU part -- what srx_plan_cus() reports on the MI355X and, by default, without a GPU."""
 
 CUS = 256
@@ -96,3 +98,68 @@ RESERVED_WGRAD = [
 
 def by_id(cases):
     return [c['id'] for c in cases]
+
+
+# ------------------------------------------------------------------------------------ 4. the kernels with a 3-channel side (thin.hip)
+# Plans: srx_thin_plan (which = 0 forward / 1 data gradient: [R, tiles_h, tiles_w, workgroups]; 2 weight gradient: [groups, nseg,
+# segs_per_range, nranges, nslabs]; 3 first3x3_fwd_kernel: [ntiles, workgroups]).  test_thin_forms_gpu.py runs every case below.
+THIN_ROWS = (3, 4, 6)      # rows per wave srx_thin_force_rows accepts besides 0; thin_fwd2_bf16_kernel exists with 3 and 6
+THIN_KS = (3, 9)
+
+
+def thin_out_desc(n, h, w, k, cthin=3, prec=0):
+    """64 -> cthin channels: forward on thin_fwd2_kernel / thin_fwd2_bf16_kernel, weight gradient on thin_wgrad_kernel<.., -1>."""
+    return (n, h, w, 64, 64, cthin, 4, k, k, 1, k // 2, 0, 0, 0.0, 0, prec)
+
+
+def thin_in_desc(n, h, w, k, cthin=3, prec=0, act=0, slope=0.0):
+    """cthin -> 64 channels: data gradient on thin_fwd2_kernel, weight gradient on thin_wgrad_kernel<.., +1>, forward (3 x 3) on
+    first3x3_fwd_kernel."""
+    return (n, h, w, cthin, 4, 64, 64, k, k, 1, k // 2, 0, act, slope, 0, prec)
+
+
+def thin_fwd_forced_shapes(r):
+    """(N, H, W) per forced R (tiles of 4 R rows x 32 pixels): one row and one column short of a tile; one row and one column into
+    the second tile; an image shorter than the halo and three tiles wide with a ragged last one; three row tiles with a ragged
+    last one under two whole column tiles."""
+    return [(1, 4 * r - 1, 31), (2, 4 * r + 1, 33), (1, 2, 70), (3, 8 * r + 5, 64)]
+
+
+THIN_FWD_FORCED = [(r, k, s) for r in THIN_ROWS for k in THIN_KS for s in thin_fwd_forced_shapes(r)]
+# thin channel counts other than 3, one (R, K, shape) each: (cthin, R, K, (N, H, W))
+THIN_FWD_CTHIN = [(1, 3, 3, (2, 13, 33)), (2, 4, 9, (2, 17, 33)), (4, 6, 3, (2, 25, 33))]
+# the planner's own R = 6 (N x ceil(H / 24) x ceil(W / 32) >= 4 x plan CUs): 130 x 2 x 2 = 520 tiles >= 4 x 128; with nothing
+# reserved the same shape runs R = 3.  (N, H, W), reserved CUs, plan
+THIN_FWD_OWN_R6 = dict(shape=(130, 25, 33), k=128, plan=[6, 2, 2, 520], plan0=[3, 3, 2, 780])
+
+# weight gradient: K, reserved CUs, (N, H, W), plan.  ranges = min(plan CUs x 8 / groups, nseg): 682 / 341 (9 x 9: three groups of
+# kernel rows) and 2048 / 1024 (3 x 3) at 0 / 128 reserved; wave slots = 4 x nslabs, `empty` of them past the last range.
+THIN_WGRAD = [
+    # ranges of two segments over rows of five (72 = 4 x 16 + 8: a ragged last one): they cross row and image ends
+    dict(id='k9.4x41x72', K=9, k=0, shape=(4, 41, 72), plan=[3, 820, 2, 410, 103], empty=2),
+    dict(id='k9.3x41x40.r128', K=9, k=128, shape=(3, 41, 40), plan=[3, 369, 2, 185, 47], empty=3),   # last range: one segment
+    dict(id='k3.6x41x72.r128', K=3, k=128, shape=(6, 41, 72), plan=[1, 1230, 2, 615, 154], empty=1),
+    # three segments per range, 820 = 273 x 3 + 1
+    dict(id='k9.4x41x72.r128', K=9, k=128, shape=(4, 41, 72), plan=[3, 820, 3, 274, 69], empty=2),
+    # one segment per range; slab counts on both sides of the reduction's 4-way (r < slabs) and 16-way (r + 12 < slabs) loops
+    dict(id='k3.1x12x7', K=3, k=0, shape=(1, 12, 7), plan=[1, 12, 1, 12, 3], empty=0),
+    dict(id='k9.2x8x16', K=9, k=0, shape=(2, 8, 16), plan=[3, 16, 1, 16, 4], empty=0),
+    dict(id='k3.1x17x9', K=3, k=0, shape=(1, 17, 9), plan=[1, 17, 1, 17, 5], empty=3),
+    dict(id='k9.3x10x20', K=9, k=0, shape=(3, 10, 20), plan=[3, 60, 1, 60, 15], empty=0),
+    dict(id='k3.2x16x23', K=3, k=0, shape=(2, 16, 23), plan=[1, 64, 1, 64, 16], empty=0),
+    dict(id='k9.1x13x70', K=9, k=0, shape=(1, 13, 70), plan=[3, 65, 1, 65, 17], empty=3),
+    dict(id='k3.1x1x5', K=3, k=0, shape=(1, 1, 5), plan=[1, 1, 1, 1, 1], empty=3),
+    dict(id='k9.1x1x5', K=9, k=0, shape=(1, 1, 5), plan=[3, 1, 1, 1, 1], empty=3),
+    dict(id='k3.2x3x16', K=3, k=0, shape=(2, 3, 16), plan=[1, 6, 1, 6, 2], empty=2),
+    dict(id='k9.2x3x16', K=9, k=0, shape=(2, 3, 16), plan=[3, 6, 1, 6, 2], empty=2),
+]
+# thin channel counts other than 3 on the weight gradient, each at 3 x 3 and at 9 x 9, thin side in and out: (cthin, case id)
+THIN_WGRAD_CTHIN = [(1, 'k3.1x17x9'), (2, 'k9.2x8x16'), (4, 'k3.2x16x23'), (4, 'k9.3x10x20')]
+
+# first3x3_fwd_kernel: tiles of 32 pixels, min(ceil(ntiles / 4), 3 x plan CUs) workgroups of four waves.  (N, H, W), reserved, plan
+THIN_FIRST3 = [
+    # M = 49 500 = 1546 x 32 + 28: 1547 tiles on 384 x 4 = 1536 waves -- eleven waves walk a second tile, the last tile is ragged
+    dict(id='5x100x99.r128', shape=(5, 100, 99), k=128, plan=[1547, 384], multi=True),
+    dict(id='1x3x5', shape=(1, 3, 5), k=0, plan=[1, 1], multi=False),      # M = 15 < 32
+    dict(id='2x7x1', shape=(2, 7, 1), k=0, plan=[1, 1], multi=False),      # one pixel per row: every tap to the left and right is padding
+]

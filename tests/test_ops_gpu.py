@@ -1212,7 +1212,9 @@ def test_strided_data_gradient_with_activation_backward(dev, n, h, w, cin, cout,
 def test_output_conv_with_bf16_products(dev, k, n, h, w):
     """``srx_conv2d_t::precision = 2``: the 64 -> 3 output convs (9x9 SRGAN, 3x3 ESRGAN) with bf16-rounded operands on
     ``v_mfma_f32_4x4x4_16b_bf16`` (inference) against fp64 of the rounded operands; images of several tiles, of less than one
-    tile, and enough tiles for the six-rows-per-wave variant."""
+    tile, and the six-rows-per-wave variant: 3 x 40 x 96 x 96 is 480 tiles of 24 rows, under the 4 x 256 from which the planner
+    takes it, so that shape runs a second time with the variant forced (srx_thin_force_rows) and the launched name asserted."""
+    from torchsr_amd import _lib
     from torchsr_amd import functional as F
     from torchsr_amd.layers import Conv2d
     torch.manual_seed(k + h)
@@ -1229,6 +1231,26 @@ def test_output_conv_with_bf16_products(dev, k, n, h, w):
         y0 = F.to_nchw(conv(F.to_nhwc(x)), 3)
     exact = torch.nn.functional.conv2d(x.double().cpu(), conv.weight.detach().double().cpu(), conv.bias.detach().double().cpu(), 1, (k - 1) // 2)
     assert rel_err(y0, exact) < 2e-5 and rel_err(y, exact) > 1e-4  # (and the two settings are different arithmetic)
+    if (k, n, h, w) == (3, 40, 96, 96):
+        d = _lib.Conv2dDesc(n, h, w, 64, 64, 3, 4, k, k, 1, 1, 0, 0, 0.0, 0, 2)
+        plan = (C.c_int * 4)()
+        _lib.call('srx_thin_plan', C.byref(d), 0, plan)
+        assert list(plan) == [3, 8, 3, 960]                     # (the model's choice here: twelve-row tiles)
+        conv._st.precision = 2
+        xh, got = F.to_nhwc(x), []
+
+        def six():
+            with torch.no_grad():
+                got.append(conv(xh))
+        try:
+            _lib.call('srx_thin_force_rows', 6)
+            _lib.call('srx_thin_plan', C.byref(d), 0, plan)
+            assert list(plan) == [6, 4, 3, 480]
+            names = _prof_names(six)
+        finally:
+            _lib.call('srx_thin_force_rows', 0)
+        assert names == ['thin_fwd2_bf16_kernel<3, 6, 0>'], names
+        assert rel_err(F.to_nchw(got[0], 3), ref) < 2e-5
 
 
 @pytest.mark.parametrize('prelu', [True, False])

@@ -169,6 +169,8 @@ _SIGS = {
     'srx_conv2d_stat_rows': (_I, [_D]),
     'srx_conv2d_plan': (_I, [_D, _I, C.POINTER(C.c_int)]),
     'srx_conv2d_force_plan': (_I, [_I, _I, _I, _I]),
+    'srx_thin_plan': (_I, [_D, _I, C.POINTER(C.c_int)]),
+    'srx_thin_force_rows': (_I, [_I]),
     'srx_conv2d_force_s2': (_I, [_I, _I, _I]),
     'srx_wgrad_force': (_I, [_I, _I]),
     'srx_pack_table_bytes': (_Z, [_I]),

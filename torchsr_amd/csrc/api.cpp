@@ -71,6 +71,13 @@ static SrxDevSwitches read_switches() {
       s.rdb_ablate = 0; s.c64_ablate = 0;
     }
   }
+  // Rows per wave of the 3-channel output kernels (thin.hip): only the instantiated counts seed srx_thin_force_rows -- any other
+  // value used to cut the grid for rows no kernel wrote
+  if (s.thin_fwd_rows != 0 && s.thin_fwd_rows != 3 && s.thin_fwd_rows != 4 && s.thin_fwd_rows != 6) {
+    fprintf(stderr, "libsrx_hip: SRX_THIN_FWD_ROWS=%d ignored: the 3-channel output kernels run 3, 4 or 6 rows per wave "
+                    "(0: the model's choice)\n", s.thin_fwd_rows);
+    s.thin_fwd_rows = 0;
+  }
   if (const char* f = getenv("SRX_FORCE_PLAN")) {
     int v[4] = {0, 0, 1, 1};
     if (sscanf(f, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]) == 4) { s.force_plan = true; for (int i = 0; i < 4; ++i) s.plan[i] = v[i]; }

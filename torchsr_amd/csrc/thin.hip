@@ -9,7 +9,9 @@
 // the 64 lanes of B hold the wide side: 75 % of the pipe does useful work and the thin operand is a
 // 4-address broadcast.  Same 64 FLOP/clk/SIMD rate as the 32x32 MFMA, exact fp32.
 #include "srx_common.h"
+#include "conv_host.h"
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <mutex>
 #include <cstdlib>
@@ -499,6 +501,60 @@ int thin_ranges(int nseg, int groups) {
   return ranges;
 }
 
+// ---- launch plans.  The ONE place that cuts them: the launch code below and srx_thin_plan read these and nothing else. ----
+
+// srx_thin_force_rows: rows per wave of thin_fwd2_kernel / thin_fwd2_bf16_kernel (0: the model's choice), seeded at first use from
+// SRX_THIN_FWD_ROWS (api.cpp keeps 0, 3, 4 and 6 and drops every other value with a line on stderr)
+std::atomic<int>& thin_force_rows() {
+  static std::atomic<int> rows{srx_dev().thin_fwd_rows};
+  return rows;
+}
+bool thin_rows_ok(int rows) { return rows == 0 || rows == 3 || rows == 4 || rows == 6; }
+
+// srx_thin_fwd (forward of the 64 -> <= 4 layers, data gradient of the <= 4 -> 64 layers): a workgroup owns 4 R x 32 output pixels
+struct ThinFwdPlan { int R, tiles_h, tiles_w, workgroups; };
+int thin_fwd_plan(const srx_conv2d_t* d, ThinFwdPlan& p) {
+  // rows per lane: 6 reads LDS least (23 b128 per 216 MFMAs) and wins whenever there are plenty of tiles; small
+  // images balance better over the CUs with 12-row tiles (R = 3).  srx_thin_force_rows / SRX_THIN_FWD_ROWS override (3, 4, 6).
+  const int forced = thin_force_rows().load(), cus = srx_plan_cus();
+  p.tiles_w = (int)srx_cdiv(d->W, 32);
+  const int64_t big_tiles = (int64_t)d->N * srx_cdiv(d->H, 24) * p.tiles_w;
+  p.R = thin_rows_ok(forced) && forced > 0 ? forced : (big_tiles >= 4 * cus ? 6 : 3);
+  if (p.R == 4 && d->precision == 2)  // (thin_fwd2_bf16_kernel exists with 3 and 6 rows)
+    SRX_FAIL(SRX_E_UNSUPPORTED, "thin_fwd: forced 4 rows per wave refused on a layer with bf16 products (precision = 2): no such kernel");
+  p.tiles_h = (int)srx_cdiv(d->H, 4 * p.R);
+  const int64_t wgs = (int64_t)d->N * p.tiles_h * p.tiles_w;
+  SRX_REQUIRE(wgs < (1LL << 31), "thin_fwd: more than 2^31 tiles");
+  p.workgroups = (int)wgs;
+  return SRX_OK;
+}
+
+// srx_thin_wgrad: segments = (image, row, 16-column block); a wave takes `segs_per_range` consecutive ones, the four waves of a
+// workgroup four consecutive ranges (one slab per workgroup and group of kernel rows); ranges past `nranges` are empty
+struct ThinWgradPlan { int groups, wsegs, nseg, ranges, segs_per_range, nranges, nslabs; };
+ThinWgradPlan thin_wgrad_plan(const srx_conv2d_t* d) {
+  ThinWgradPlan p;
+  p.groups = d->KH == 9 ? 3 : 1;
+  p.wsegs = (int)srx_cdiv(d->W, 16);
+  p.nseg = d->N * d->H * p.wsegs;
+  p.ranges = thin_ranges(p.nseg, p.groups);
+  p.segs_per_range = (int)srx_cdiv(p.nseg, p.ranges);
+  p.nranges = (int)srx_cdiv(p.nseg, p.segs_per_range);
+  p.nslabs = (int)srx_cdiv(p.nranges, 4);
+  return p;
+}
+
+// srx_first3_fwd: tiles of 32 pixels, a wave walks tile = 4 workgroup + wave, += 4 workgroups
+struct First3Plan { int ntiles, workgroups; };
+First3Plan first3_plan(const srx_conv2d_t* d) {
+  First3Plan p;
+  p.ntiles = (int)srx_cdiv((int64_t)d->N * d->H * d->W, 32);
+  // three workgroups per CU, each wave walking its share of the tiles: the weight prologue is paid 768 times, not 2304
+  const int cus = srx_plan_cus(), gdev = srx_dev().first3_wgs_per_cu;
+  p.workgroups = (int)std::min<int64_t>(srx_cdiv(p.ntiles, 4), (int64_t)cus * (gdev > 0 ? gdev : 3));
+  return p;
+}
+
 }  // namespace
 
 // ---- internal entry points used by the C ABI functions of gconv.hip, wgrad.hip and convpack.hip ----
@@ -511,9 +567,7 @@ bool srx_thin_wgrad_applicable(const srx_conv2d_t* d) {  // (the 3-channel layer
 }
 
 size_t srx_thin_wgrad_ws_floats(const srx_conv2d_t* d) {
-  const int nseg = d->N * d->H * (int)srx_cdiv(d->W, 16);
-  const int groups = d->KH == 9 ? 3 : 1;
-  return (size_t)srx_cdiv(thin_ranges(nseg, groups), 4) * 4 * d->KH * d->KW * 64;  // one slab per workgroup
+  return (size_t)srx_cdiv(thin_wgrad_plan(d).ranges, 4) * 4 * d->KH * d->KW * 64;  // one slab per workgroup
 }
 
 int srx_thin_wgrad(const srx_conv2d_t* d, const float* x, const float* dy, float* dw, int accumulate, float* ws,
@@ -525,16 +579,11 @@ int srx_thin_wgrad(const srx_conv2d_t* d, const float* x, const float* dy, float
   a.slab = ws;
   a.N = d->N; a.H = d->H; a.W = d->W;
   SRX_REQUIRE((size_t)d->N * d->H * d->W * 256 < 0xfffffff0ull, "conv2d_bwd_weight(thin): activation tensor above 4 GiB (32-bit buffer offsets)");
-  a.wsegs = (int)srx_cdiv(d->W, 16);
-  a.nseg = d->N * d->H * a.wsegs;
-  const int groups = d->KH == 9 ? 3 : 1;
-  const int ranges = thin_ranges(a.nseg, groups);
-  a.segs_per_range = (int)srx_cdiv(a.nseg, ranges);
-  const int nranges = (int)srx_cdiv(a.nseg, a.segs_per_range);
-  const int nslabs = (int)srx_cdiv(nranges, 4);
+  const ThinWgradPlan p = thin_wgrad_plan(d);
+  a.wsegs = p.wsegs; a.nseg = p.nseg; a.segs_per_range = p.segs_per_range; a.nranges = p.nranges;
+  const int groups = p.groups, nslabs = p.nslabs;
   if ((size_t)nslabs * 4 * d->KH * d->KW * 64 > ws_floats)
     SRX_FAIL(SRX_E_WORKSPACE, "conv2d_bwd_weight(thin): workspace too small");
-  a.nranges = nranges;
   const unsigned blocks = (unsigned)(nslabs * groups);
   char nm[64];
   if (srx_prof_on()) snprintf(nm, sizeof(nm), "thin_wgrad_kernel<%d, %d, %d, %d>", d->KH, d->KW, groups, thin_out ? -1 : 1);
@@ -600,14 +649,13 @@ int srx_first3_fwd(const srx_conv2d_t* d, const float* in, const float* wpk, int
   First3 a;
   a.in = in; a.w = wpk; a.bias = bias; a.out = out;
   a.H = d->H; a.W = d->W; a.HW = d->H * d->W; a.M = d->N * a.HW; a.Kp = Kp;
-  a.ntiles = (int)srx_cdiv(a.M, 32);
+  const First3Plan p = first3_plan(d);
+  a.ntiles = p.ntiles;
   a.inv_HW = 1.0f / (float)a.HW; a.inv_W = 1.0f / (float)a.W;
   a.slope = d->act == SRX_ACT_RELU ? 0.f : (d->act == SRX_ACT_LRELU ? d->slope : 1.f);  // v > 0 ? v : v * slope
   a.in_bytes = (unsigned)((size_t)a.M * 4 * sizeof(float));
   a.out_bytes = (unsigned)((size_t)a.M * 64 * (out_bf16 ? 2 : sizeof(float)));
-  // three workgroups per CU, each wave walking its share of the tiles: the weight prologue is paid 768 times, not 2304
-  const int cus = srx_plan_cus(), gdev = srx_dev().first3_wgs_per_cu;
-  const unsigned grid = (unsigned)std::min<int64_t>(srx_cdiv(a.ntiles, 4), (int64_t)cus * (gdev > 0 ? gdev : 3));
+  const unsigned grid = (unsigned)p.workgroups;
   char nm[64];
   if (srx_prof_on()) snprintf(nm, sizeof(nm), "first3x3_fwd_kernel<%d> MxNxK=%dx64x36", d->precision ? 1 : 0, a.M);
   if (out_bf16) {
@@ -641,16 +689,13 @@ int srx_thin_fwd(const srx_conv2d_t* d, const float* in, const float* wpk, const
   ThinF a;
   a.in = in; a.w = wpk; a.bias = bias; a.out = out;
   a.N = d->N; a.H = d->H; a.W = d->W; a.Cout = n_out;
-  a.tiles_w = (int)srx_cdiv(d->W, 32);
   a.in_bf16 = in_bf16;
   a.in_bytes = (unsigned)((size_t)d->N * d->H * d->W * 64 * (in_bf16 ? 2 : sizeof(float)));
   if (in_bf16 && d->precision != 2) SRX_FAIL(SRX_E_UNSUPPORTED, "thin_fwd: a bf16 input needs precision = 2 (bf16 products)");
-  // rows per lane: 6 reads LDS least (23 b128 per 216 MFMAs) and wins whenever there are plenty of tiles; small
-  // images balance better over the CUs with 12-row tiles (R = 3).  SRX_THIN_FWD_ROWS overrides (3, 4, 6).
-  const int dev = srx_dev().thin_fwd_rows, cus = srx_plan_cus();
-  const int64_t big_tiles = (int64_t)d->N * srx_cdiv(d->H, 24) * a.tiles_w;
-  const int R = dev > 0 ? dev : (big_tiles >= 4 * cus ? 6 : 3);
-  a.tiles_h = (int)srx_cdiv(d->H, 4 * R);
+  ThinFwdPlan p;
+  if (int rc = thin_fwd_plan(d, p)) return rc;  // (a forced form without a kernel: refused before any launch)
+  a.tiles_w = p.tiles_w; a.tiles_h = p.tiles_h;
+  const int R = p.R;  // 3, 4 or 6; 3 or 6 with bf16 products
   if (d->precision == 2) {  // bf16 products in the 3-channel layer too (inference)
     if (in_bf16) {
       if (d->KH == 9) return R == 3 ? launch_thin_fwd2_bf16<9, 3, true>(a, st) : launch_thin_fwd2_bf16<9, 6, true>(a, st);
@@ -661,4 +706,36 @@ int srx_thin_fwd(const srx_conv2d_t* d, const float* in, const float* wpk, const
   }
   if (d->KH == 9) return R == 3 ? launch_thin_fwd2<9, 3>(a, st) : (R == 6 ? launch_thin_fwd2<9, 6>(a, st) : launch_thin_fwd2<9, 4>(a, st));
   return R == 3 ? launch_thin_fwd2<3, 3>(a, st) : (R == 6 ? launch_thin_fwd2<3, 6>(a, st) : launch_thin_fwd2<3, 4>(a, st));
+}
+
+// which: 0 forward / 1 data gradient through srx_thin_fwd: out[4] = {R, tiles_h, tiles_w, workgroups}; 2 weight gradient:
+// out[5] = {groups, nseg, segs_per_range, nranges, nslabs}; 3 first3x3_fwd_kernel: out[2] = {ntiles, workgroups}.  Host code only:
+// the conditions are those of the dispatchers (conv_fwd_impl, conv_bwd_data_impl, wgrad_multi_impl), the numbers the launch code's.
+extern "C" int srx_thin_plan(const srx_conv2d_t* d, int which, int* out) {
+  if (int rc = check_desc(d)) return rc;
+  SRX_REQUIRE(out && which >= 0 && which <= 3, "thin_plan: which = 0..3 and a result array");
+  if (which == 0 || which == 1) {
+    if (!(which == 0 ? srx_thin_fwd_applicable(d) && d->up != 2 : srx_thin_dgrad_applicable(d) && d->precision != 3))
+      SRX_FAIL(SRX_E_UNSUPPORTED, "thin_plan: the layer's %s does not run on the 3-channel output kernel", which ? "data gradient" : "forward");
+    ThinFwdPlan p;
+    if (int rc = thin_fwd_plan(d, p)) return rc;
+    out[0] = p.R; out[1] = p.tiles_h; out[2] = p.tiles_w; out[3] = p.workgroups;
+  } else if (which == 2) {
+    if (!srx_thin_wgrad_applicable(d) || d->up == 2 || d->precision == 3)
+      SRX_FAIL(SRX_E_UNSUPPORTED, "thin_plan: the layer's weight gradient does not run on the 3-channel kernel");
+    const ThinWgradPlan p = thin_wgrad_plan(d);
+    out[0] = p.groups; out[1] = p.nseg; out[2] = p.segs_per_range; out[3] = p.nranges; out[4] = p.nslabs;
+  } else {
+    if (!srx_first3_fwd_applicable(d) || d->precision == 3 || d->act == SRX_ACT_PRELU)
+      SRX_FAIL(SRX_E_UNSUPPORTED, "thin_plan: the layer's forward does not run on the 3-channel first-layer kernel");
+    const First3Plan p = first3_plan(d);
+    out[0] = p.ntiles; out[1] = p.workgroups;
+  }
+  return SRX_OK;
+}
+
+extern "C" int srx_thin_force_rows(int rows) {
+  SRX_REQUIRE(thin_rows_ok(rows), "thin_force_rows: 0 (the model's choice), 3, 4 or 6 rows per wave");
+  thin_force_rows().store(rows);
+  return SRX_OK;
 }
