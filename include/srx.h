@@ -560,6 +560,24 @@ int srx_jpeg_sim(const float* in_nchw, float* out_nchw, const int32_t* quality, 
 int srx_usm_sharpen(const float* in, float* out, float* blur, float* mask, const float* taps, int ksize, int64_t planes, int H,
                     int W, float weight, float threshold, void* stream);
 
+/* ------------------------------------------------- training pair pool (pool.hip) */
+/* Real-ESRGAN's training pair pool (_dequeue_and_enqueue) in one launch ('Training pair pool').  pool_a: float
+ * [cap][elems_a], batch_a: float [n][elems_a]; the _b pair likewise with elems_b floats per sample.  _a is the low-resolution
+ * side and _b the target; both are moved by the SAME launch, so a low-resolution sample and its target never part.
+ * pool_b == batch_b == NULL with elems_b == 0: one tensor only.  slots: DEVICE int32 [n].
+ *   mode 0 (store):    pool[slots[i]] = batch[i]; the batch is left untouched
+ *   mode 1 (exchange): pool[slots[i]] and batch[i] change places in place (both read into registers, then both written)
+ * Values are moved as 32-bit words, 16 bytes at a time where elems % 4 == 0 and the bases are 16-byte aligned: every bit
+ * pattern arrives unchanged.  The kernel is safe for any value it finds in slots: a slot outside [0, cap) leaves sample i and
+ * the pool untouched.  DUPLICATE slots are a caller error: which of the samples ends up in the slot, and what the batch holds
+ * afterwards, is unspecified -- but every access stays inside the two buffers.  No atomics, no device state; the grid is sized
+ * from elems and n alone.
+ * Refused before anything is issued: a null pool_a, batch_a or slots; exactly one of pool_b / batch_b null, or a null pair with
+ * elems_b != 0 (or a given one with elems_b == 0); elems_a < 1 or elems_b < 0; n outside 1..65535; cap < 1 or n > cap;
+ * cap * elems >= 2^31 for either side; mode not 0 or 1; any two of the pool and batch ranges overlapping. */
+int srx_pool_exchange(float* pool_a, float* batch_a, int64_t elems_a, float* pool_b, float* batch_b, int64_t elems_b,
+                      const int32_t* slots, int n, int cap, int mode, void* stream);
+
 /* -------------------------------------------------------------- batch norm */
 /* nn.BatchNorm2d(C), eps 1e-5, momentum 0.1 (srgan/residual.py:65,68;
  * srgan/generator.py:49; srgan/discriminator.py:36-60).

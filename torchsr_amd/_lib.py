@@ -12,7 +12,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('SRX_LIB') or os.path.join(CSRC, 'libsrx_hip.so')  # SRX_LIB: developer A/B builds on one GPU box
-SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'degrade.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip', 'resample.hip', 'usm.hip']
+SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'degrade.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip', 'resample.hip', 'usm.hip', 'pool.hip']
 # headers the sources include, relative to CSRC: part of the build's digest and of every object's cache key
 HEADERS = ['srx_common.h', 'conv_host.h', os.path.join('..', '..', 'include', 'srx.h')]
 
@@ -229,6 +229,7 @@ _SIGS = {
     'srx_add_poisson_noise': (_I, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _I, _I, _P]),
     'srx_jpeg_sim': (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     'srx_usm_sharpen': (_I, [_P, _P, _P, _P, _P, _I, _L, _I, _I, _F, _F, _P]),
+    'srx_pool_exchange': (_I, [_P, _P, _L, _P, _P, _L, _P, _I, _I, _I, _P]),
     'srx_act_bwd_from_out': (_I, [_P, _P, _P, _L, _I, _F, _P]),
     'srx_act_bwd_from_out_strided': (_I, [_P, _I, _P, _I, _P, _I, _L, _I, _I, _F, _P]),
     'srx_prelu_fwd': (_I, [_P, _P, _P, _L, _P]),

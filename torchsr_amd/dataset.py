@@ -92,8 +92,8 @@ class DeviceLoader:
     """
 
     def __init__(self, images, device, batch_size: int, crop_size: int, upscale_factor: int, test: bool, seed: int,
-                 multiplier: int = 1, rank: int = 0, world_size: int = 1, gt_usm: bool = False, poisson_prob: float = 0.0,
-                 degradation: str = 'bicubic'):
+                 multiplier: int = 1, rank: int = 0, world_size: int = 1, gt_usm: bool = False, pair_pool: int = 0,
+                 poisson_prob: float = 0.0, degradation: str = 'bicubic'):
         from . import _lib
         if degradation not in DEGRADATIONS:
             raise ValueError(f'DeviceLoader: degradation must be one of {DEGRADATIONS}, got {degradation!r}')
@@ -118,6 +118,19 @@ class DeviceLoader:
         if poisson_prob > 0 and degradation not in ('blind', 'blind2'):
             raise ValueError(f'DeviceLoader: poisson_prob needs degradation blind or blind2 (bicubic adds no noise), got '
                              f'{degradation!r}')
+        if isinstance(pair_pool, bool) or not isinstance(pair_pool, int) or pair_pool < 0:
+            raise ValueError(f'DeviceLoader: pair_pool must be a non-negative int (pairs in the pool; 0: off), got {pair_pool!r}')
+        if pair_pool > 0:
+            if test:
+                raise ValueError('DeviceLoader: pair_pool is for train loaders (a test loader yields its own batches)')
+            if degradation not in ('blind', 'blind2'):
+                raise ValueError(f'DeviceLoader: pair_pool needs degradation blind or blind2 (bicubic batches share no drawn '
+                                 f'parameters to mix), got {degradation!r}')
+            if batch_size < 1 or pair_pool % batch_size:
+                b = max(batch_size, 1)
+                below, above = pair_pool // b * b, -(-pair_pool // b) * b
+                raise ValueError(f'DeviceLoader: pair_pool must be a multiple of the batch size {batch_size} (every step takes a whole '
+                                 f'batch out of a full pool), got {pair_pool}; the nearest are {below}{"" if below else " (off)"} and {above}')
         self._lib = _lib
         self.device, self.batch, self.crop, self.up, self.test = device, batch_size, crop_size, upscale_factor, test
         self.images = [self._fit(im).to(device) for im in images]          # uint8 [H][W][3]
@@ -136,6 +149,12 @@ class DeviceLoader:
         # one, and its scale, come from a third stream, so the two above are what they were ('Poisson noise')
         self.poisson_prob = float(poisson_prob)
         self.poi_rng = random.Random(seed * 32452843 + rank + 472882027) if self.poisson_prob > 0 else None
+        # train batches with ``pair_pool`` > 0 only: the pool's slots come from a fourth stream, so the three above produce exactly the
+        # pairs they produce without a pool; only the order in which pairs reach the trainer changes ('Training pair pool')
+        self.pair_pool = pair_pool
+        self.pool_rng = random.Random(seed * 49979687 + rank + 715225739) if pair_pool > 0 else None
+        self.pool_lr = self.pool_hr = None     # [pair_pool, 3, crop / scale, crop / scale] and [pair_pool, 3, crop, crop], made at the first batch
+        self.pool_filled = 0                   # pairs stored so far; the pool outlives the epochs
         self.last_degradation = None
         self.epoch = 0
 
@@ -304,6 +323,29 @@ class DeviceLoader:
         deg['poisson_scale'] = scale
         return deg
 
+    def _draw_pool_slots(self):
+        """The pool's part of the next train batch: ``(slots, mode)`` for ``srx_pool_exchange``.  While the pool fills -- its first
+        ``pair_pool / batch`` batches -- the next free slots in order and mode 0 (store: the batch is yielded as generated, what
+        basicsr does until its queue is full), with no draw; from then on ``batch`` distinct uniform slots from the pool stream
+        and mode 1 (exchange).  Real-ESRGAN shuffles its pool, takes the first ``batch`` pairs and puts the new ones in their
+        place: the same distribution of what is dequeued, without moving the other pairs."""
+        if self.pool_filled < self.pair_pool:
+            slots = list(range(self.pool_filled, self.pool_filled + self.batch))
+            self.pool_filled += self.batch
+            return slots, 0
+        return self.pool_rng.sample(range(self.pair_pool), self.batch), 1
+
+    def _pool(self, lr, hr):
+        """A generated train batch through the pair pool: stored (while the pool fills) or exchanged in place for ``batch`` pooled
+        pairs; returns ``(lr, hr)``, the tensors it was given.  The pool tensors are made at the first batch."""
+        from . import functional as F
+        if self.pool_lr is None:
+            self.pool_lr = torch.empty((self.pair_pool,) + tuple(lr.shape[1:]), dtype=torch.float32, device=lr.device)
+            self.pool_hr = torch.empty((self.pair_pool,) + tuple(hr.shape[1:]), dtype=torch.float32, device=hr.device)
+        slots, mode = self._draw_pool_slots()
+        with torch.no_grad():
+            return F.pool_exchange(self.pool_lr, self.pool_hr, lr, hr, slots, exchange=bool(mode))
+
     def _plan(self):
         """Host side of one epoch: per batch the sample indices, the crop / flip rows and -- ``blind`` and ``blind2`` train batches
         only, and after the rows, from the other stream -- the degradation parameters (else None); with ``poisson_prob`` > 0 their
@@ -402,7 +444,8 @@ class DeviceLoader:
                     hr = F.usm_sharpen(hr)
             if deg is not None:
                 self.last_degradation = deg
-                yield (self._degrade2 if self.degradation == 'blind2' else self._degrade)(hr, deg, stream), hr
+                lr = (self._degrade2 if self.degradation == 'blind2' else self._degrade)(hr, deg, stream)
+                yield self._pool(lr, hr) if self.pair_pool else (lr, hr)
                 continue
             lc = self.crop // self.up
             lr = torch.empty((len(idx), 3, lc, lc), dtype=torch.float32, device=dev)
@@ -423,14 +466,15 @@ def _decode(path: str) -> torch.Tensor:
 
 def initialize_device_datasets(train_directory: str, device, batch_size: int = 64, crop_size: int = 96,
                                upscale_factor: int = 4, dataset_multiplier: int = 1, distributed: bool = False,
-                               seed: int = 0, rank: int = 0, world_size: int = 1, gt_usm: bool = False,
+                               seed: int = 0, rank: int = 0, world_size: int = 1, gt_usm: bool = False, pair_pool: int = 0,
                                poisson_prob: float = 0.0, degradation: str = 'bicubic'):
     """``initialize_datasets`` with the augmentation on the device (``--device-data``).  ``synthetic:N`` draws N
     seeded random 2*crop x 2*crop images.  ``degradation='blind'`` degrades the TRAIN batches' low-resolution side with blur,
     noise and JPEG (``--degradation``), ``'blind2'`` with the second-order recipe; ``gt_usm`` unsharp-masks the TRAIN batches'
     high-resolution crop, which is then both the target and what is degraded (``--gt-usm``); ``poisson_prob`` gives each sample of
     each noise stage of ``blind`` / ``blind2`` Poisson noise with that probability in place of the Gaussian one
-    (``--poisson-noise-prob``); the test loader stays bicubic and unsharpened."""
+    (``--poisson-noise-prob``); ``pair_pool`` > 0 sends the TRAIN batches through a pool of that many pairs, so that a step sees
+    pairs of several generated batches (``--pair-pool``); the test loader stays bicubic and unsharpened and never has a pool."""
     if train_directory.startswith('synthetic:'):
         n = int(train_directory.split(':')[1])
         g = torch.Generator().manual_seed(seed)
@@ -446,7 +490,8 @@ def initialize_device_datasets(train_directory: str, device, batch_size: int = 6
     if not distributed:
         rank, world_size = 0, 1
     train = DeviceLoader(images[n_test:] or images, device, batch_size, crop_size, upscale_factor, False, seed,
-                         dataset_multiplier, rank, world_size, degradation=degradation, gt_usm=gt_usm, poisson_prob=poisson_prob)
+                         dataset_multiplier, rank, world_size, degradation=degradation, gt_usm=gt_usm, poisson_prob=poisson_prob,
+                         pair_pool=pair_pool)
     # dataset.py:343-360: the test set is multiplied like the train set, sharded over the ranks, nothing dropped
     test = DeviceLoader(images[:n_test], device, batch_size, crop_size, upscale_factor, True, seed + 1,
                         dataset_multiplier, rank, world_size)

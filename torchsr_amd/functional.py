@@ -792,6 +792,57 @@ def add_poisson_noise(x: Tensor, scale, gray, seed: int, quantize: bool = False)
     return out, levels
 
 
+def pool_exchange(pool_lr: Tensor, pool_hr: Optional[Tensor], lr: Tensor, hr: Optional[Tensor], slots, exchange: bool = True):
+    """Real-ESRGAN's training pair pool in one ``srx_pool_exchange`` launch: sample ``i`` of the batch ``(lr, hr)`` and slot
+    ``slots[i]`` of the pool ``(pool_lr, pool_hr)`` change places IN PLACE (``exchange=True``), or the sample is stored in the slot
+    and the batch left as it is (``exchange=False``, while a pool fills).  ``pool_*`` are ``[cap, ...]``, the batch tensors
+    ``[n, ...]`` with the same per-sample shape, ``n <= cap``; ``slots`` is a host sequence of ``n`` distinct ints in
+    ``[0, cap)``.  Both sides move in the same launch, so a low-resolution sample and its target never part; ``pool_hr`` and
+    ``hr`` may both be None (one tensor only).  Everything is checked on the host before the device is touched.  Returns
+    ``(lr, hr)``, the same tensors, now holding the dequeued pairs.  Moves bits only.  No backward."""
+    if (pool_hr is None) != (hr is None):
+        raise ValueError('pool_exchange: pool_hr and hr must both be given or both be None')
+    sides = [('lr', pool_lr, lr)] + ([('hr', pool_hr, hr)] if hr is not None else [])
+    for name, pool, batch in sides:
+        for what, t in ((f'pool_{name}', pool), (name, batch)):
+            if not isinstance(t, Tensor):
+                raise ValueError(f'pool_exchange: {what} must be a tensor, got {type(t).__name__}')
+            if t.requires_grad:
+                raise RuntimeError(f'pool_exchange: no backward; {what} requires grad')
+            if t.dtype != torch.float32:
+                raise RuntimeError(f'pool_exchange: {what}: expected float32, got {t.dtype}')
+            if not t.is_contiguous():
+                raise RuntimeError(f'pool_exchange: {what} must be contiguous (it is moved in place), got strides {t.stride()}')
+            if t.device != pool_lr.device:
+                raise RuntimeError(f'pool_exchange: {what} is on {t.device}, pool_lr on {pool_lr.device}: one device for all')
+        if pool.dim() < 2 or batch.dim() != pool.dim() or tuple(pool.shape[1:]) != tuple(batch.shape[1:]):
+            raise ValueError(f'pool_exchange: pool_{name} {tuple(pool.shape)} and {name} {tuple(batch.shape)} must be [cap, ...] and '
+                             f'[n, ...] with one per-sample shape')
+    cap, n = int(pool_lr.shape[0]), int(lr.shape[0])
+    if hr is not None and (int(pool_hr.shape[0]) != cap or int(hr.shape[0]) != n):
+        raise ValueError(f'pool_exchange: the two sides must agree in capacity and batch size, got pools of {cap} and '
+                         f'{int(pool_hr.shape[0])}, batches of {n} and {int(hr.shape[0])}')
+    elems = [int(pool[0].numel()) if cap else 0 for _, pool, _ in sides] + [0]
+    if n < 1 or n > 65535 or n > cap or elems[0] < 1 or (hr is not None and elems[1] < 1):
+        raise ValueError(f'pool_exchange: the batch size must be in 1..65535 and at most the capacity, the samples non-empty; got '
+                         f'batch {n}, capacity {cap}, {elems[0]} and {elems[1]} values per sample')
+    if cap * max(elems) >= 1 << 31:
+        raise ValueError(f'pool_exchange: a pool of {cap} x {max(elems)} values holds 2^31 or more')
+    slots = list(slots)
+    if len(slots) != n:
+        raise ValueError(f'pool_exchange: {len(slots)} slots for a batch of {n}')
+    for s in slots:
+        if isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < cap:
+            raise ValueError(f'pool_exchange: every slot must be an int in [0, {cap}), got {s!r}')
+    if len(set(slots)) != n:
+        raise ValueError(f'pool_exchange: the slots must be distinct, got {slots}')
+    _chk(pool_lr, 'pool_exchange.pool_lr')  # the device: no CPU fallback
+    slots_dev = torch.tensor(slots, dtype=torch.int32).to(lr.device)
+    call('srx_pool_exchange', _p(pool_lr), _p(lr), elems[0], _p(pool_hr), _p(hr), elems[1], _p(slots_dev), n, cap,
+         int(bool(exchange)), _stream())
+    return lr, hr
+
+
 # --------------------------------------------------------------------------- conv2d
 class WeightPack:
     """One packed layout of a layer's (or a chain of layers') weights: the forward buffer, the optional backward one, the key

@@ -56,6 +56,16 @@ def probability(value: str) -> float:
     return float_value
 
 
+def non_negative_integer(value: str) -> int:
+    try:
+        int_value = int(value)
+    except (TypeError, ValueError):
+        raise ArgumentTypeError(f'invalid int value: \'{value}\'')
+    if int_value < 0:
+        raise ArgumentTypeError('value must be a non-negative integer!')
+    return int_value
+
+
 def get_device(args: Namespace) -> torch.device:
     """torchsr.py:69-98."""
     count = torch.cuda.device_count()
@@ -141,6 +151,13 @@ def parse_args(argv=None) -> Namespace:
                        help='with --device-data and --degradation blind or blind2: the probability with which a sample of a '
                             'noise stage gets signal-dependent Poisson (shot) noise, the noise of dark photos, in place of the '
                             'stage\'s Gaussian noise.  Real-ESRGAN uses 0.5; the default 0 leaves the degradation as it was')
+    train.add_argument('--pair-pool', type=non_negative_integer, default=0, metavar='N',
+                       help='with --device-data and --degradation blind or blind2: keep a pool of N degraded training pairs in HBM '
+                            '(Real-ESRGAN\'s training pair pool).  blind2 draws its resize factors, modes and order once per batch; '
+                            'with the pool every step stores its fresh pairs in random slots and trains on the pairs it finds '
+                            'there, so one step sees several of those draws.  N must be a multiple of --batch-size (Real-ESRGAN: '
+                            '180 at batch 12); the first N / batch steps fill the pool and train on their own batches.  The pool is '
+                            'per process and is not checkpointed: a resumed run fills it again.  The default 0 is off')
     train.add_argument('--clip-grad-norm', type=positive_float, default=None, metavar='FLOAT',
                        help='clip the global l2 norm of each model\'s gradient to FLOAT before its Adam step '
                             '(torch.nn.utils.clip_grad_norm_, computed on the GPU inside the captured step; default: off)')
@@ -167,6 +184,15 @@ def parse_args(argv=None) -> Namespace:
     if args.function == 'train' and args.poisson_noise_prob > 0 and not (args.device_data and args.degradation in ('blind', 'blind2')):
         parser.error('--poisson-noise-prob replaces the Gaussian noise of a blind degradation: add --device-data and '
                      '--degradation blind or --degradation blind2')
+    if args.function == 'train' and args.pair_pool > 0:
+        if not (args.device_data and args.degradation in ('blind', 'blind2')):
+            parser.error('--pair-pool pools the pairs of a blind degradation: add --device-data and --degradation blind or '
+                         '--degradation blind2')
+        if args.batch_size < 1 or args.pair_pool % args.batch_size:
+            b = max(args.batch_size, 1)
+            nearest = sorted({m for m in (args.pair_pool // b * b, -(-args.pair_pool // b) * b) if m > 0})
+            parser.error(f'--pair-pool must be a multiple of --batch-size {args.batch_size} (every step takes a whole batch out of '
+                         f'the full pool), got {args.pair_pool}; nearest: {" and ".join(map(str, nearest))}')
     if args.function == 'train' and args.degradation in ('blind', 'blind2') and not args.device_data:
         parser.error(f'--degradation {args.degradation} needs --device-data (the host DataLoader path has no blind degradation)')
     if args.function == 'train' and args.gt_usm and not args.device_data:
@@ -219,7 +245,11 @@ def main(argv=None) -> None:
             args.train_dir, device, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=4,
             dataset_multiplier=args.dataset_multiplier, distributed=distributed, seed=args.seed,
             rank=max(int(args.rank), 0) if distributed else 0, world_size=int(args.world_size) if distributed else 1,
-            degradation=args.degradation, gt_usm=args.gt_usm, poisson_prob=args.poisson_noise_prob)
+            degradation=args.degradation, gt_usm=args.gt_usm, poisson_prob=args.poisson_noise_prob, pair_pool=args.pair_pool)
+        if args.pair_pool and args.rank in [-1, 0]:
+            per_pair = 4 * 3 * (crop_size * crop_size + (crop_size // 4) ** 2)
+            print(f'training pair pool: {args.pair_pool} pairs per process, {args.pair_pool * per_pair / 1e6:.1f} MB of HBM; the first '
+                  f'{args.pair_pool // args.batch_size} steps fill it')
     else:
         train_loader, test_loader, train_len, test_len = initialize_datasets(
             args.train_dir, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=4,
