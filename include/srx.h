@@ -175,12 +175,12 @@ int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out);
 
 /* Plan overrides for tests and tile experiments (no reference counterpart).  They hold for every later call of this process until
  * reset with zeros (srx_wgrad_force: (-1, 0)); the environment seeds them at load (SRX_FORCE_PLAN="BM,BN,split,ks", SRX_S2_MODE bit 0,
- * SRX_NO_WGRAD_LIN, SRX_WGRAD_NSPLIT, SRX_THIN_FWD_ROWS).  srx_conv2d_plan, srx_thin_plan and the workspace queries report what a
- * forced call runs.  A forced form a
+ * SRX_NO_WGRAD_LIN, SRX_WGRAD_NSPLIT, SRX_THIN_FWD_ROWS; srx_linear_force has no environment seed).  srx_conv2d_plan, srx_thin_plan,
+ * srx_linear_plan and the workspace queries report what a forced call runs.  A forced form a
  * layer has no kernel for (tile not instantiated at the layer's arithmetic, BN not dividing the padded columns, 144 rows with bf16
  * products, the fused kernel on a layer it cannot run, more row splits than the rows allow, 4 rows per wave on a 3-channel output
- * layer with bf16 products) is refused with SRX_E_UNSUPPORTED and
- * a message when that layer is planned or called, before anything is launched.
+ * layer with bf16 products, the fast linear form on a launch that cannot take it, more linear splits than there are trips) is
+ * refused with SRX_E_UNSUPPORTED and a message when that layer is planned or called, before anything is launched.
  * srx_conv2d_force_plan: every gconv_kernel / gconv_multi_kernel plan (not the whole-frame calls above 2^24 pixels) is BM x BN
  *   (BM = 144: the 128 + 16 row tile), every tile K-split `split` ways where the output is linear (strided / shuffled outputs run
  *   unsplit), KS = 2: two wave groups on the 64 x 64 tile (64 x 32 always has 2, or 4 with bf16 products).
@@ -191,11 +191,17 @@ int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out);
  * srx_thin_force_rows: the 3-channel output kernel (forward of the 64 -> <= 4 channel layers, data gradient of the <= 4 -> 64
  *   ones) -- 3, 4 or 6 output rows per wave, i.e. tiles of 12, 16 or 24 rows x 32 pixels; 0: the model's (6 from four tiles of
  *   24 rows per plan CU on, else 3).  Any other value is refused (SRX_THIN_FWD_ROWS: ignored with a line on stderr); the
- *   kernel with bf16 products (precision = 2) exists with 3 and 6 rows. */
+ *   kernel with bf16 products (precision = 2) exists with 3 and 6 rows.
+ * srx_linear_force: nn.Linear (linear.hip) -- form 0 the model's choice, 1 always the plain kernels (linear_*_kernel), 2 the fast
+ *   kernels (linear_*_fast_kernel) wherever they may run: K a multiple of 64, J a multiple of 16 for the two gradients, at most
+ *   32 rows in a 64-row launch of the forward / data gradient; a launch that cannot is refused, never downgraded.  splits > 0:
+ *   that many K splits of the forward / J splits of the data gradient before the rounding to whole trips of 256 / 16 (more than
+ *   cdiv(K, 256) / cdiv(J, 16) is refused by that pass), 0: the model's.  Reset with (0, 0). */
 int srx_conv2d_force_plan(int bm, int bn, int split, int ks);
 int srx_conv2d_force_s2(int mode, int bm, int bn);
 int srx_wgrad_force(int lin, int nsplit);
 int srx_thin_force_rows(int rows);
+int srx_linear_force(int form, int splits);
 
 /* Launch plan of the kernels with a <= 4-channel side (thin.hip), computed by the function the launches themselves plan with;
  * host code only.  which = 0 forward of a 64 -> <= 4 channel layer, 1 data gradient of a <= 4 -> 64 channel layer (both
@@ -206,6 +212,13 @@ int srx_thin_force_rows(int rows);
  * channel layer (first3x3_fwd_kernel): out[2] = {tiles of 32 pixels, workgroups}; a wave walks tile = 4 workgroup + wave, += 4
  * workgroups.  SRX_E_UNSUPPORTED when the layer does not take that path, or is forced to a form it has no kernel for. */
 int srx_thin_plan(const srx_conv2d_t* d, int which, int* out);
+
+/* Launch plan of nn.Linear (linear.hip), computed by the function the launches themselves plan with; host code only.  which = 0
+ * forward, 1 data gradient: out[6] = {splits launched (slabs of partial sums), contraction elements per split (k / j), launches
+ * of up to 64 rows, 16-row blocks NB of the last launch, form of the first launch (1 plain, 2 fast), form of the last launch}.
+ * which = 2 weight gradient: out[6] = {1, 0, 1, batch trips of 32 rows, form, form}.  SRX_E_UNSUPPORTED for what srx_linear_force
+ * asked for and the shape cannot run. */
+int srx_linear_plan(int B, int K, int J, int which, int* out);
 
 /* OIHW master weights -> packed forward ([Cout_p][K_p], K=(kh,kw,ci)) and, when
  * wpk_bwd != NULL, packed data-gradient operands (per stride-parity class,
@@ -704,7 +717,9 @@ int srx_maxpool2x2_relu_bwd(const float* dy, const float* x, float* dx, int N, i
 
 /* ------------------------------------------------------------------ linear */
 /* nn.Linear (srgan/discriminator.py:65,67; esrgan/discriminator.py:73,75).
- * x [B][K], w [J][K] (reference layout), y [B][J] = act(x w^T + bias) */
+ * x [B][K], w [J][K] (reference layout), y [B][J] = act(x w^T + bias)
+ * ws: srx_linear_ws_floats floats -- the slabs of the forward's and the data gradient's splits, under srx_linear_force those
+ * of the forced plan */
 size_t srx_linear_ws_floats(int B, int K, int J);
 int srx_linear_fwd(const float* x, const float* w, const float* bias, float* y, int B, int K, int J,
                    int act, float slope, float* ws, size_t ws_floats, void* stream);

@@ -1,0 +1,46 @@
+"""Device tensors with owned surroundings, and the elementwise comparison, for the tests that watch what a kernel reads and writes
+next to its tensors (test_linear_forms_gpu.py, test_head_gpu.py)."""
+import ctypes as C
+
+import torch
+
+SENTINEL = 12345.6789
+
+
+class Guarded:
+    """A contiguous view of `shape` inside a larger device buffer: 64 rows of its own row length (or `margin_floats`) on either
+    side, 16-byte aligned.  Inputs: NaN margins.  Outputs: sentinel margins, a NaN (or given) interior."""
+
+    def __init__(self, dev, shape, src=None, margin=float('nan'), margin_floats=None):
+        n = 1
+        for s in shape:
+            n *= s
+        self.m = 64 * shape[-1] if margin_floats is None else margin_floats
+        self.margin = margin
+        self.buf = torch.full((2 * self.m + n,), margin, dtype=torch.float32, device=dev)
+        self.t = self.buf[self.m:self.m + n].view(shape)
+        self.t.fill_(float('nan'))
+        if src is not None:
+            self.t.copy_(src)
+        assert self.t.data_ptr() % 16 == 0 and self.t.is_contiguous()
+
+    def ptr(self):
+        return C.c_void_p(self.t.data_ptr())
+
+    def margins_unchanged(self):
+        want = torch.tensor(self.margin, dtype=torch.float32).view(torch.int32).item()
+        got = torch.cat([self.buf[:self.m], self.buf[-self.m:]]).view(torch.int32)
+        return bool((got == want).all())
+
+
+def within(got, ref, bound, what):
+    """elementwise, NaN-proof: every element of `got` within its own bound"""
+    err = (got.double() - ref).abs()
+    bound = torch.as_tensor(bound, dtype=torch.float64).expand_as(err)
+    ok = err <= bound
+    if not bool(ok.all()):
+        bad = (~ok).nonzero()
+        i = tuple(bad[0].tolist())
+        raise AssertionError('%s: %d of %d elements outside their bound; first at %s: got %r, fp64 %r, bound %.3e; worst err / bound %.3f'
+                             % (what, len(bad), ok.numel(), i, float(got[i]), float(ref[i]), float(bound[i]),
+                                float((err / bound).nan_to_num(float('inf')).max())))

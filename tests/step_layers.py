@@ -353,8 +353,10 @@ OP_ARGS = {
 }
 # srx_* launches that are neither convolutions nor in the four files above, and the op-level tests that hold them
 OPS_TESTED_ELSEWHERE = {
-    'srx_linear_fwd': 'test_ops_gpu.py::test_linear', 'srx_linear_bwd_data': 'test_ops_gpu.py::test_linear',
-    'srx_linear_bwd_weight': 'test_ops_gpu.py::test_linear', 'srx_gan_head_fwd': 'test_head_gpu.py', 'srx_gan_head_bwd': 'test_head_gpu.py',
+    'srx_linear_fwd': 'test_linear_forms_gpu.py (every launch form, fp64), test_ops_gpu.py::test_linear',
+    'srx_linear_bwd_data': 'test_linear_forms_gpu.py, test_ops_gpu.py::test_linear',
+    'srx_linear_bwd_weight': 'test_linear_forms_gpu.py, test_ops_gpu.py::test_linear',
+    'srx_gan_head_fwd': 'test_head_gpu.py', 'srx_gan_head_bwd': 'test_head_gpu.py',
     'srx_ring_push': 'test_step_gpu.py (one thread, no shape)', 'srx_crop_flip_u8': 'test_ops_gpu.py', 'srx_bicubic_down': 'test_ops_gpu.py',
 }
 _CONV_PREFIXES = ('srx_conv', 'srx_wino', 'srx_pack_table', 'srx_rdb', 'srx_prof', 'srx_f32_to', 'srx_bf16_to', 'srx_f16_to',

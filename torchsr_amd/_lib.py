@@ -173,6 +173,8 @@ _SIGS = {
     'srx_thin_force_rows': (_I, [_I]),
     'srx_conv2d_force_s2': (_I, [_I, _I, _I]),
     'srx_wgrad_force': (_I, [_I, _I]),
+    'srx_linear_force': (_I, [_I, _I]),
+    'srx_linear_plan': (_I, [_I, _I, _I, _I, C.POINTER(C.c_int)]),
     'srx_pack_table_bytes': (_Z, [_I]),
     'srx_pack_table_build': (_I, [_P, _I, _P, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     'srx_pack_table_add_wino': (_I, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong), _D, _P, _P, _I]),

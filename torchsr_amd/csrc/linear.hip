@@ -8,6 +8,7 @@
 // MFMA 16x16x4 maps: A[i=l&15][k=l>>4], B[k=l>>4][j=l&15], D: col=l&15, row=4*(l>>4)+reg.
 #include "srx_common.h"
 #include <algorithm>
+#include <atomic>
 
 namespace {
 
@@ -423,11 +424,79 @@ int bwd_splits(int K, int J, int B) {
   return (int)s;
 }
 
+// ---- launch plans.  The ONE place that cuts them: the launch loops below and srx_linear_plan read these and nothing else. ----
+
+// srx_linear_force: {form, splits}, both 0 = the model's choice
+std::atomic<int>& linear_force(int i) {
+  static std::atomic<int> f[2]{{0}, {0}};
+  return f[i];
+}
+
+// form (1 plain / 2 fast) and NB (16-row blocks) of the launch that covers rows [b0, b0 + 64); 0: a forced fast form this launch
+// cannot take (the caller refuses).  The weight gradient is one launch over every row: nb is not used there.
+int linear_launch_form(int B, int K, int J, int b0, bool need_j16, bool whole_batch, int* nb) {
+  *nb = (int)srx_cdiv(std::min(B - b0, 64), 16);
+  const int force = linear_force(0).load(std::memory_order_relaxed);
+  const bool can = linear_fast_ok(B, K, J, need_j16) && (whole_batch || *nb <= 2);
+  if (force == 2 && !can) return 0;
+  return can && force != 1 ? 2 : 1;
+}
+
+// which = 0 forward, 1 data gradient: nsplit slabs of B x J / B x K partials, `per` contraction elements each, one launch per 64
+// rows.  which = 2 weight gradient: one launch, `trips` batch trips of 32 rows in the fast form.
+struct LinearPlan { int nsplit, per, launches, nb_last, form_first, form_last, trips; };
+int linear_plan(int B, int K, int J, int which, LinearPlan& p) {
+  static const char* const who[3] = {"linear_fwd", "linear_bwd_data", "linear_bwd_weight"};
+  p = LinearPlan{1, 0, 1, 0, 0, 0, (int)srx_cdiv(B, 32)};
+  if (which == 2) {
+    p.form_first = p.form_last = linear_launch_form(B, K, J, 0, true, true, &p.nb_last);
+    if (!p.form_first)
+      SRX_FAIL(SRX_E_UNSUPPORTED, "%s: forced fast form refused for B = %d, K = %d, J = %d: it needs K a multiple of 64, J a multiple of 16 and tensors below 4 GiB", who[2], B, K, J);
+    p.nb_last = p.trips;
+    return SRX_OK;
+  }
+  const int forced = linear_force(1).load(std::memory_order_relaxed);
+  const int unit = which ? 16 : 256, len = which ? J : K;  // (a split is whole 256-wide k trips / 16-wide j trips)
+  if (forced > srx_cdiv(len, unit))
+    SRX_FAIL(SRX_E_UNSUPPORTED, "%s: %d forced splits refused: %s = %d has %d trips of %d", who[which], forced, which ? "J" : "K", len, (int)srx_cdiv(len, unit), unit);
+  const int ns = forced > 0 ? forced : (which ? bwd_splits(K, J, B) : fwd_splits(K, J, B));
+  p.per = (int)srx_roundup(srx_cdiv(len, ns), unit);
+  p.nsplit = (int)srx_cdiv(len, p.per);
+  p.launches = (int)srx_cdiv(B, 64);
+  for (int b0 = 0; b0 < B; b0 += 64) {
+    const int form = linear_launch_form(B, K, J, b0, which == 1, false, &p.nb_last);
+    if (!form)
+      SRX_FAIL(SRX_E_UNSUPPORTED, "%s: forced fast form refused for rows %d.. of B = %d, K = %d, J = %d: it needs K a multiple of 64%s, at most 32 rows in the launch and tensors below 4 GiB",
+               who[which], b0, B, K, J, which ? ", J a multiple of 16" : "");
+    if (b0 == 0) p.form_first = form;
+    p.form_last = form;
+  }
+  return SRX_OK;
+}
+
 }  // namespace
 
+extern "C" int srx_linear_force(int form, int splits) {
+  SRX_REQUIRE(form >= 0 && form <= 2 && splits >= 0, "linear_force: form 0 / 1 / 2, splits >= 0");
+  linear_force(0).store(form);
+  linear_force(1).store(splits);
+  return SRX_OK;
+}
+
+extern "C" int srx_linear_plan(int B, int K, int J, int which, int* out) {
+  SRX_REQUIRE(out && B > 0 && K > 0 && J > 0 && which >= 0 && which <= 2, "linear_plan: bad argument");
+  LinearPlan p;
+  if (int rc = linear_plan(B, K, J, which, p)) return rc;
+  out[0] = p.nsplit; out[1] = p.per; out[2] = p.launches; out[3] = p.nb_last; out[4] = p.form_first; out[5] = p.form_last;
+  return SRX_OK;
+}
+
+// (a pass that the forcing refuses cannot run and needs nothing)
 extern "C" size_t srx_linear_ws_floats(int B, int K, int J) {
-  const size_t f = (size_t)fwd_splits(K, J, B) * B * J;
-  const size_t b = (size_t)bwd_splits(K, J, B) * B * K;
+  if (B <= 0 || K <= 0 || J <= 0) return 0;
+  LinearPlan p;
+  const size_t f = linear_plan(B, K, J, 0, p) == SRX_OK ? (size_t)p.nsplit * B * J : 0;
+  const size_t b = linear_plan(B, K, J, 1, p) == SRX_OK ? (size_t)p.nsplit * B * K : 0;
   return f > b ? f : b;
 }
 
@@ -435,15 +504,15 @@ extern "C" int srx_linear_fwd(const float* x, const float* w, const float* bias,
                               float slope, float* ws, size_t ws_floats, void* stream) {
   SRX_REQUIRE(x && w && y && ws && B > 0 && K > 0 && J > 0, "linear_fwd: bad argument");
   SRX_REQUIRE(K % 4 == 0, "linear_fwd: in_features must be a multiple of 4");
-  const int ns = fwd_splits(K, J, B);
-  if ((size_t)ns * B * J > ws_floats) SRX_FAIL(SRX_E_WORKSPACE, "linear_fwd: workspace too small");
-  const int kper = (int)srx_roundup(srx_cdiv(K, ns), 256);
-  const int nsplit = (int)srx_cdiv(K, kper);
+  LinearPlan p;
+  if (int rc = linear_plan(B, K, J, 0, p)) return rc;
+  if ((size_t)p.nsplit * B * J > ws_floats) SRX_FAIL(SRX_E_WORKSPACE, "linear_fwd: workspace too small");
+  const int kper = p.per, nsplit = p.nsplit;
   hipStream_t st = srx_stream(stream);
   for (int b0 = 0; b0 < B; b0 += 64) {  // up to four 16-row blocks per launch share one pass over the weight
     const dim3 grid((unsigned)srx_cdiv(J, 16), nsplit);
-    const int nb = (int)srx_cdiv(std::min(B - b0, 64), 16);
-    if (linear_fast_ok(B, K, J, false) && nb <= 2) {
+    int nb;
+    if (linear_launch_form(B, K, J, b0, false, false, &nb) == 2) {
       if (nb == 1) hipLaunchKernelGGL(linear_fwd_fast_kernel<1>, grid, dim3(256), 0, st, x, w, ws, B, K, J, b0, kper);
       else hipLaunchKernelGGL(linear_fwd_fast_kernel<2>, grid, dim3(256), 0, st, x, w, ws, B, K, J, b0, kper);
     }
@@ -463,15 +532,15 @@ extern "C" int srx_linear_bwd_data(const float* dy, const float* w, float* dx, i
                                    size_t ws_floats, void* stream) {
   SRX_REQUIRE(dy && w && dx && ws && B > 0 && K > 0 && J > 0, "linear_bwd_data: bad argument");
   SRX_REQUIRE(K % 4 == 0, "linear_bwd_data: in_features must be a multiple of 4");
-  const int ns = bwd_splits(K, J, B);
-  if ((size_t)ns * B * K > ws_floats) SRX_FAIL(SRX_E_WORKSPACE, "linear_bwd_data: workspace too small");
-  const int jper = (int)srx_roundup(srx_cdiv(J, ns), 16);
-  const int nsplit = (int)srx_cdiv(J, jper);
+  LinearPlan p;
+  if (int rc = linear_plan(B, K, J, 1, p)) return rc;
+  if ((size_t)p.nsplit * B * K > ws_floats) SRX_FAIL(SRX_E_WORKSPACE, "linear_bwd_data: workspace too small");
+  const int jper = p.per, nsplit = p.nsplit;
   hipStream_t st = srx_stream(stream);
   for (int b0 = 0; b0 < B; b0 += 64) {  // up to four 16-row blocks per launch share one pass over the weight
     const dim3 grid((unsigned)srx_cdiv(K, 256), nsplit);
-    const int nb = (int)srx_cdiv(std::min(B - b0, 64), 16);
-    if (linear_fast_ok(B, K, J, true) && nb <= 2) {
+    int nb;
+    if (linear_launch_form(B, K, J, b0, true, false, &nb) == 2) {
       if (nb == 1) hipLaunchKernelGGL(linear_bwd_data_fast_kernel<1>, grid, dim3(256), 0, st, dy, w, ws, B, K, J, b0, jper);
       else hipLaunchKernelGGL(linear_bwd_data_fast_kernel<2>, grid, dim3(256), 0, st, dy, w, ws, B, K, J, b0, jper);
     }
@@ -491,7 +560,9 @@ extern "C" int srx_linear_bwd_weight(const float* x, const float* dy, float* dw,
                                      void* stream) {
   SRX_REQUIRE(x && dy && dw && B > 0 && K > 0 && J > 0, "linear_bwd_weight: bad argument");
   SRX_REQUIRE(K % 4 == 0, "linear_bwd_weight: in_features must be a multiple of 4");
-  if (linear_fast_ok(B, K, J, true))
+  LinearPlan p;
+  if (int rc = linear_plan(B, K, J, 2, p)) return rc;
+  if (p.form_first == 2)
     hipLaunchKernelGGL(linear_bwd_weight_fast_kernel, dim3((unsigned)srx_cdiv(K, 256), (unsigned)srx_cdiv(J, 16)), dim3(256),
                        0, srx_stream(stream), x, dy, dw, B, K, J, accumulate);
   else
