@@ -237,7 +237,7 @@ CONV_LAUNCHES_TESTED_ELSEWHERE = {
     'rdb_kernel<0>': 'test_ops_gpu.py::test_fused_dense_block_forward[16-32-32]',
     'rdb_kernel<1>': 'test_ops_gpu.py::test_fused_dense_block_backward[16-32-32]',
     'rdb_pack_kernel': 'test_ops_gpu.py::test_fused_dense_block_forward[16-32-32]',
-    'pack_table_kernel': 'test_step_gpu.py::test_pack_tables_take_over_after_the_first_step',
+    'pack_table_kernel': 'test_pack_table_gpu.py::test_one_table_for_every_layer',
 }
 
 
