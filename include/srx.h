@@ -119,6 +119,34 @@ int srx_dihedral_planes(const float* src, float* dst, int64_t planes, int H, int
 int srx_resample_planes(const float* src, float* dst, int64_t planes, int H, int W, int OH, int OW, const int* start_y,
                         const float* weight_y, int Ky, const int* start_x, const float* weight_x, int Kx, float* ws,
                         size_t ws_floats, void* stream);
+/* Colour fix of a super-resolved frame against its input -- the `color_fix` of test.upscale, `torchsr test --color-fix`
+ * (functional.color_fix_wavelet / color_fix_adain; csrc/colorfix.hip); no reference counterpart.  All tensors are
+ * [planes][H][W] fp32, every plane alone; H * W < 2^31, planes < 2^28, 64-bit plane bases, any H, W >= 1.
+ *
+ * One level of the a-trous blur with [1 2 1]^T [1 2 1] / 16 at dilation `radius` (1..32768), replicate padding, cl = clamp to
+ * the plane:
+ *   D         = sub ? src - sub : src                                               (one rounding)
+ *   t[y][x]   = 0.25f * (D[y][cl(x - radius)] + D[y][cl(x + radius)]) + 0.5f * D[y][x]
+ *   v[y][x]   = 0.25f * (t[cl(y - radius)][x] + t[cl(y + radius)][x]) + 0.5f * t[y][x]
+ *   dst       = add ? add + v : v                                                   (one rounding)
+ * in one launch, with the intermediate values of separate passes (two roundings per pass): the same bits from every call and
+ * alignment.  sub and add may be null; dst must overlap no operand.  The wavelet colour fix with `levels` levels is level 0 with
+ * src = the enlarged input and sub = sr, the levels between from one workspace to another, the last with add = sr:
+ * out = sr + B(U - sr).  4-byte aligned pointers; 16-byte accesses when W % 4 == 0, every pointer given is 16-byte aligned and
+ * radius is 1, 2 or a multiple of 4. */
+int srx_color_fix_wavelet_level(const float* src, const float* sub, const float* add, float* dst, int64_t planes, int H, int W,
+                                int radius, void* stream);
+/* Mean and unbiased variance (0 for H * W == 1) of every plane in fp64: stats[planes][2] = {mean, variance}.  Sums of
+ * d = x - x[p][0] and of d * d per workgroup into fixed slots of part ([planes][B][2] doubles, B = srx_plane_moments_blocks(H, W),
+ * part_doubles >= planes * B * 2), then added in index order by one wave per plane -- two launches, no atomics; an element's
+ * place in the sum depends on H * W alone: the same bits from every call, batch and alignment.  x, part and stats disjoint. */
+int srx_plane_moments_blocks(int H, int W); /* 0 for sizes srx_plane_moments refuses */
+int srx_plane_moments(const float* x, int64_t planes, int H, int W, double* part, size_t part_doubles, double* stats, void* stream);
+/* AdaIN colour fix: dst = fmaf(sr, s, b) per plane with s = sqrt(var_lr + 1e-5) / sqrt(var_sr + 1e-5) and b = mean_lr - mean_sr * s
+ * formed in fp64 from the two srx_plane_moments results (the input's at its own size) and rounded once to fp32.  dst must overlap
+ * no operand. */
+int srx_color_fix_adain_apply(const float* sr, float* dst, int64_t planes, int H, int W, const double* stats_sr,
+                              const double* stats_lr, void* stream);
 
 /* ------------------------------------------------------------------ conv2d */
 /* One nn.Conv2d instance: srgan/residual.py:27,64,67; srgan/generator.py:38,48,58;

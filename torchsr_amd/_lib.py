@@ -12,7 +12,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('SRX_LIB') or os.path.join(CSRC, 'libsrx_hip.so')  # SRX_LIB: developer A/B builds on one GPU box
-SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'degrade.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip', 'resample.hip', 'usm.hip', 'pool.hip']
+SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'degrade.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip', 'resample.hip', 'usm.hip', 'pool.hip', 'colorfix.hip']
 # headers the sources include, relative to CSRC: part of the build's digest and of every object's cache key
 HEADERS = ['srx_common.h', 'conv_host.h', os.path.join('..', '..', 'include', 'srx.h')]
 
@@ -161,6 +161,10 @@ _SIGS = {
     'srx_nhwc_to_nchw': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     'srx_dihedral_planes': (_I, [_P, _P, _L, _I, _I, _I, _F, _F, _P]),
     'srx_resample_planes': (_I, [_P, _P, _L, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _Z, _P]),
+    'srx_color_fix_wavelet_level': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    'srx_plane_moments_blocks': (_I, [_I, _I]),
+    'srx_plane_moments': (_I, [_P, _L, _I, _I, _P, _Z, _P, _P]),
+    'srx_color_fix_adain_apply': (_I, [_P, _P, _L, _I, _I, _P, _P, _P]),
     'srx_conv2d_packed_fwd_floats': (_Z, [_D]),
     'srx_conv2d_packed_bwd_floats': (_Z, [_D]),
     'srx_conv2d_fwd_ws_floats': (_Z, [_D]),
@@ -305,7 +309,7 @@ _SIGS = {
     'srx_adam_step_guarded': (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _P, _P, _P]),
 }
 # functions whose int return value is data, not a status
-_UNCHECKED = {'srx_wino_applicable', 'srx_wino_infer_applicable', 'srx_conv3x3_bf16s_applicable', 'srx_wino_stat_rows', 'srx_conv2d_bwd_data_bn_rows', 'srx_conv2d_fwd_bn_in_ok', 'srx_conv2d_bwd_data_bn_in_ok', 'srx_pack_table_bytes', 'srx_version', 'srx_last_error', 'srx_device_cus', 'srx_plan_cus', 'srx_prof_stop', 'srx_conv2d_stat_rows', 'srx_bn_stat_rows', 'srx_bn_rows_per_block'}
+_UNCHECKED = {'srx_wino_applicable', 'srx_wino_infer_applicable', 'srx_conv3x3_bf16s_applicable', 'srx_wino_stat_rows', 'srx_conv2d_bwd_data_bn_rows', 'srx_conv2d_fwd_bn_in_ok', 'srx_conv2d_bwd_data_bn_in_ok', 'srx_pack_table_bytes', 'srx_version', 'srx_last_error', 'srx_device_cus', 'srx_plan_cus', 'srx_prof_stop', 'srx_conv2d_stat_rows', 'srx_bn_stat_rows', 'srx_bn_rows_per_block', 'srx_plane_moments_blocks'}
 
 EXPORTS = tuple(_SIGS.keys())
 

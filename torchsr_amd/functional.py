@@ -570,6 +570,92 @@ def resize_bicubic_aa(x: Tensor, size: Tuple[int, int], out: Optional[Tensor] = 
     return out
 
 
+COLOR_FIX_MODES = ('wavelet', 'adain')
+COLOR_FIX_MAX_LEVELS = 8  # radius 2^7 = 128
+
+
+def _color_fix_operands(who: str, sr: Tensor, lr: Tensor, out: Optional[Tensor]):
+    """The refusals shared by the two colour fixes, all before the device is touched; ``(sr, lr, out)`` with ``out`` allocated."""
+    if torch.is_grad_enabled() and (sr.requires_grad or lr.requires_grad):
+        raise RuntimeError(f'{who}: inference-only (no backward); run it under torch.no_grad()')
+    if sr.dim() != 4 or lr.dim() != 4:
+        raise ValueError(f'{who}: expected NCHW tensors, got shapes {tuple(sr.shape)} and {tuple(lr.shape)}')
+    if tuple(sr.shape[:2]) != tuple(lr.shape[:2]):
+        raise ValueError(f'{who}: sr and lr must agree in N and C, got {tuple(sr.shape)} and {tuple(lr.shape)}')
+    if min(sr.shape) < 1 or min(lr.shape) < 1:
+        raise ValueError(f'{who}: every dimension must be positive, got {tuple(sr.shape)} and {tuple(lr.shape)}')
+    if sr.shape[2] * sr.shape[3] >= 2 ** 31 or lr.shape[2] * lr.shape[3] >= 2 ** 31:
+        raise ValueError(f'{who}: a plane must stay below 2^31 elements, got {tuple(sr.shape)} and {tuple(lr.shape)}')
+    operands = (('sr', sr), ('lr', lr)) + ((('out', out),) if out is not None else ())
+    for name, t in operands:
+        if not t.is_contiguous():
+            raise RuntimeError(f'{who}: {name} must be contiguous')
+    for name, t in operands:
+        _chk(t, f'{who}.{name}')
+    if lr.device != sr.device:
+        raise ValueError(f'{who}: sr is on {sr.device}, lr on {lr.device}')
+    if out is None:
+        out = torch.empty_like(sr)
+    elif tuple(out.shape) != tuple(sr.shape) or out.device != sr.device:
+        raise ValueError(f'{who}: the result is {tuple(sr.shape)} on {sr.device}, out is {tuple(out.shape)} on {out.device}')
+    return sr, lr, out
+
+
+def color_fix_wavelet(sr: Tensor, lr: Tensor, levels: int = 5, out: Optional[Tensor] = None) -> Tensor:
+    """StableSR's wavelet colour fix: the high frequencies of ``sr`` ([N,C,H,W]) on the low frequencies of ``lr`` ([N,C,h,w])
+    enlarged to (H, W) with ``resize_bicubic_aa`` -- ``sr + B(U - sr)``, ``B`` the a-trous blurs with [1 2 1]^T [1 2 1] / 16 at
+    the radii 1, 2, ..., 2^(levels - 1), replicate padding.  One ``srx_color_fix_wavelet_level`` launch per level behind the
+    resize, the subtraction folded into the first and the addition into the last; fp32, bit-reproducible.  Inference only."""
+    who = 'color_fix_wavelet'
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= COLOR_FIX_MAX_LEVELS:
+        raise ValueError(f'{who}: levels must be an int in 1..{COLOR_FIX_MAX_LEVELS}, got {levels!r}')
+    sr, lr, out = _color_fix_operands(who, sr, lr, out)
+    n, c, h, w = sr.shape
+    if lr.shape[2] > RESAMPLE_MAX_REDUCTION * h or lr.shape[3] > RESAMPLE_MAX_REDUCTION * w:
+        raise ValueError(f'{who}: lr {tuple(lr.shape[2:])} is more than {RESAMPLE_MAX_REDUCTION}:1 larger than sr {(h, w)}')
+    u = resize_bicubic_aa(lr, (h, w))
+    s = _stream()
+    # the levels between alternate between one workspace and U, which is free once level 0 has read it (lr itself when the sizes
+    # are equal: then a second workspace)
+    ws = [torch.empty_like(sr) if levels > 1 else None, u if u is not lr else torch.empty_like(sr) if levels > 2 else None]
+    src = u
+    for i in range(levels):
+        last = i == levels - 1
+        dst = out if last else ws[i & 1]
+        call('srx_color_fix_wavelet_level', _p(src), _p(sr) if i == 0 else None, _p(sr) if last else None, _p(dst), n * c, h, w,
+             1 << i, s)
+        src = dst
+    return out
+
+
+def plane_moments(x: Tensor) -> Tensor:
+    """``[N, C, 2]`` fp64: the mean and the unbiased variance (0 for a one-pixel plane) of every plane of an NCHW fp32 tensor,
+    summed in fp64 in a fixed order (``srx_plane_moments``): bit-reproducible.  Inference only."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError('plane_moments: inference-only (no backward); run it under torch.no_grad()')
+    if x.dim() != 4 or min(x.shape) < 1 or x.shape[2] * x.shape[3] >= 2 ** 31:
+        raise ValueError(f'plane_moments: expected an NCHW tensor with planes of 1 .. 2^31 - 1 elements, got shape {tuple(x.shape)}')
+    x = _chk(x, 'plane_moments.input')
+    n, c, h, w = x.shape
+    blocks = _lib.lib().srx_plane_moments_blocks(h, w)
+    part = torch.empty(n * c * blocks * 2, dtype=torch.float64, device=x.device)
+    stats = torch.empty((n, c, 2), dtype=torch.float64, device=x.device)
+    call('srx_plane_moments', _p(x), n * c, h, w, _p(part), part.numel(), _p(stats), _stream())
+    return stats
+
+
+def color_fix_adain(sr: Tensor, lr: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """StableSR's AdaIN colour fix: every plane of ``sr`` ([N,C,H,W]) mapped to the mean and the standard deviation of the same
+    plane of ``lr`` ([N,C,h,w], at its own size) -- ``fmaf(sr, s, b)``, ``s = sqrt(var_lr + 1e-5) / sqrt(var_sr + 1e-5)``,
+    ``b = mean_lr - mean_sr * s`` from ``plane_moments`` in fp64, each rounded once to fp32 (``srx_color_fix_adain_apply``).
+    Bit-reproducible.  Inference only."""
+    sr, lr, out = _color_fix_operands('color_fix_adain', sr, lr, out)
+    n, c, h, w = sr.shape
+    m_sr, m_lr = plane_moments(sr), plane_moments(lr)
+    call('srx_color_fix_adain_apply', _p(sr), _p(out), n * c, h, w, _p(m_sr), _p(m_lr), _stream())
+    return out
+
+
 RESIZE_MODES = ('area', 'bilinear', 'bicubic')
 
 

@@ -36,7 +36,7 @@ def load_generator_state(path: str) -> OrderedDict:
 @torch.no_grad()
 def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
             max_tile_pixels: int = MAX_TILE_PIXELS, scale: int = 4, precision: str = None, staged: bool = True,
-            self_ensemble: int = 0, outscale: float = None) -> Tensor:
+            self_ensemble: int = 0, outscale: float = None, color_fix: str = None) -> Tensor:
     """``generator(low_res)`` in eval mode, tiled when the image is large.  ``low_res``: [N,3,h,w].
 
     ``precision``: ``'fp32'`` (exact; the reference's ``test`` runs no autocast, test.py:57-62), ``'bf16'`` (bf16
@@ -56,7 +56,21 @@ def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
     path untouched.  Any other positive number: the generator still runs at x ``scale``, and its full result -- tiles or
     strips assembled, the ensemble averaged, the fp16 check passed -- is resampled ONCE to ``(int(h * outscale + 0.5),
     int(w * outscale + 0.5))`` (at least 1) with the antialiased bicubic the training data is reduced with
-    (``F.resize_bicubic_aa``, csrc/resample.hip).  A reduction of the x ``scale`` result by more than 16:1 is refused."""
+    (``F.resize_bicubic_aa``, csrc/resample.hip).  A reduction of the x ``scale`` result by more than 16:1 is refused.
+
+    ``color_fix``: ``None``: off, this path untouched.  ``'wavelet'`` or ``'adain'``: the generator's full x ``scale`` result --
+    assembled, averaged and checked as above -- is colour-corrected against the ORIGINAL ``low_res`` (``F.color_fix_wavelet``:
+    its high frequencies on the low frequencies of the enlarged input; ``F.color_fix_adain``: every channel mapped to the
+    input's mean and standard deviation; csrc/colorfix.hip), and ``outscale`` resamples that."""
+    if color_fix is not None:
+        from . import functional as F
+        if not isinstance(color_fix, str) or color_fix not in F.COLOR_FIX_MODES:
+            raise ValueError(f"upscale: color_fix must be None, 'wavelet' or 'adain', got {color_fix!r}")
+        size = None if outscale is None else _outscale_size(low_res, outscale, scale)  # its refusals, too, before the generator runs
+        full = upscale(generator, low_res, halo, max_tile_pixels, scale, precision, staged, self_ensemble)
+        fix = F.color_fix_wavelet if color_fix == 'wavelet' else F.color_fix_adain
+        full = fix(full, low_res.contiguous())
+        return full if size is None else F.resize_bicubic_aa(full, size)
     if outscale is not None:
         size = _outscale_size(low_res, outscale, scale)
         if size is not None:
@@ -196,6 +210,7 @@ def test(args: Namespace, model: object, device) -> None:
     image = np.asarray(Image.open(args.image).convert('RGB'), dtype='float32') / 255.0
     low_res = torch.from_numpy(image).permute(2, 0, 1).unsqueeze(0).contiguous().to(device)
     super_res = upscale(generator, low_res, precision=getattr(args, 'precision', None) or 'fp32',
-                        self_ensemble=getattr(args, 'self_ensemble', 0) or 0, outscale=getattr(args, 'outscale', None))
+                        self_ensemble=getattr(args, 'self_ensemble', 0) or 0, outscale=getattr(args, 'outscale', None),
+                        color_fix=getattr(args, 'color_fix', None))
     head, tail = os.path.split(args.image)
     save_image(super_res, os.path.join(head, f'upres-{tail}'))

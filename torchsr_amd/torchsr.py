@@ -180,6 +180,11 @@ def parse_args(argv=None) -> Namespace:
                            'x4; its result is then resampled once, on the GPU, with the antialiased bicubic filter the '
                            'training data was reduced with (2: a 4K picture from a 1080p one).  Combines with every '
                            '--precision, --self-ensemble and either --model')
+    test.add_argument('--color-fix', type=str, default=None, choices=('wavelet', 'adain'),
+                      help='correct the colour of the x4 result against the image, on the GPU (default: off).  wavelet: keep '
+                           'the result\'s detail and take the low frequencies -- five levels of a dilated 3x3 blur -- from the '
+                           'enlarged image; adain: map every channel to the image\'s mean and standard deviation.  Runs behind '
+                           'the ensemble average and before --outscale; combines with every other option')
     args = parser.parse_args(argv)
     if args.function == 'train' and args.poisson_noise_prob > 0 and not (args.device_data and args.degradation in ('blind', 'blind2')):
         parser.error('--poisson-noise-prob replaces the Gaussian noise of a blind degradation: add --device-data and '
