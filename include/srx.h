@@ -202,9 +202,10 @@ int srx_conv2d_stat_rows(const srx_conv2d_t* d);
 int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out);
 
 /* Plan overrides for tests and tile experiments (no reference counterpart).  They hold for every later call of this process until
- * reset with zeros (srx_wgrad_force: (-1, 0)); the environment seeds them at load (SRX_FORCE_PLAN="BM,BN,split,ks", SRX_S2_MODE bit 0,
- * SRX_NO_WGRAD_LIN, SRX_WGRAD_NSPLIT, SRX_THIN_FWD_ROWS; srx_linear_force has no environment seed).  srx_conv2d_plan, srx_thin_plan,
- * srx_linear_plan and the workspace queries report what a forced call runs.  A forced form a
+ * reset with zeros (srx_wgrad_force: (-1, 0), srx_wgrad_force_kernels: (-1, -1, -1)); the environment seeds them at load
+ * (SRX_FORCE_PLAN="BM,BN,split,ks", SRX_S2_MODE bit 0, SRX_NO_WGRAD_LIN, SRX_WGRAD_NSPLIT, SRX_WGRAD_ROWS_NSPLIT, SRX_NO_WGRAD_DMA,
+ * SRX_NO_WGRAD_ROWS, SRX_OLD_WGRAD_REDUCE, SRX_THIN_FWD_ROWS; srx_linear_force has no environment seed).  srx_conv2d_plan, srx_thin_plan,
+ * srx_linear_plan, srx_wgrad_plan and the workspace queries report what a forced call runs.  A forced form a
  * layer has no kernel for (tile not instantiated at the layer's arithmetic, BN not dividing the padded columns, 144 rows with bf16
  * products, the fused kernel on a layer it cannot run, more row splits than the rows allow, 4 rows per wave on a 3-channel output
  * layer with bf16 products, the fast linear form on a launch that cannot take it, more linear splits than there are trips) is
@@ -214,8 +215,14 @@ int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out);
  *   unsplit), KS = 2: two wave groups on the 64 x 64 tile (64 x 32 always has 2, or 4 with bf16 products).
  * srx_conv2d_force_s2: strided data gradients -- mode 0 the cost model, 1 always gconv_multi_kernel (tile from the model or
  *   srx_conv2d_force_plan), 2 always gconv_s2f_kernel on tile BM x BN ((2, 0, 0): the model's fused tile).
- * srx_wgrad_force: fp32 weight gradients -- lin 0: never the LIN form of wgrad_dma_kernel, 1 / -1: wherever it is eligible (the
- *   default); nsplit > 0: that many row splits (whole 32-row chunks of at least 128 rows), 0: the model's.
+ * srx_wgrad_force: weight gradients -- lin 0: never the LIN form of wgrad_dma_kernel (fp32), 1 / -1: wherever it is eligible (the
+ *   default); nsplit > 0: that many row splits, 0: the model's.  The generic kernels (wgrad_kernel, wgrad_dma_kernel) split the
+ *   M = N Ho Wo output pixels into whole 32-row chunks of at least 128 rows; the image-row kernel (wgrad_rows_bf16_kernel) splits
+ *   the N H image rows into whole rows: v is taken iff v <= N H and cdiv(N H, cdiv(N H, v)) == v.  SRX_WGRAD_NSPLIT seeds the
+ *   former, SRX_WGRAD_ROWS_NSPLIT the latter; this call sets both.
+ * srx_wgrad_force_kernels: which weight-gradient kernels run, each argument -1 (default) / 0 (off) / 1 (on where eligible, which is
+ *   the default) -- dma 0: fp32 layers run wgrad_kernel<0> (register-staged) instead of wgrad_dma_kernel; rows 0: the layers of
+ *   the image-row bf16 kernel run wgrad_kernel<1>; reduce 0: wgrad_reduce_kernel sums every layer's slabs (otherwise only K > 12288).
  * srx_thin_force_rows: the 3-channel output kernel (forward of the 64 -> <= 4 channel layers, data gradient of the <= 4 -> 64
  *   ones) -- 3, 4 or 6 output rows per wave, i.e. tiles of 12, 16 or 24 rows x 32 pixels; 0: the model's (6 from four tiles of
  *   24 rows per plan CU on, else 3).  Any other value is refused (SRX_THIN_FWD_ROWS: ignored with a line on stderr); the
@@ -228,6 +235,7 @@ int srx_conv2d_plan(const srx_conv2d_t* d, int which, int* out);
 int srx_conv2d_force_plan(int bm, int bn, int split, int ks);
 int srx_conv2d_force_s2(int mode, int bm, int bn);
 int srx_wgrad_force(int lin, int nsplit);
+int srx_wgrad_force_kernels(int dma, int rows, int reduce);
 int srx_thin_force_rows(int rows);
 int srx_linear_force(int form, int splits);
 
@@ -247,6 +255,16 @@ int srx_thin_plan(const srx_conv2d_t* d, int which, int* out);
  * which = 2 weight gradient: out[6] = {1, 0, 1, batch trips of 32 rows, form, form}.  SRX_E_UNSUPPORTED for what srx_linear_force
  * asked for and the shape cannot run. */
 int srx_linear_plan(int B, int K, int J, int which, int* out);
+
+/* Launch plan of srx_conv2d_bwd_weight* (wgrad.hip) for `nprob` problems of this geometry, `per_out` of them summed into one
+ * output, under the current overrides and reservation; computed by the function the launch and the workspace query plan with;
+ * host code only.  out[6] = {slab kernel: 0 wgrad_kernel<0>, 1 wgrad_dma_kernel<0, 0>, 2 wgrad_dma_kernel<1, 0> (WIDE),
+ * 3 wgrad_dma_kernel<1, 1> (WIDE + LIN), 4 wgrad_kernel<1>, 5 wgrad_rows_bf16_kernel<32>, 6 wgrad_rows_bf16_kernel<16>, 7 the
+ * 3-channel path of thin.hip (the other entries are 0: srx_thin_plan(d, 2, .) has its plan); row splits; output pixels per
+ * split; reduce kernel: 0 wgrad_reduce_kernel, 1 wgrad_reduce_rows_kernel; workgroups of the slab kernel; slabs summed into one
+ * output (splits x per_out)}.  The workspace is Cnw (Kw + 1) x splits x nprob floats, Cnw / Kw = Cout / K in whole tiles of 64.
+ * up = 2: the plan of the upsampled descriptor.  SRX_E_UNSUPPORTED for a forced row split the rows cannot take. */
+int srx_wgrad_plan(const srx_conv2d_t* d, int nprob, int per_out, int* out);
 
 /* OIHW master weights -> packed forward ([Cout_p][K_p], K=(kh,kw,ci)) and, when
  * wpk_bwd != NULL, packed data-gradient operands (per stride-parity class,

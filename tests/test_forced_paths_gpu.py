@@ -21,6 +21,7 @@ def _no_forced_plans():
     assert L.srx_conv2d_force_plan(0, 0, 0, 0) == 0
     assert L.srx_conv2d_force_s2(0, 0, 0) == 0
     assert L.srx_wgrad_force(-1, 0) == 0
+    assert L.srx_wgrad_force_kernels(-1, -1, -1) == 0
 
 
 def rel_err(a, b):

@@ -177,6 +177,8 @@ _SIGS = {
     'srx_thin_force_rows': (_I, [_I]),
     'srx_conv2d_force_s2': (_I, [_I, _I, _I]),
     'srx_wgrad_force': (_I, [_I, _I]),
+    'srx_wgrad_force_kernels': (_I, [_I, _I, _I]),
+    'srx_wgrad_plan': (_I, [_D, _I, _I, C.POINTER(C.c_int)]),
     'srx_linear_force': (_I, [_I, _I]),
     'srx_linear_plan': (_I, [_I, _I, _I, _I, C.POINTER(C.c_int)]),
     'srx_pack_table_bytes': (_Z, [_I]),

@@ -1273,6 +1273,8 @@ ConvForce& conv_force() {
     for (int i = 0; i < 4; ++i) s->plan[i].store(e.force_plan ? e.plan[i] : 0);
     s->s2[0].store((e.s2_mode & 1) ? 1 : 0); s->s2[1].store(0); s->s2[2].store(0);
     s->wg[0].store(e.no_wgrad_lin ? 0 : -1); s->wg[1].store(e.wgrad_nsplit > 0 && e.wgrad_nsplit <= 64 ? e.wgrad_nsplit : 0);
+    s->wg_rows.store(e.wgrad_rows_nsplit > 0 && e.wgrad_rows_nsplit <= 64 ? e.wgrad_rows_nsplit : 0);
+    s->wk[0].store(e.no_wgrad_dma ? 0 : -1); s->wk[1].store(e.no_wgrad_rows ? 0 : -1); s->wk[2].store(e.old_wgrad_reduce ? 0 : -1);
     return s;
   }();
   return *f;
@@ -1854,7 +1856,15 @@ extern "C" int srx_conv2d_force_s2(int mode, int bm, int bn) {
 extern "C" int srx_wgrad_force(int lin, int nsplit) {
   SRX_REQUIRE(lin >= -1 && lin <= 1 && nsplit >= 0 && nsplit <= 64, "wgrad_force: LIN -1 / 0 / 1, 0..64 row splits");
   ConvForce& f = conv_force();
-  f.wg[0].store(lin); f.wg[1].store(nsplit);
+  f.wg[0].store(lin); f.wg[1].store(nsplit); f.wg_rows.store(nsplit);
+  return SRX_OK;
+}
+
+extern "C" int srx_wgrad_force_kernels(int dma, int rows, int reduce) {
+  SRX_REQUIRE(dma >= -1 && dma <= 1 && rows >= -1 && rows <= 1 && reduce >= -1 && reduce <= 1,
+              "wgrad_force_kernels: DMA staging, image-row kernel, row-wise reduction: each -1 / 0 / 1");
+  ConvForce& f = conv_force();
+  f.wk[0].store(dma); f.wk[1].store(rows); f.wk[2].store(reduce);
   return SRX_OK;
 }
 

@@ -851,10 +851,12 @@ static int wgrad_nsplit(int M, int64_t tiles, int nprob, int Cnw, int Kw, int pr
 // bf16 products, 3x3 / stride 1 / pad 1, 64 output columns, whole 32-channel groups, image rows of 16 or 32 pixels (ESRGAN's
 // dense blocks at the training crop size): the image-row kernel (wgrad_rows_bf16_kernel)
 static bool wgrad_rows_ok(const srx_conv2d_t* d) {
-  if (srx_dev().no_wgrad_rows || !d->precision || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->shuffle || d->up == 2) return false;
+  // (srx_wgrad_force_kernels(., 0, .) / SRX_NO_WGRAD_ROWS: such layers run wgrad_kernel<1>)
+  if (conv_force().wk[1].load(std::memory_order_relaxed) == 0 || !d->precision || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->shuffle || d->up == 2) return false;
   return d->Cout == 64 && srx_roundup(d->Cin, 4) % 32 == 0 && (d->W == 32 || d->W == 16);
 }
-// row splits of the image-row kernel: workgroups = channel groups x problems x splits, four resident per CU
+// row splits of the image-row kernel: workgroups = channel groups x problems x splits, four resident per CU.  -1: a forced split
+// (srx_wgrad_force / SRX_WGRAD_ROWS_NSPLIT, in image rows) the rows cannot take, message set
 static int wgrad_rows_nsplit(const srx_conv2d_t* d, int nprob) {
   const int cus = srx_plan_cus();
   const int groups = (int)srx_roundup(d->Cin, 4) / 32, rows = d->N * d->H;
@@ -867,9 +869,83 @@ static int wgrad_rows_nsplit(const srx_conv2d_t* d, int nprob) {
     const float cost = rounds * (rps + 8.0f) + 0.25f * ns;  // (+ the slab reduction grows with the splits)
     if (cost < best_cost) { best_cost = cost; best = ns; }
   }
-  if (const int v = srx_dev().wgrad_rows_nsplit; v > 0 && v <= 64 && v <= rows) best = v;
+  if (const int v = conv_force().wg_rows.load(std::memory_order_relaxed); v > 0) {
+    if (v > rows || (int)srx_cdiv(rows, srx_cdiv(rows, v)) != v) {
+      srx_set_error("conv2d_bwd_weight: forced %d row splits refused: %d image rows split into whole rows give %d splits", v, rows,
+                    v > rows ? rows : (int)srx_cdiv(rows, srx_cdiv(rows, v)));
+      return -1;
+    }
+    best = v;
+  }
   const int rps = (int)srx_cdiv(rows, best);
   return (int)srx_cdiv(rows, rps);
+}
+
+// ---- launch plan.  The ONE place that cuts it: srx_wgrad_plan, the workspace query and wgrad_multi_impl read wgrad_plan and nothing
+// else, so what the query reports is what the call launches. ----
+enum { WK_F32 = 0, WK_DMA = 1, WK_DMA_WIDE = 2, WK_DMA_LIN = 3, WK_BF16 = 4, WK_ROWS32 = 5, WK_ROWS16 = 6, WK_THIN = 7 };
+struct WgradPlan {
+  int kernel;          // WK_*: wgrad_kernel<0>, wgrad_dma_kernel<0, 0> / <1, 0> (WIDE) / <1, 1> (WIDE + LIN: offsets linear in the row, validity
+                       // from a per-workgroup bit table, see wgrad_dma_kernel), wgrad_kernel<1>, wgrad_rows_bf16_kernel<32> / <16>
+  int nsplit;          // row splits = slabs per problem
+  int rows_per_split;  // output pixels per split (the image-row kernel: whole image rows)
+  int reduce;          // 0 wgrad_reduce_kernel, 1 wgrad_reduce_rows_kernel
+  int workgroups;      // of the slab kernel
+  int Cnw, Kw;         // slab extents: output columns and K in whole tiles of 64
+};
+// `d`: a checked descriptor without a fused upsample (up = 2: plan upsampled_desc(d)) whose gradient is not thin.hip's.  Returns SRX_OK,
+// or SRX_E_UNSUPPORTED for a forced row split the rows cannot take (message set).
+static int wgrad_plan(const srx_conv2d_t* d, int nprob, WgradPlan& p) {
+  const Geo g = fwd_geo(d);
+  const ConvForce& f = conv_force();
+  p.Cnw = (int)srx_roundup(d->Cout, 64);
+  p.Kw = (int)srx_roundup(g.K, 64);
+  const int M = d->N * g.Ho * g.Wo;
+  const int64_t tiles = (int64_t)(p.Kw / 64) * (p.Cnw / 64);
+  if (wgrad_rows_ok(d)) {
+    p.nsplit = wgrad_rows_nsplit(d, nprob);
+    if (p.nsplit < 0) return SRX_E_UNSUPPORTED;
+    p.kernel = d->W == 32 ? WK_ROWS32 : WK_ROWS16;
+    p.rows_per_split = (int)srx_cdiv(d->N * d->H, p.nsplit) * d->W;
+    p.workgroups = (g.Ck / 32) * nprob * p.nsplit;
+  } else {
+    p.nsplit = wgrad_nsplit(M, tiles, nprob, p.Cnw, p.Kw, d->precision);
+    if (p.nsplit < 0) return SRX_E_UNSUPPORTED;
+    p.rows_per_split = (int)srx_roundup(srx_cdiv(M, p.nsplit), 32);
+    p.workgroups = (int)(tiles * nprob * p.nsplit);
+    if (d->precision) {
+      p.kernel = WK_BF16;
+    } else if (f.wk[0].load(std::memory_order_relaxed) == 0) {  // srx_wgrad_force_kernels(0, ., .) / SRX_NO_WGRAD_DMA
+      p.kernel = WK_F32;
+    } else {
+      p.kernel = WK_DMA;
+      const int Cdv = bwd_ck(d);
+      if (g.Ck % 64 == 0 && Cdv % 64 == 0 && (!g.cps || g.cps % 64 == 0)) {
+        const size_t in_bytes = (size_t)d->N * d->H * d->W * d->Cin_s * sizeof(float);
+        const size_t dy_bytes = (size_t)M * (d->shuffle ? 4 : 1) * d->Cout_s * sizeof(float);
+        const bool lin = f.wg[0].load(std::memory_order_relaxed) != 0 && d->stride == 1 && d->H == g.Ho && d->W == g.Wo && !g.cps &&
+                         g.K % 64 == 0 && p.rows_per_split / 32 + 3 <= WG_MASKW && in_bytes < 0xfff00000ull && dy_bytes < 0xfff00000ull;
+        p.kernel = lin ? WK_DMA_LIN : WK_DMA_WIDE;  // (srx_wgrad_force(0, .) turns LIN off)
+      }
+    }
+  }
+  // wgrad_reduce_rows_kernel parks a slab row's K sums in LDS; srx_wgrad_force_kernels(., ., 0) / SRX_OLD_WGRAD_REDUCE: never
+  p.reduce = (f.wk[2].load(std::memory_order_relaxed) == 0 || (size_t)g.K * sizeof(float) > 48 * 1024) ? 0 : 1;
+  return SRX_OK;
+}
+
+extern "C" int srx_wgrad_plan(const srx_conv2d_t* d, int nprob, int per_out, int* out) {
+  if (int rc = check_desc(d)) return rc;
+  SRX_REQUIRE(out && nprob >= 1 && nprob <= WG_MAXP && per_out >= 1 && nprob % per_out == 0,
+              "wgrad_plan: a result array, 1..%d problems, a whole number of outputs", WG_MAXP);
+  SRX_REQUIRE(d->precision != 3, "conv2d: precision 3 (fp16 products) is forward-only");
+  if (d->up == 2) { const srx_conv2d_t h = upsampled_desc(d); return srx_wgrad_plan(&h, nprob, per_out, out); }
+  for (int i = 0; i < 6; ++i) out[i] = 0;
+  if (srx_thin_wgrad_applicable(d)) { out[0] = WK_THIN; return SRX_OK; }  // (thin.hip plans it: srx_thin_plan(d, 2, .))
+  WgradPlan p;
+  if (int rc = wgrad_plan(d, nprob, p)) return rc;
+  out[0] = p.kernel; out[1] = p.nsplit; out[2] = p.rows_per_split; out[3] = p.reduce; out[4] = p.workgroups; out[5] = p.nsplit * per_out;
+  return SRX_OK;
 }
 
 extern "C" size_t srx_conv2d_bwd_weight_multi_ws_floats(const srx_conv2d_t* d, int nprob) {
@@ -877,12 +953,9 @@ extern "C" size_t srx_conv2d_bwd_weight_multi_ws_floats(const srx_conv2d_t* d, i
   if (d->up == 2) { const srx_conv2d_t h = upsampled_desc(d); return nprob * upsampled_floats(d) + srx_conv2d_bwd_weight_multi_ws_floats(&h, nprob); }
   if (srx_thin_wgrad_applicable(d))  // (one call per problem) + the column-sum scratch of an optional bias gradient
     return srx_thin_wgrad_ws_floats(d) + srx_colsum_ws_floats((int64_t)d->N * d->H * d->W, d->Cout);
-  const Geo g = fwd_geo(d);
-  const size_t Cnw = (size_t)srx_roundup(d->Cout, 64), Kw = (size_t)srx_roundup(g.K, 64);
-  const int ns = wgrad_rows_ok(d) ? wgrad_rows_nsplit(d, nprob)
-                                  : wgrad_nsplit(d->N * g.Ho * g.Wo, (int64_t)(Kw / 64) * (Cnw / 64), nprob, (int)Cnw, (int)Kw, d->precision);
-  if (ns < 0) return 0;  // (a refused forced split: the call reports it)
-  return Cnw * (Kw + 1) * (size_t)ns * nprob;  // one slab (+ one bias row) per problem and row split
+  WgradPlan p;
+  if (wgrad_plan(d, nprob, p)) return 0;  // (a refused forced split: the call reports it)
+  return (size_t)p.Cnw * ((size_t)p.Kw + 1) * (size_t)p.nsplit * nprob;  // one slab (+ one bias row) per problem and row split
 }
 
 extern "C" size_t srx_conv2d_bwd_weight_ws_floats(const srx_conv2d_t* d) { return srx_conv2d_bwd_weight_multi_ws_floats(d, 1); }
@@ -967,12 +1040,11 @@ static int wgrad_multi_impl(const srx_conv2d_t* d, int nprob, int per_out, const
       a.dD1 = 0;
     }
   }
-  const int ntiles = a.Cnw / 64;
-  const int64_t tiles = (int64_t)a.ktiles * ntiles;
-  const bool rows_kernel = wgrad_rows_ok(d);
-  const int nsplit = rows_kernel ? wgrad_rows_nsplit(d, nprob) : wgrad_nsplit(a.M, tiles, nprob, a.Cnw, a.Kw, d->precision);
-  if (nsplit < 0) return SRX_E_UNSUPPORTED;  // (wgrad_nsplit set the message)
-  a.rows_per_split = rows_kernel ? (int)srx_cdiv(d->N * d->H, nsplit) * d->W : (int)srx_roundup(srx_cdiv(a.M, nsplit), 32);
+  WgradPlan plan;
+  if (int rc = wgrad_plan(d, nprob, plan)) return rc;  // (a refused forced split: the planner set the message)
+  const bool rows_kernel = plan.kernel == WK_ROWS32 || plan.kernel == WK_ROWS16;
+  const int nsplit = plan.nsplit;
+  a.rows_per_split = plan.rows_per_split;
   a.nsplit = nsplit;
   a.nprob = nprob;
   const size_t nslabs = (size_t)nsplit * nprob;
@@ -989,40 +1061,28 @@ static int wgrad_multi_impl(const srx_conv2d_t* d, int nprob, int per_out, const
   }
   outs.rows_lo = dws_hi ? d->Cout / 2 : 0;
   outs.cin_lo = cin_lo;
-  dim3 grid((unsigned)(tiles * nprob * nsplit));
+  const dim3 grid((unsigned)plan.workgroups);
   const double wfl = 2.0 * a.M * d->Cout * a.K * nprob;
   char nm[112];
   if (rows_kernel) {
-    grid = dim3((unsigned)((g.Ck / 32) * nprob * nsplit));
     if (srx_prof_on()) snprintf(nm, sizeof(nm), "wgrad_rows_bf16_kernel<%d> MxNxK=%dx%dx%d x%d", d->W, a.M, d->Cout, a.K, nprob);
-    if (d->W == 32) SRX_LAUNCH_PROF(nm, wfl, wgrad_rows_bf16_kernel<32>, grid, dim3(256), 0, st, mp);
+    if (plan.kernel == WK_ROWS32) SRX_LAUNCH_PROF(nm, wfl, wgrad_rows_bf16_kernel<32>, grid, dim3(256), 0, st, mp);
     else SRX_LAUNCH_PROF(nm, wfl, wgrad_rows_bf16_kernel<16>, grid, dim3(256), 0, st, mp);
     SRX_CHECK_LAUNCH("wgrad_rows_bf16_kernel");
   } else {
-    // form: 0 wgrad_kernel<PR>, 1 wgrad_dma_kernel<0, 0>, 2 wgrad_dma_kernel<1, 0> (WIDE), 3 wgrad_dma_kernel<1, 1> (WIDE + LIN:
-    // offsets linear in the row, validity from a per-workgroup bit table, see wgrad_dma_kernel; srx_wgrad_force(0, .) turns it off)
-    int form = 0;
-    if (!d->precision && !srx_dev().no_wgrad_dma) {
-      form = 1;
-      if (g.Ck % 64 == 0 && a.Cdv % 64 == 0 && (!a.dy_shuffle || a.dy_shuffle % 64 == 0)) {
-        const bool lin = conv_force().wg[0].load(std::memory_order_relaxed) != 0 && a.in_stride == 1 && a.Hi == a.Hm && a.Wi == a.Wm &&
-                         !a.dy_shuffle && a.K % 64 == 0 && a.rows_per_split / 32 + 3 <= WG_MASKW && a.in_bytes < 0xfff00000u &&
-                         a.dy_bytes < 0xfff00000u;
-        form = lin ? 3 : 2;
-      }
-    }
+    const int form = plan.kernel;
     if (srx_prof_on()) {
-      if (form == 0) snprintf(nm, sizeof(nm), "wgrad_kernel<%d> MxNxK=%dx%dx%d x%d", d->precision ? 1 : 0, a.M, d->Cout, a.K, nprob);
-      else snprintf(nm, sizeof(nm), "wgrad_dma_kernel<%d, %d> MxNxK=%dx%dx%d x%d", form >= 2 ? 1 : 0, form == 3 ? 1 : 0, a.M, d->Cout, a.K, nprob);
+      if (form == WK_F32 || form == WK_BF16) snprintf(nm, sizeof(nm), "wgrad_kernel<%d> MxNxK=%dx%dx%d x%d", form == WK_BF16 ? 1 : 0, a.M, d->Cout, a.K, nprob);
+      else snprintf(nm, sizeof(nm), "wgrad_dma_kernel<%d, %d> MxNxK=%dx%dx%d x%d", form >= WK_DMA_WIDE ? 1 : 0, form == WK_DMA_LIN ? 1 : 0, a.M, d->Cout, a.K, nprob);
     }
-    if (d->precision) SRX_LAUNCH_PROF(nm, wfl, wgrad_kernel<1>, grid, dim3(256), 0, st, mp);
-    else if (form == 0) SRX_LAUNCH_PROF(nm, wfl, wgrad_kernel<0>, grid, dim3(256), 0, st, mp);
-    else if (form == 3) SRX_LAUNCH_PROF(nm, wfl, (wgrad_dma_kernel<true, true>), grid, dim3(256), 0, st, mp);
-    else if (form == 2) SRX_LAUNCH_PROF(nm, wfl, wgrad_dma_kernel<true>, grid, dim3(256), 0, st, mp);
+    if (form == WK_BF16) SRX_LAUNCH_PROF(nm, wfl, wgrad_kernel<1>, grid, dim3(256), 0, st, mp);
+    else if (form == WK_F32) SRX_LAUNCH_PROF(nm, wfl, wgrad_kernel<0>, grid, dim3(256), 0, st, mp);
+    else if (form == WK_DMA_LIN) SRX_LAUNCH_PROF(nm, wfl, (wgrad_dma_kernel<true, true>), grid, dim3(256), 0, st, mp);
+    else if (form == WK_DMA_WIDE) SRX_LAUNCH_PROF(nm, wfl, wgrad_dma_kernel<true>, grid, dim3(256), 0, st, mp);
     else SRX_LAUNCH_PROF(nm, wfl, wgrad_dma_kernel<false>, grid, dim3(256), 0, st, mp);
     SRX_CHECK_LAUNCH("wgrad_kernel");
   }
-  if (srx_dev().old_wgrad_reduce || (size_t)g.K * sizeof(float) > 48 * 1024) {
+  if (plan.reduce == 0) {
     const int64_t n = (int64_t)d->Cout * g.K;
     SRX_LAUNCH_PROF_AUX("wgrad_reduce_kernel", wgrad_reduce_kernel, dim3((unsigned)srx_cdiv(n, 256), (unsigned)nout), dim3(256), 0, st, ws,
                     nsplit * per_out, a.Cnw, a.Kw, g.K, g.Ck, d->Cout, d->Cin, d->KH, d->KW, g.cps, outs, accumulate,
