@@ -339,6 +339,14 @@ int srx_conv3x3_c64_f16_pack(const float* w, const float* bias, const float* out
 /* y (fp16) = act(conv(x) + bias) [+ residual (fp16)], rounded once */
 int srx_conv3x3_c64_f16_fwd(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk, float slope,
                             const void* residual, void* y, int y_cs, void* stream);
+/* The 64 -> 64k layers with one PReLU slope per output channel (the compact generator's body): the arguments of
+ * srx_conv3x3_c64_{bf16,f16}_fwd with a device array slopes[Cout] (16-byte aligned) in place of the scalar;
+ * y = v > 0 ? v : slopes[c] * v with v = conv(x) + bias, then the optional addend, rounded once.  shuffle must be 0.  A kernel
+ * instantiation of its own: the scalar entry points keep their code and bits. */
+int srx_conv3x3_c64_bf16_fwd_slopes(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk,
+                                    const float* slopes, const void* residual, void* y, int y_cs, void* stream);
+int srx_conv3x3_c64_f16_fwd_slopes(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk,
+                                   const float* slopes, const void* residual, void* y, int y_cs, void* stream);
 /* fp32 -> fp16 rounds to nearest even (beyond 65519.99..: +-inf); fp16 -> fp32 is exact; n a positive multiple of 4 */
 int srx_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int srx_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
@@ -484,6 +492,25 @@ int srx_prelu_fwd(const float* x, const float* slope, float* y, int64_t n, void*
 /* dx and d(slope); ws >= 1024 floats */
 int srx_prelu_bwd(const float* dy, const float* x, const float* slope, float* dx, float* dslope,
                   int accumulate, int64_t n, float* ws, void* stream);
+/* nn.PReLU(C), one slope per channel, on NHWC rows (csrc/compact.hip): x, y [M][Cs], slopes [C];
+ * y = x > 0 ? x : slopes[c] * x for c < C, channels C .. Cs - 1 pass through.  y == x is allowed.  16-byte accesses:
+ * C % 4 == 0, Cs % 4 == 0, C <= Cs, C <= 512, Cs <= 1024, or the call is refused before any launch. */
+int srx_prelu_channels_fwd(const float* x, const float* slopes, float* y, int64_t M, int C, int Cs, void* stream);
+/* dx = x > 0 ? dy : slopes[c] * dy (channels past C: dy) and dslopes[c] (+)= sum over rows of (x > 0 ? 0 : x * dy).  The sum
+ * runs in fp64 per lane, per-workgroup partials go to fixed workspace slots and are added in index order -- no atomics, the
+ * same bits from every call.  ws: 8-byte aligned, ws_floats >= srx_prelu_channels_ws_floats(M, C).  dx, dy, x disjoint. */
+size_t srx_prelu_channels_ws_floats(int64_t M, int C);
+int srx_prelu_channels_bwd(const float* dy, const float* x, const float* slopes, float* dx, float* dslopes, int accumulate,
+                           int64_t M, int C, int Cs, float* ws, size_t ws_floats, void* stream);
+/* The compact generator's tail in one pass: y4[n][s y + i][s x + j][c] = t[n][y][x][c s^2 + i s + j] + x4[n][y][x][c] for
+ * c < 3, channel 3 of y4 = 0 -- PixelShuffle(s) of t's first 3 s^2 channels plus the nearest-enlarged input.  t: [N][h][w][t_cs],
+ * t_dtype 0 fp32, 1 bf16, 2 fp16, t_cs >= 3 s^2 and a multiple of 4; x4 [N][h][w][4] and y4 [N][s h][s w][4] fp32; s = 2, 3, 4.
+ * One fp32 add per element.  Every store is a whole NHWC-4 pixel, consecutive lanes along the output row. */
+int srx_shuffle_add_nearest_fwd(const void* t, int t_dtype, int t_cs, const float* x4, float* y4, int N, int h, int w, int s,
+                                void* stream);
+/* The inverse permutation: dt[n][y][x][c s^2 + i s + j] = dy4[n][s y + i][s x + j][c], channels 3 s^2 .. t_cs - 1 of dt = 0
+ * (fp32 dt; the input image takes no gradient). */
+int srx_shuffle_add_nearest_bwd(const float* dy4, float* dt, int t_cs, int N, int h, int w, int s, void* stream);
 /* nn.LeakyReLU as a standalone op (ESRGAN, esrgan/residual.py:36-55) */
 int srx_lrelu_fwd(const float* x, float* y, int64_t n, float slope, void* stream);
 /* y = a*x + b*z  (residual scaling of esrgan/residual.py:86,128; torch.add of srgan/generator.py:78) */

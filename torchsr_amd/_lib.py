@@ -12,7 +12,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('SRX_LIB') or os.path.join(CSRC, 'libsrx_hip.so')  # SRX_LIB: developer A/B builds on one GPU box
-SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'degrade.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip', 'resample.hip', 'usm.hip', 'pool.hip', 'colorfix.hip']
+SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'degrade.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip', 'resample.hip', 'usm.hip', 'pool.hip', 'colorfix.hip', 'compact.hip']
 # headers the sources include, relative to CSRC: part of the build's digest and of every object's cache key
 HEADERS = ['srx_common.h', 'conv_host.h', os.path.join('..', '..', 'include', 'srx.h')]
 
@@ -200,6 +200,13 @@ _SIGS = {
     'srx_conv3x3_c64_f16_packed_bytes': (_Z, [_I]),
     'srx_conv3x3_c64_f16_pack': (_I, [_P, _P, _P, _I, _I, _P, _P]),
     'srx_conv3x3_c64_f16_fwd': (_I, [_I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _I, _P]),
+    'srx_conv3x3_c64_bf16_fwd_slopes': (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
+    'srx_conv3x3_c64_f16_fwd_slopes': (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
+    'srx_prelu_channels_fwd': (_I, [_P, _P, _P, _L, _I, _I, _P]),
+    'srx_prelu_channels_ws_floats': (_Z, [_L, _I]),
+    'srx_prelu_channels_bwd': (_I, [_P, _P, _P, _P, _P, _I, _L, _I, _I, _P, _Z, _P]),
+    'srx_shuffle_add_nearest_fwd': (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
+    'srx_shuffle_add_nearest_bwd': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     'srx_f32_to_f16': (_I, [_P, _P, _L, _P]),
     'srx_f16_to_f32': (_I, [_P, _P, _L, _P]),
     'srx_conv9x9_c64_thin_f16_packed_bytes': (_Z, []),

@@ -86,6 +86,7 @@ struct C64Args {
   int shuffle;               // 0, or 2: group g writes sub-pixel (g >> 1, g & 1) of a [N][2H][2W][out_cs] tensor
   int out_cs;                // channel stride of the output (and the addend) in bf16 elements, >= 64
   float slope;               // v > 0 ? v : v * slope (none: 1, ReLU: 0)
+  const float* slopes;       // c64_kernel<.., PC = true> only: one slope per output channel, [groups * 64] (never with shuffle)
   int strips, chunks, rows_per_chunk, nwork;
   unsigned* dbg;  // developer aid (srx_conv3x3_c64_bf16_fwd_dbg): per workgroup and wave, cycles spent per phase; null in the product
   int ablate;  // developer aid (SRX_C64_ABLATE, timing only, results are wrong): 1 skip the finishing, 2 skip the MFMAs, 4 skip the window requests
@@ -100,7 +101,10 @@ struct C64Args {
 // T: the 16-bit type of activations, weights and addend -- __bf16 (profile name c64_bf16_kernel<RW, CW>) or _Float16
 // (c64_f16_kernel<RW, CW>: precision 3, v_mfma_f32_32x32x16_f16).  (A template parameter of the kernel itself, not a __device__
 // body behind two wrappers: inlined into a wrapper, the bf16 body came out with other registers and another schedule.)
-template <typename T, int RW, int CW>
+// PC: the activation's slope is per output channel (a.slopes: the compact generator's PReLU(64)), read once per helper lane where
+// the scalar modes read a.slope.  An instantiation of its own: the scalar-slope kernels above it are compiled from the text they
+// always had (`if constexpr`), so their registers, schedule and bits do not move.
+template <typename T, int RW, int CW, bool PC = false>
 __global__ __launch_bounds__(512) void c64_kernel(const C64Args a) {
   typedef typename E16<T>::v8 v8;
   static_assert(RW * CW == 4, "128 pixels per step");
@@ -264,6 +268,16 @@ __global__ __launch_bounds__(512) void c64_kernel(const C64Args a) {
   // activation: none (slope 1), v > 0 ? v : v * slope in general, max(v, v * slope) when 0 <= slope <= 1 (ReLU, LeakyReLU, a
   // PReLU parameter in its usual range): two instructions per pair of elements instead of five
   const int act_mode = a.slope == 1.f ? 0 : ((a.slope >= 0.f && a.slope <= 1.f) ? 1 : 2);  // (uniform)
+  // PC: the slopes of this lane's 8 channels, 64 g + 32 nh + 8 ech .. + 7.  A compiler-tracked load, but the only one of this wave
+  // and consumed right here, in front of the loops: the counted waits below never see it.
+  float sl[8] = {};
+  if constexpr (PC) {
+    const f32x4* sp = reinterpret_cast<const f32x4*>(a.slopes + 64 * blockIdx.y + 32 * nh + 8 * (lane & 3));
+    const f32x4 s0 = sp[0], s1 = sp[1];
+    asm volatile("" :: "v"(s0), "v"(s1));
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sl[e] = e < 4 ? s0[e] : s1[e - 4];
+  }
   // staging units of the four helper waves.  Unit e = 256 u + tid of a group of RW rows is 16-byte position (e % 8) of window
   // pixel (e / 8) % PX of row e / (8 PX): LDS byte 16 e of the group's slots (rows are contiguous), i.e. lane-linear per wave.
   int srow[NLD], scol[NLD];
@@ -381,7 +395,10 @@ __global__ __launch_bounds__(512) void c64_kernel(const C64Args a) {
         float v[8];  // (the bias is already in: the matrix waves start their accumulators from it)
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = e < 4 ? lo[e] : hi[e - 4];
-        if (act_mode == 1) {
+        if constexpr (PC) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * sl[e];
+        } else if (act_mode == 1) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], v[e] * a.slope);
         } else if (act_mode == 2) {
@@ -556,12 +573,12 @@ int c64_plan(int N, int H, int W, int groups, int RW, int TW, int* rows_per_chun
   return SRX_OK;
 }
 
-template <typename T, int RW, int CW>
+template <typename T, int RW, int CW, bool PC>
 int launch_c64(C64Args& a, int groups, hipStream_t st) {
   constexpr int TW = 32 * CW, NR = RW == 1 ? 4 : 3 * RW;
   constexpr bool F16 = std::is_same<T, _Float16>::value;
-  constexpr auto kernel = &c64_kernel<T, RW, CW>;
-  const char* kname = F16 ? "c64_f16_kernel" : "c64_bf16_kernel";
+  constexpr auto kernel = &c64_kernel<T, RW, CW, PC>;
+  const char* kname = PC ? (F16 ? "c64_f16_slopes_kernel" : "c64_bf16_slopes_kernel") : (F16 ? "c64_f16_kernel" : "c64_bf16_kernel");
   const size_t lds = (size_t)NR * (TW + 2) * 128 + 4 * 2 * 64 * EPI_PITCH + 4 * 4096;
   static std::once_flag once;
   std::call_once(once, [] {
@@ -617,10 +634,16 @@ extern "C" int srx_conv3x3_c64_f16_pack(const float* w, const float* bias, const
   return c64_pack_impl(w, bias, out_scale, Cout, shuffle, wpk, stream, true);
 }
 
-static int c64_fwd_impl(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk, float slope,
+template <bool PC>
+static int c64_fwd_impl(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk, float slope, const float* slopes,
                         const void* residual, void* y, int y_cs, void* stream, unsigned* dbg, bool f16 = false) {
   const char* fn = f16 ? "conv3x3_c64_f16_fwd" : "conv3x3_c64_bf16_fwd";
   SRX_REQUIRE(x && wpk && y, "%s: null pointer", fn);
+  if (PC) {
+    SRX_REQUIRE(slopes, "%s: null slopes", fn);
+    SRX_REQUIRE(((uintptr_t)slopes & 15) == 0, "%s: the slopes must be 16-byte aligned", fn);
+    SRX_REQUIRE(shuffle == 0, "%s: per-channel slopes come without PixelShuffle", fn);
+  }
   SRX_REQUIRE(N > 0 && H > 0 && W > 0 && Cout > 0 && Cout % 64 == 0 && Cout <= 1024, "%s: bad size (Cout a multiple of 64)", fn);
   SRX_REQUIRE(shuffle == 0 || (shuffle == 2 && Cout == 256), "%s: PixelShuffle(2) needs Cout = 256", fn);
   SRX_REQUIRE(y_cs % 8 == 0 && y_cs >= (shuffle ? 64 : Cout), "%s: the output's channel stride must hold its channels in whole 16-byte chunks", fn);
@@ -634,20 +657,20 @@ static int c64_fwd_impl(int N, int H, int W, int Cout, int shuffle, const void* 
   a.bias = reinterpret_cast<const float*>(a.w + (size_t)(Cout / 64) * KSTEPS * 2 * 1024);
   a.res = static_cast<const unsigned char*>(residual);
   a.out = static_cast<unsigned char*>(y);
-  a.N = N; a.H = H; a.W = W; a.shuffle = shuffle; a.out_cs = y_cs; a.slope = slope;
+  a.N = N; a.H = H; a.W = W; a.shuffle = shuffle; a.out_cs = y_cs; a.slope = slope; a.slopes = slopes;
   a.ablate = srx_dev().c64_ablate;
   a.dbg = dbg;
   hipStream_t st = srx_stream(stream);
   const int groups = Cout / 64;
   // narrow images: waves take rows instead of column segments
   if (f16) {
-    if (W <= 32) return launch_c64<_Float16, 4, 1>(a, groups, st);
-    if (W <= 64) return launch_c64<_Float16, 2, 2>(a, groups, st);
-    return launch_c64<_Float16, 1, 4>(a, groups, st);
+    if (W <= 32) return launch_c64<_Float16, 4, 1, PC>(a, groups, st);
+    if (W <= 64) return launch_c64<_Float16, 2, 2, PC>(a, groups, st);
+    return launch_c64<_Float16, 1, 4, PC>(a, groups, st);
   }
-  if (W <= 32) return launch_c64<__bf16, 4, 1>(a, groups, st);
-  if (W <= 64) return launch_c64<__bf16, 2, 2>(a, groups, st);
-  return launch_c64<__bf16, 1, 4>(a, groups, st);
+  if (W <= 32) return launch_c64<__bf16, 4, 1, PC>(a, groups, st);
+  if (W <= 64) return launch_c64<__bf16, 2, 2, PC>(a, groups, st);
+  return launch_c64<__bf16, 1, 4, PC>(a, groups, st);
 }
 
 // out[3] = {rows per chunk, chunks per column strip, column strips} of the launch srx_conv3x3_c64_bf16_fwd would make (host only)
@@ -660,12 +683,24 @@ extern "C" int srx_conv3x3_c64_bf16_plan(int N, int H, int W, int Cout, int* out
 
 extern "C" int srx_conv3x3_c64_bf16_fwd(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk, float slope,
                                         const void* residual, void* y, int y_cs, void* stream) {
-  return c64_fwd_impl(N, H, W, Cout, shuffle, x, wpk, slope, residual, y, y_cs, stream, nullptr);
+  return c64_fwd_impl<false>(N, H, W, Cout, shuffle, x, wpk, slope, nullptr, residual, y, y_cs, stream, nullptr);
 }
 
 extern "C" int srx_conv3x3_c64_f16_fwd(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk, float slope,
                                        const void* residual, void* y, int y_cs, void* stream) {
-  return c64_fwd_impl(N, H, W, Cout, shuffle, x, wpk, slope, residual, y, y_cs, stream, nullptr, true);
+  return c64_fwd_impl<false>(N, H, W, Cout, shuffle, x, wpk, slope, nullptr, residual, y, y_cs, stream, nullptr, true);
+}
+
+// The same layers with one slope per output channel (device array [Cout], 16-byte aligned): y = v > 0 ? v : slopes[c] * v with
+// v = conv(x) + bias, then the optional addend.  No PixelShuffle.
+extern "C" int srx_conv3x3_c64_bf16_fwd_slopes(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk,
+                                               const float* slopes, const void* residual, void* y, int y_cs, void* stream) {
+  return c64_fwd_impl<true>(N, H, W, Cout, shuffle, x, wpk, 0.f, slopes, residual, y, y_cs, stream, nullptr);
+}
+
+extern "C" int srx_conv3x3_c64_f16_fwd_slopes(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk,
+                                              const float* slopes, const void* residual, void* y, int y_cs, void* stream) {
+  return c64_fwd_impl<true>(N, H, W, Cout, shuffle, x, wpk, 0.f, slopes, residual, y, y_cs, stream, nullptr, true);
 }
 
 // Developer aid (tools/bench_c64.py stamps): the same launch with in-kernel cycle stamps; dbg: 256 x 4 (workgroups) x 8 (waves) x 8
@@ -674,7 +709,7 @@ extern "C" int srx_conv3x3_c64_f16_fwd(int N, int H, int W, int Cout, int shuffl
 extern "C" int srx_conv3x3_c64_bf16_fwd_dbg(int N, int H, int W, int Cout, int shuffle, const void* x, const void* wpk, float slope,
                                             const void* residual, void* y, int y_cs, void* stream, unsigned* dbg) {
   SRX_REQUIRE(dbg, "conv3x3_c64_bf16_fwd_dbg: null stamp buffer");
-  return c64_fwd_impl(N, H, W, Cout, shuffle, x, wpk, slope, residual, y, y_cs, stream, dbg);
+  return c64_fwd_impl<false>(N, H, W, Cout, shuffle, x, wpk, slope, nullptr, residual, y, y_cs, stream, dbg);
 }
 
 extern "C" int srx_f32_to_bf16(const float* x, void* y, int64_t n, void* stream) {

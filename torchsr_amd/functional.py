@@ -1568,6 +1568,98 @@ def prelu(x: Tensor, w: Tensor) -> Tensor:
     return _PReLU.apply(x, w)
 
 
+def _slopes16(w: Tensor) -> Tensor:
+    """The slope vector where the kernels can read it in 16-byte pieces (a parameter inside a flat buffer may start anywhere)."""
+    w = _chk(w, 'prelu_channels.weight')
+    return w if w.data_ptr() % 16 == 0 else w.clone()
+
+
+def _prelu_channels_rows(x: Tensor, w: Tensor) -> Tuple[int, int, int]:
+    cs, c = x.shape[-1], w.numel()
+    if x.dim() < 2 or c > cs or c % 4 or cs % 4:
+        raise RuntimeError(f'prelu_channels: {c} slopes on a channel-last tensor of stride {cs}: both must be multiples of 4 and '
+                           f'the slopes no more than the stride')
+    return x.numel() // cs, c, cs
+
+
+class _PReLUChannels(Function):
+    """``nn.PReLU(C)`` on a channel-last tensor: one slope per channel (csrc/compact.hip)."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, w: Tensor):
+        ctx.set_materialize_grads(False)
+        x = _chk(x, 'prelu_channels.input')
+        wd = _slopes16(w.detach())
+        m, c, cs = _prelu_channels_rows(x, wd)
+        y = torch.empty_like(x)
+        call('srx_prelu_channels_fwd', _p(x), _p(wd), _p(y), m, c, cs, _stream())
+        ctx.save_for_backward(x, wd)
+        ctx.param = w
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        if dy is None:
+            return None, None
+        x, w = ctx.saved_tensors
+        dy = _chk(dy, 'prelu_channels.grad')
+        m, c, cs = _prelu_channels_rows(x, w)
+        dx = torch.empty_like(x)
+        sink = _sink(ctx.param) if ctx.needs_input_grad[1] else None
+        dw = None if sink is not None else torch.empty(c, dtype=torch.float32, device=x.device)
+        nws = _lib.lib().srx_prelu_channels_ws_floats(m, c)
+        ws = torch.empty((int(nws) + 1) // 2, dtype=torch.float64, device=x.device)  # (fp64 slots: 8-byte aligned)
+        call('srx_prelu_channels_bwd', _p(dy), _p(x), _p(w), _p(dx), _p(dw if sink is None else sink), 0 if sink is None else 1,
+             m, c, cs, _p(ws), nws, _stream())
+        return dx, (None if dw is None else dw.view(ctx.param.shape))
+
+
+def prelu_channels(x: Tensor, w: Tensor) -> Tensor:
+    """``y = x > 0 ? x : w[c] * x`` on NHWC fp32 ``[..., Cs]`` with ``w`` of ``C <= Cs`` slopes (channels past ``C`` pass
+    through); differentiable in both arguments."""
+    return _PReLUChannels.apply(x, w)
+
+
+_TAIL_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+
+class _ShuffleAddNearest(Function):
+    """The compact generator's tail: ``PixelShuffle(s)`` of the last conv's ``3 s^2`` channels plus the nearest-enlarged input."""
+
+    @staticmethod
+    def forward(ctx, t: Tensor, x4: Tensor, s: int):
+        ctx.set_materialize_grads(False)
+        if t.dtype not in _TAIL_DTYPES:
+            raise RuntimeError(f'shuffle_add_nearest: expected a float32, bfloat16 or float16 tensor, got {t.dtype}')
+        t = _chk(t, 'shuffle_add_nearest.input') if t.dtype == torch.float32 else _chk16(t, 'shuffle_add_nearest.input', None)
+        x4 = _chk(x4, 'shuffle_add_nearest.image')
+        if t.dim() != 4 or x4.dim() != 4 or x4.shape[3] != 4 or tuple(x4.shape[:3]) != tuple(t.shape[:3]):
+            raise RuntimeError(f'shuffle_add_nearest: features {tuple(t.shape)} and NHWC-4 image {tuple(x4.shape)} do not match')
+        n, h, w, cs = t.shape
+        y4 = torch.empty((n, h * s, w * s, 4), dtype=torch.float32, device=t.device)
+        call('srx_shuffle_add_nearest_fwd', _p(t), _TAIL_DTYPES[t.dtype], cs, _p(x4), _p(y4), n, h, w, int(s), _stream())
+        ctx.geom = (n, h, w, cs, int(s), t.dtype)
+        return y4
+
+    @staticmethod
+    def backward(ctx, dy4: Tensor):
+        if dy4 is None:
+            return None, None, None
+        n, h, w, cs, s, dt = ctx.geom
+        if dt != torch.float32:
+            raise RuntimeError('shuffle_add_nearest: only fp32 features are differentiable')
+        dy4 = _chk(dy4, 'shuffle_add_nearest.grad')
+        d = torch.empty((n, h, w, cs), dtype=torch.float32, device=dy4.device)
+        call('srx_shuffle_add_nearest_bwd', _p(dy4), _p(d), cs, n, h, w, s, _stream())
+        return d, None, None  # (the input image is data)
+
+
+def shuffle_add_nearest(t: Tensor, x4: Tensor, s: int) -> Tensor:
+    """``y4[n, s y + i, s x + j, c] = t[n, y, x, c s^2 + i s + j] + x4[n, y, x, c]`` (``c < 3``; channel 3 zero): NHWC-4 fp32 out.
+    ``t``: fp32 (differentiable), bf16 or fp16 ``[N, h, w, >= 3 s^2]``; ``s`` in 2, 3, 4."""
+    return _ShuffleAddNearest.apply(t, x4, int(s))
+
+
 class _LReLU(Function):
     @staticmethod
     def forward(ctx, x: Tensor, slope: float):
@@ -2209,10 +2301,17 @@ class FoldedConv:
     fused PixelShuffle); the skip connection is the epilogue's addend (``srx_conv2d_fwd_residual``).
     Replaces an elementwise pass over the activation per BatchNorm / PReLU of the generator at inference
     (SURVEY.md section 8f row 1).  Folded tensors are cached and rebuilt when any source tensor changes.
+
+    A PReLU with one slope per output channel (the compact generator) stays a vector: the 16-bit chain reads it in the conv's
+    epilogue (``srx_conv3x3_c64_*_fwd_slopes``); in fp32 the conv runs without activation and ``srx_prelu_channels_fwd``
+    follows in place (``ConvState`` and ``srx_conv2d_t`` keep their single slope).  ``pad16``: a 64-input 3x3 layer with fewer
+    than 64 outputs joins the 16-bit chain as a 64-output layer whose surplus filters and biases are zero.
     """
 
-    def __init__(self, conv, bn=None, prelu=None):
+    def __init__(self, conv, bn=None, prelu=None, pad16: bool = False):
         self.conv, self.bn, self.prelu = conv, bn, prelu
+        self.pad16 = bool(pad16)
+        self.slopes = None  # per-channel PReLU: the slope vector (fp32, on the device)
         self._key = None
         self.st = None
         self.pack16 = WeightPack()  # the weights of the 16-bit-native chain (csrc/c64.hip)
@@ -2242,7 +2341,13 @@ class FoldedConv:
             self.b = None if b is None else b.contiguous()
             src = conv._st
             act, slope = src.act, src.slope
-            if self.prelu is not None:
+            self.slopes = None
+            if self.prelu is not None and self.prelu.weight.numel() > 1:
+                if self.prelu.weight.numel() != src.cout or src.act != ACT_NONE or src.shuffle:
+                    raise RuntimeError('FoldedConv: a per-channel PReLU has one slope per output channel and follows a linear '
+                                       'conv without PixelShuffle')
+                self.slopes = _slopes16(self.prelu.weight.detach())
+            elif self.prelu is not None:
                 if self.prelu.weight.numel() != 1 or src.act != ACT_NONE:
                     raise RuntimeError('FoldedConv: PReLU must have one parameter and follow a linear conv')
                 act, slope = ACT_LRELU, float(self.prelu.weight.detach().reshape(()).item())
@@ -2254,7 +2359,8 @@ class FoldedConv:
     def bf16_native_ok(self) -> bool:
         """3x3 / stride 1 / pad 1, 64 input channels, a multiple of 64 outputs: the layers ``srx_conv3x3_c64_bf16_fwd`` runs."""
         st = self.conv._st
-        return (st.k == 3 and st.stride == 1 and st.pad == 1 and st.cin == 64 and st.cout % 64 == 0 and st.up == 0
+        return (st.k == 3 and st.stride == 1 and st.pad == 1 and st.cin == 64 and st.up == 0
+                and (st.cout % 64 == 0 or (self.pad16 and st.cout < 64 and st.shuffle == 0))
                 and (st.shuffle == 0 or (st.shuffle == 2 and st.cout == 256)))
 
     def _call_bf16(self, x: Tensor, residual: Optional[Tensor]) -> Tensor:
@@ -2270,18 +2376,38 @@ class FoldedConv:
         n, h, w, cs = x.shape
         if cs != 64:
             raise RuntimeError(f'folded_conv: {sfx} input has {cs} channels, the layer expects 64')
+        cout = (st.cout + 63) // 64 * 64  # (pad16: the layer as the kernel sees it)
+
+        def pack(fwd, bwd, _):
+            wsrc, bsrc = self.w, self.b
+            if cout != st.cout:  # zero filters and biases: the surplus channels come out as 0 and nobody reads them
+                wsrc = torch.cat([wsrc, wsrc.new_zeros((cout - st.cout,) + tuple(wsrc.shape[1:]))]).contiguous()
+                bsrc = None if bsrc is None else torch.cat([bsrc, bsrc.new_zeros(cout - st.cout)]).contiguous()
+            call(f'srx_conv3x3_c64_{sfx}_pack', _p(wsrc), _p(bsrc), None, cout, st.shuffle, _p(fwd), _stream())
+
         self.pack16.ensure(  # (keyed by the storage type too: fp16 and bf16 packs differ)
-            (self._key, dt), x.device, False, lambda: (_lib.lib().srx_conv3x3_c64_bf16_packed_bytes(st.cout), 0, torch.uint8),
-            lambda fwd, bwd, _: call(f'srx_conv3x3_c64_{sfx}_pack', _p(self.w), _p(self.b), None, st.cout, st.shuffle, _p(fwd), _stream()))
-        y = torch.empty(st.out_shape(n, h, w), dtype=dt, device=x.device)
+            (self._key, dt), x.device, False, lambda: (_lib.lib().srx_conv3x3_c64_bf16_packed_bytes(cout), 0, torch.uint8), pack)
+        y = torch.empty(st.out_shape(n, h, w) if cout == st.cout else (n, h, w, cout), dtype=dt, device=x.device)
         slope = 1.0 if st.act == ACT_NONE else (0.0 if st.act == ACT_RELU else st.slope)
         r = None
         if residual is not None:
             r = _chk16(residual, 'folded_conv.residual', dt)
             if r.shape != y.shape:
                 raise RuntimeError('folded_conv: residual must have the output shape')
-        call(f'srx_conv3x3_c64_{sfx}_fwd', n, h, w, st.cout, st.shuffle, _p(x), _p(self.pack16.fwd), float(slope), _p(r), _p(y),
+        if self.slopes is not None:
+            call(f'srx_conv3x3_c64_{sfx}_fwd_slopes', n, h, w, cout, st.shuffle, _p(x), _p(self.pack16.fwd), _p(self.slopes), _p(r),
+                 _p(y), y.shape[3], _stream())
+            return y
+        call(f'srx_conv3x3_c64_{sfx}_fwd', n, h, w, cout, st.shuffle, _p(x), _p(self.pack16.fwd), float(slope), _p(r), _p(y),
              y.shape[3], _stream())
+        return y
+
+    def _finish_slopes(self, y: Tensor, r: Optional[Tensor]) -> Tensor:
+        """fp32, per-channel PReLU: the conv ran without activation; the slopes in place, then the addend -- the order of the
+        16-bit epilogue."""
+        call('srx_prelu_channels_fwd', _p(y), _p(self.slopes), _p(y), y.numel() // y.shape[3], self.st.cout, y.shape[3], _stream())
+        if r is not None:
+            call('srx_axpby', _p(y), _p(r), _p(y), y.numel(), 1.0, 1.0, _stream())
         return y
 
     def __call__(self, x: Tensor, residual: Optional[Tensor] = None) -> Tensor:
@@ -2310,9 +2436,13 @@ class FoldedConv:
             dref = C.byref(d)
             nws = _lib.lib().srx_wino_ws_floats(dref, 0)
             ws = _ws(nws, x) if nws else None
-            call('srx_wino_fwd_act', dref, _p(x), _p(st.wino_fwd), _p(self.b), _p(r), _p(y), _p(ws), nws, _stream())
-            return y
+            call('srx_wino_fwd_act', dref, _p(x), _p(st.wino_fwd), _p(self.b), None if self.slopes is not None else _p(r), _p(y),
+                 _p(ws), nws, _stream())
+            return y if self.slopes is None else self._finish_slopes(y, r)
         st.pack(self.w, d)
+        if self.slopes is not None:
+            _conv_fwd(d, _p(x), _p(st.wpk_fwd), _p(self.b), _p(y), x, _stream())
+            return self._finish_slopes(y, r)
         _conv_fwd(d, _p(x), _p(st.wpk_fwd), _p(self.b), _p(y), x, _stream(), residual=None if residual is None else (_p(r), 1.0))
         return y
 

@@ -90,6 +90,8 @@ class BatchNorm2d(nn.BatchNorm2d):
 
 class PReLU(nn.PReLU):
     def forward(self, x: Tensor) -> Tensor:
+        if self.weight.numel() > 1:  # nn.PReLU(C): one slope per channel (the compact generator)
+            return F.prelu_channels(x, _w(self.weight))
         return F.prelu(x, _w(self.weight))
 
 

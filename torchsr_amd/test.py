@@ -28,9 +28,23 @@ TRUNK_MAX_PIXELS = 8 * 1000 * 1000  # LR pixels the staged path runs untiled (x2
 
 
 def load_generator_state(path: str) -> OrderedDict:
+    """The generator's state_dict from a checkpoint: this package's ``{"epoch", "phase", "state"}``, Real-ESRGAN's
+    ``{"params_ema": ...}`` (preferred) or ``{"params": ...}``, or a bare state_dict; DDP's ``module.`` prefix is dropped."""
     ckpt = torch.load(path, map_location='cpu')
-    state = ckpt['state'] if isinstance(ckpt, dict) and 'state' in ckpt else ckpt
+    state = ckpt
+    for key in ('state', 'params_ema', 'params'):
+        if isinstance(ckpt, dict) and isinstance(ckpt.get(key), dict):
+            state = ckpt[key]
+            break
     return OrderedDict((k[len('module.'):] if k.startswith('module.') else k, v) for k, v in state.items())
+
+
+def compact_num_conv(state) -> int:
+    """The number of body convs of an SRVGGNetCompact state_dict: its last key is ``body.{2 num_conv + 2}.weight`` / ``.bias``."""
+    idx = [int(k.split('.')[1]) for k in state if k.startswith('body.') and k.split('.')[1].isdigit()]
+    if not idx or max(idx) < 4 or max(idx) % 2:
+        raise RuntimeError(f'not a compact (SRVGGNetCompact) state_dict: keys {list(state)[:4]} ...')
+    return (max(idx) - 2) // 2
 
 
 @torch.no_grad()
@@ -41,7 +55,7 @@ def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
 
     ``precision``: ``'fp32'`` (exact; the reference's ``test`` runs no autocast, test.py:57-62), ``'bf16'`` (bf16
     products with fp32 accumulation in every conv but the 3-channel INPUT conv) or ``'fp16'``
-    (a generator with the 16-bit-native chain -- SRGAN's ``Generator.native16`` -- only: fp16 products with fp32
+    (a generator with the 16-bit-native chain -- ``Generator.native16``: SRGAN, compact -- only: fp16 products with fp32
     accumulation in every conv, the 64-channel activations stored as fp16; a non-finite output, i.e. an overflow of
     fp16's +-65504, raises ``FloatingPointError``); ``None`` keeps whatever the generator's convs are set to.  The setting
     is restored afterwards.  ``staged=False`` forces the halo tiling for a generator that offers the two-stage interface
@@ -91,7 +105,7 @@ def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
         if precision not in ('fp32', 'bf16', 'fp16'):
             raise ValueError(f"upscale: precision must be 'fp32', 'bf16' or 'fp16', got {precision!r}")
         if precision == 'fp16' and (not hasattr(generator, 'native16') or _dev.NO_C64 or _dev.NO_T9):
-            raise ValueError(f"upscale: precision 'fp16' needs a generator with the 16-bit-native chain (SRGAN; "
+            raise ValueError(f"upscale: precision 'fp16' needs a generator with the 16-bit-native chain (SRGAN, compact; "
                              f"{type(generator).__name__} has none) and its kernels enabled (SRX_NO_C64 / SRX_NO_T9 unset)")
         saved = [(m, m._st.precision) for m in generator.modules() if isinstance(m, Conv2d)]
         if precision == 'fp16':  # inference only: set here, never through set_conv_precision (training has no fp16)
@@ -205,8 +219,12 @@ def test(args: Namespace, model: object, device) -> None:
     import numpy as np
     from PIL import Image
     from .srgan.trainer import save_image
-    generator = model().to(device)
-    generator.load_state_dict(load_generator_state(f'{args.model.lower()}-gan-best.pth'))
+    state = load_generator_state(getattr(args, 'weights', None) or f'{args.model.lower()}-gan-best.pth')
+    if args.model.lower() == 'compact':  # a 16-conv and a 32-conv file both load: the depth is the file's
+        generator = model(num_conv=compact_num_conv(state)).to(device)
+    else:
+        generator = model().to(device)
+    generator.load_state_dict(state)
     image = np.asarray(Image.open(args.image).convert('RGB'), dtype='float32') / 255.0
     low_res = torch.from_numpy(image).permute(2, 0, 1).unsqueeze(0).contiguous().to(device)
     super_res = upscale(generator, low_res, precision=getattr(args, 'precision', None) or 'fp32',

@@ -17,7 +17,7 @@ import torch
 import torch.distributed as dist
 
 from torchsr_amd.constants import BATCH_SIZE, EPOCHS, MODEL, PRE_EPOCHS, TRAIN_DIR
-from torchsr_amd.models import MODELS, select_test_model, select_trainer_model
+from torchsr_amd.models import model_names, select_test_model, select_trainer_model
 
 try:  # optional, as in the reference (torchsr.py:26-29)
     import wandb
@@ -121,7 +121,10 @@ def parse_args(argv=None) -> Namespace:
     train.add_argument('--gan-checkpoint', type=str, default=None)
     train.add_argument('--master-addr', type=str, default=None)
     train.add_argument('--master-port', type=str, default=None)
-    train.add_argument('--model', type=str, default=MODEL, choices=MODELS.keys())
+    train.add_argument('--model', type=str, default=MODEL, choices=model_names())
+    train.add_argument('--num-conv', type=positive_integer, default=None, metavar='N',
+                       help='--model compact only: the number of 64 -> 64 body convs of SRVGGNetCompact (default 32, '
+                            'realesr-general-x4v3; realesr-animevideov3 has 16)')
     train.add_argument('--pretrain-epochs', type=int, default=PRE_EPOCHS)
     train.add_argument('--psnr-checkpoint', type=str, default=None)
     train.add_argument('--seed', type=int, default=0)
@@ -166,11 +169,15 @@ def parse_args(argv=None) -> Namespace:
                             'does); the skipped steps are counted and logged per epoch')
     test = commands.add_parser('test', help='Generate a super resolution image from a trained model.')
     test.add_argument('image', type=str)
-    test.add_argument('--model', type=str, default=MODEL, choices=MODELS.keys())
+    test.add_argument('--model', type=str, default=MODEL, choices=model_names())
+    test.add_argument('--weights', type=str, default=None, metavar='PATH',
+                      help='the checkpoint to load (default: <model>-gan-best.pth in the working directory): a bare state_dict, '
+                           'this package\'s {"state": ...} or Real-ESRGAN\'s {"params_ema": ...} / {"params": ...}.  For --model '
+                           'compact the number of body convs is read off the file')
     test.add_argument('--precision', type=str, default='fp32', choices=('fp32', 'bf16', 'fp16'),
                       help='conv arithmetic of the generator forward: exact fp32 (the reference runs no autocast here), '
                            'bf16 products with fp32 accumulation, or fp16 products and fp16-stored activations with fp32 '
-                           'accumulation (SRGAN only; an fp16 overflow is reported, not written)')
+                           'accumulation (SRGAN and compact; an fp16 overflow is reported, not written)')
     test.add_argument('--self-ensemble', type=int, nargs='?', const=8, default=0, choices=(4, 8),
                       help='geometric self-ensemble: run the generator on the 8 flips / transposes of the image (4: the '
                            'flips only), map every result back and average them.  Costs N generator forwards instead of '
@@ -186,6 +193,11 @@ def parse_args(argv=None) -> Namespace:
                            'enlarged image; adain: map every channel to the image\'s mean and standard deviation.  Runs behind '
                            'the ensemble average and before --outscale; combines with every other option')
     args = parser.parse_args(argv)
+    if args.function == 'train':
+        if args.num_conv is not None and args.model.lower() != 'compact':
+            parser.error(f'--num-conv sets the depth of --model compact; --model {args.model} has none')
+        if args.num_conv is None:
+            args.num_conv = 32
     if args.function == 'train' and args.poisson_noise_prob > 0 and not (args.device_data and args.degradation in ('blind', 'blind2')):
         parser.error('--poisson-noise-prob replaces the Gaussian noise of a blind degradation: add --device-data and '
                      '--degradation blind or --degradation blind2')
