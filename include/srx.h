@@ -563,6 +563,13 @@ int srx_copy_channels(const float* src, int src_cs, int src_off, float* dst, int
 /* F.interpolate(scale_factor=2, mode='nearest') (esrgan/generator.py:73,76) and its adjoint; x is [N][H][W][C] */
 int srx_upsample_nearest2x_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream);
 int srx_upsample_nearest2x_bwd(const float* dy, float* dx, int N, int H, int W, int C, void* stream);
+/* F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) and its adjoint on NHWC fp32: x is
+ * [N][H][W][Cs], y [N][2H][2W][Cs]; the first C channels (rounded up to whole quads, which must fit in
+ * Cs) are computed, the others are left alone.  Weights 0.75 / 0.25 per direction, the neighbour clamped
+ * at the border.  The adjoint is a gather (every input pixel adds its at most 4 x 4 output pixels in a
+ * fixed order): no atomics, repeatable bits.  Cs a multiple of 4, tensors 16-byte aligned. */
+int srx_upsample_bilinear2x_fwd(const float* x, float* y, int N, int H, int W, int C, int Cs, void* stream);
+int srx_upsample_bilinear2x_bwd(const float* dy, float* dx, int N, int H, int W, int C, int Cs, void* stream);
 /* nn.Sigmoid of the SRGAN discriminator head (srgan/discriminator.py:68) */
 int srx_sigmoid_fwd(const float* x, float* y, int64_t n, void* stream);
 int srx_sigmoid_bwd(const float* dy, const float* y, float* dx, int64_t n, void* stream);
@@ -893,6 +900,25 @@ int srx_grad_guard(const float* g, int64_t n, float grad_scale, float max_norm, 
 int srx_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, const float* lr, float beta1,
                           float beta2, float eps, float grad_scale, int64_t* step,
                           const srx_grad_guard_t* state, void* stream);
+
+/* Spectral normalisation of a weight W [rows][cols] (a conv's [Cout][Cin * KH * KW]), the semantics of
+ * torch.nn.utils.spectral_norm with n_power_iterations = 1 and eps = 1e-12.
+ *   train != 0:  v <- W^T u / max(|W^T u|, eps);  u <- W v / max(|W v|, eps)   (u, v updated in place)
+ *   always:      sigma = u . (W v);  W_sn = W / sigma
+ * uv_keep (optional, roundup(rows, 4) + cols floats): the u and v this call used for sigma, for the
+ * backward -- u and v themselves move on with the next training call.  The training call reads W three
+ * times and writes W_sn once.  Grids and reduction trees are fixed functions of (rows, cols) and there
+ * are no floating-point atomics: the same inputs give the same bits.
+ * Refused: null pointers, W / v / W_sn / ws / uv_keep not 16-byte aligned, cols not a multiple of 4,
+ * rows * cols >= 2^31, ws shorter than srx_spectral_norm_ws_floats(rows, cols). */
+size_t srx_spectral_norm_ws_floats(int rows, int cols);
+int srx_spectral_norm_fwd(const float* W, float* u, float* v, float* W_sn, float* sigma, float* uv_keep, int rows,
+                          int cols, int train, float* ws, size_t ws_floats, void* stream);
+/* Its backward: with G = dL/dW_sn and W_sn = W / sigma (formed on the fly from W, so the caller's W_sn
+ * buffer may have been overwritten since),  dW (+)= (G - <G, W_sn> u v^T) / sigma;  u, v, sigma: those
+ * of the forward (uv_keep).  accumulate != 0 adds to dW.  Same refusals and the same workspace size. */
+int srx_spectral_norm_bwd(const float* G, const float* W, const float* u, const float* v, const float* sigma,
+                          float* dW, int accumulate, int rows, int cols, float* ws, size_t ws_floats, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 """Trainer of the compact generator (Real-ESRGAN's SRVGGNetCompact).
 
 The discriminator, the losses (L1 pre-training; relativistic-average GAN, ``0.01 L1 + VGG + 0.005 adversarial``), the amp
-phases and the hipGraph capture are ESRGAN's, unchanged; only the generator differs.  ``args.num_conv`` (``train --num-conv``)
+phases and the hipGraph capture are ESRGAN's, unchanged; only the generator differs.  (``train --discriminator unet`` swaps the
+critic and its loss: ``realesrgan/trainer.py``.)  ``args.num_conv`` (``train --num-conv``)
 sets the number of body convs.
 """
 import functools

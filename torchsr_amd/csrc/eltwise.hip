@@ -445,6 +445,72 @@ __global__ void upsample2x_bwd_kernel(const float* __restrict__ dy, float* __res
   }
 }
 
+// F.interpolate(scale_factor=2, mode='bilinear', align_corners=False): output o = 2 i + p reads input i with weight 0.75 and
+// its neighbour i - 1 (p = 0) / i + 1 (p = 1), clamped at the border, with 0.25 -- separably in both directions.  C: channels
+// processed (whole quads), Cs: the channel stride of both tensors.
+__global__ void bilinear2x_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W, int C, int Cs) {
+  const int cq = (C + 3) / 4;
+  const int64_t total = (int64_t)N * 2 * H * 2 * W * cq;
+  GRID_STRIDE(i, total) {
+    const int q = (int)(i % cq);
+    int64_t t = i / cq;
+    const int ow = (int)(t % (2 * W));
+    t /= 2 * W;
+    const int oh = (int)(t % (2 * H));
+    const int n = (int)(t / (2 * H));
+    const int h0 = oh >> 1, w0 = ow >> 1;
+    int h1 = h0 + ((oh & 1) ? 1 : -1), w1 = w0 + ((ow & 1) ? 1 : -1);
+    h1 = h1 < 0 ? 0 : (h1 > H - 1 ? H - 1 : h1);
+    w1 = w1 < 0 ? 0 : (w1 > W - 1 ? W - 1 : w1);
+    const float* r0 = x + ((int64_t)n * H + h0) * W * Cs + q * 4;
+    const float* r1 = x + ((int64_t)n * H + h1) * W * Cs + q * 4;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(r0 + (int64_t)w0 * Cs), b = *reinterpret_cast<const f32x4*>(r0 + (int64_t)w1 * Cs);
+    const f32x4 c = *reinterpret_cast<const f32x4*>(r1 + (int64_t)w0 * Cs), d = *reinterpret_cast<const f32x4*>(r1 + (int64_t)w1 * Cs);
+    *reinterpret_cast<f32x4*>(y + (((int64_t)n * 2 * H + oh) * 2 * W + ow) * Cs + q * 4) =
+        0.75f * (0.75f * a + 0.25f * b) + 0.25f * (0.75f * c + 0.25f * d);
+  }
+}
+
+// the four output rows (columns) that read input row (column) i, and their weights; a clamped neighbour adds its 0.25 to the
+// border row itself.  Entries with weight 0 are skipped by the caller.
+__device__ __forceinline__ void bilinear2x_taps(int i, int n, int o[4], float wt[4]) {
+  o[0] = 2 * i - 1; wt[0] = i > 0 ? 0.25f : 0.f;
+  o[1] = 2 * i;     wt[1] = i > 0 ? 0.75f : 1.f;
+  o[2] = 2 * i + 1; wt[2] = i < n - 1 ? 0.75f : 1.f;
+  o[3] = 2 * i + 2; wt[3] = i < n - 1 ? 0.25f : 0.f;
+}
+
+// its adjoint as a gather: every input pixel adds its (at most 4 x 4) output pixels in a fixed order -- no atomics
+__global__ void bilinear2x_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int N, int H, int W, int C, int Cs) {
+  const int cq = (C + 3) / 4;
+  const int64_t total = (int64_t)N * H * W * cq;
+  GRID_STRIDE(i, total) {
+    const int q = (int)(i % cq);
+    int64_t t = i / cq;
+    const int w = (int)(t % W);
+    t /= W;
+    const int h = (int)(t % H);
+    const int n = (int)(t / H);
+    int oh[4], ow[4];
+    float wh[4], ww[4];
+    bilinear2x_taps(h, H, oh, wh);
+    bilinear2x_taps(w, W, ow, ww);
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      if (wh[a] == 0.f) continue;
+      f32x4 row = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        if (ww[b] == 0.f) continue;
+        row += ww[b] * *reinterpret_cast<const f32x4*>(dy + (((int64_t)n * 2 * H + oh[a]) * 2 * W + ow[b]) * Cs + q * 4);
+      }
+      s += wh[a] * row;
+    }
+    *reinterpret_cast<f32x4*>(dx + (((int64_t)n * H + h) * W + w) * Cs + q * 4) = s;
+  }
+}
+
 }  // namespace
 
 extern "C" int srx_copy_channels(const float* src, int src_cs, int src_off, float* dst, int dst_cs, int dst_off, int C,
@@ -485,6 +551,31 @@ extern "C" int srx_upsample_nearest2x_bwd(const float* dy, float* dx, int N, int
   hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(stream_grid((int64_t)N * H * W * (C / 4))), dim3(256), 0,
                      srx_stream(stream), dy, dx, N, H, W, C);
   SRX_CHECK_LAUNCH("upsample2x_bwd_kernel");
+  return SRX_OK;
+}
+
+static int bilinear2x_check(const void* a, const void* b, int N, int H, int W, int C, int Cs, const char* who) {
+  SRX_REQUIRE(a && b && a != b, "%s: null or aliased pointer", who);
+  SRX_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 15) == 0, "%s: tensors must be 16-byte aligned", who);
+  SRX_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && Cs > 0 && Cs % 4 == 0 && (C + 3) / 4 * 4 <= Cs,
+              "%s: sizes must be positive, the channel stride a multiple of 4 and the channels, rounded up to quads, within it", who);
+  SRX_REQUIRE((int64_t)N * 4 * H * W * Cs < (1LL << 40), "%s: tensor too large", who);
+  return SRX_OK;
+}
+
+extern "C" int srx_upsample_bilinear2x_fwd(const float* x, float* y, int N, int H, int W, int C, int Cs, void* stream) {
+  if (int rc = bilinear2x_check(x, y, N, H, W, C, Cs, "upsample_bilinear2x_fwd")) return rc;
+  hipLaunchKernelGGL(bilinear2x_fwd_kernel, dim3(stream_grid((int64_t)N * 4 * H * W * ((C + 3) / 4))), dim3(256), 0,
+                     srx_stream(stream), x, y, N, H, W, C, Cs);
+  SRX_CHECK_LAUNCH("bilinear2x_fwd_kernel");
+  return SRX_OK;
+}
+
+extern "C" int srx_upsample_bilinear2x_bwd(const float* dy, float* dx, int N, int H, int W, int C, int Cs, void* stream) {
+  if (int rc = bilinear2x_check(dy, dx, N, H, W, C, Cs, "upsample_bilinear2x_bwd")) return rc;
+  hipLaunchKernelGGL(bilinear2x_bwd_kernel, dim3(stream_grid((int64_t)N * H * W * ((C + 3) / 4))), dim3(256), 0,
+                     srx_stream(stream), dy, dx, N, H, W, C, Cs);
+  SRX_CHECK_LAUNCH("bilinear2x_bwd_kernel");
   return SRX_OK;
 }
 

@@ -29,8 +29,8 @@ direct_grads = [False]
 
 
 def _sink(param: Optional[Tensor]) -> Optional[Tensor]:
-    if not direct_grads[0] or param is None or not param.requires_grad:
-        return None
+    if not direct_grads[0] or param is None or not param.requires_grad or not param.is_leaf:
+        return None  # (not a leaf: a spectrally normalised weight, whose gradient goes on through autograd)
     g = param.grad
     if g is None or not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
         return None
@@ -1209,6 +1209,7 @@ class _Conv2d(Function):
         ctx.params = (weight, bias)
         ctx.save_for_backward(x, y if st.act != ACT_NONE else None)
         ctx.wpk_bwd = st.wpk_bwd
+        ctx.sn_calls = getattr(st, 'sn_calls', None)  # (SNConvState: which normalised weight the packed copies hold)
         if want_stats:
             ctx.mark_non_differentiable(part)
             return y, part
@@ -1228,6 +1229,10 @@ class _Conv2d(Function):
             call('srx_act_bwd_from_out', _p(dy), _p(y), _p(g), dy.numel(), st.act, st.slope, s)
             dy = g
         dx = None
+        if ctx.needs_input_grad[0] and ctx.sn_calls is not None and ctx.sn_calls != st.sn_calls:
+            raise RuntimeError('conv2d: this spectrally normalised layer ran forward again before this backward: its one W_sn buffer '
+                               'and packed copies now hold the later call\'s weight, and the input gradient would be taken through '
+                               'it.  Run the backward of a call before the layer\'s next forward (or both inputs as one batch)')
         if ctx.needs_input_grad[0]:  # ... with the backward of the activation that produced x (in_act)
             dx, masked = _layer_dgrad(st, d, ctx.master, ctx.wino, st.wino_bwd if ctx.wino else None, ctx.wpk_bwd, dy, x, ctx.in_act, s)
             if masked:
@@ -2822,3 +2827,90 @@ class _Upsample2x(Function):
 def upsample_nearest2x(x: Tensor) -> Tensor:
     """F.interpolate(x, scale_factor=2, mode='nearest') (esrgan/generator.py:73,76) on NHWC."""
     return _Upsample2x.apply(x)
+
+
+class _UpsampleBilinear2x(Function):
+    @staticmethod
+    def forward(ctx, x: Tensor):
+        ctx.set_materialize_grads(False)
+        x = _chk(x, 'upsample_bilinear2x.input')
+        n, h, w, c = x.shape
+        if c % 4:
+            raise RuntimeError(f'upsample_bilinear2x: the channel stride must be a multiple of 4, got {c}')
+        y = torch.empty((n, 2 * h, 2 * w, c), dtype=torch.float32, device=x.device)
+        call('srx_upsample_bilinear2x_fwd', _p(x), _p(y), n, h, w, c, c, _stream())
+        ctx.shape = (n, h, w, c)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        dy = _chk(dy, 'upsample_bilinear2x.grad')
+        n, h, w, c = ctx.shape
+        dx = torch.empty((n, h, w, c), dtype=torch.float32, device=dy.device)
+        call('srx_upsample_bilinear2x_bwd', _p(dy), _p(dx), n, h, w, c, c, _stream())
+        return dx
+
+
+def upsample_bilinear2x(x: Tensor) -> Tensor:
+    """F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=False) on NHWC (the U-Net discriminator's decoder)."""
+    return _UpsampleBilinear2x.apply(x)
+
+
+# --------------------------------------------------------------------------- spectral normalisation
+class SNConvState(ConvState):
+    """``ConvState`` of a conv that multiplies a spectrally normalised copy of its weight.  The copy lives in ONE persistent
+    buffer per layer (a captured step holds its address) that every ``spectral_norm`` call rewrites by raw pointer, so neither
+    its address nor its ``_version`` says that the packed copies are stale: ``sn_calls``, bumped by each call, is part of the
+    key.  Such layers stay out of ``PackTable``, whose launch after Adam repacks from the Parameters."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.sn_calls = 0
+
+    def pack_key(self, weight: Tensor):
+        return super().pack_key(weight) + (self.sn_calls,)
+
+
+class _SpectralNorm(Function):
+    @staticmethod
+    def forward(ctx, w: Tensor, u: Tensor, v: Tensor, out: Tensor, train: bool, master):
+        ctx.set_materialize_grads(False)
+        w, out = _chk(w, 'spectral_norm.weight'), _chk(out, 'spectral_norm.out')
+        u, v = _chk(u, 'spectral_norm.u'), _chk(v, 'spectral_norm.v')
+        rows = w.shape[0]
+        cols = w.numel() // rows
+        if u.numel() != rows or v.numel() != cols or out.numel() != w.numel():
+            raise RuntimeError(f'spectral_norm: a {rows} x {cols} weight needs u[{rows}], v[{cols}] and an output of its size, got '
+                               f'{u.numel()}, {v.numel()}, {out.numel()}')
+        sigma = torch.empty(1, dtype=torch.float32, device=w.device)
+        keep = torch.empty(round4(rows) + cols, dtype=torch.float32, device=w.device) if ctx.needs_input_grad[0] else None
+        nws = _lib.lib().srx_spectral_norm_ws_floats(rows, cols)
+        call('srx_spectral_norm_fwd', _p(w), _p(u), _p(v), _p(out), _p(sigma), _p(keep), rows, cols, int(bool(train)),
+             _p(_ws(nws, w)), nws, _stream())
+        ctx.w, ctx.keep, ctx.sigma, ctx.master, ctx.dims = w, keep, sigma, master[0], (rows, cols)
+        return out.detach()  # (a fresh alias: the persistent buffer itself never carries a grad_fn)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        if g is None or ctx.keep is None:
+            return None, None, None, None, None, None
+        g = _chk(g, 'spectral_norm.grad')
+        rows, cols = ctx.dims
+        sink = _sink(ctx.master)
+        dw = sink if sink is not None else torch.empty_like(ctx.w)
+        nws = _lib.lib().srx_spectral_norm_ws_floats(rows, cols)
+        call('srx_spectral_norm_bwd', _p(g), _p(ctx.w), _p(ctx.keep), ctx.keep.data_ptr() + 4 * round4(rows), _p(ctx.sigma), _p(dw),
+             0 if sink is None else 1, rows, cols, _p(_ws(nws, g)), nws, _stream())
+        return (dw if sink is None else None), None, None, None, None, None
+
+
+def spectral_norm(w: Tensor, u: Tensor, v: Tensor, out: Tensor, train: bool, master: Optional[Tensor] = None) -> Tensor:
+    """``torch.nn.utils.spectral_norm``'s weight (one power iteration, eps 1e-12) written into the persistent buffer ``out``.
+
+    ``train``: ``u`` and ``v`` take one power iteration in place first (no gradient flows through them); otherwise sigma comes
+    from the stored vectors.  The backward is the closed form ``dW = (G - <G, W_sn> u v^T) / sigma`` with the vectors of THIS
+    call; it accumulates into ``master.grad`` when the trainers' flat gradient buffers are on (``direct_grads``).  The returned
+    tensor aliases ``out``: a later call overwrites it, so a conv that used it must have run (and packed it) before -- and its
+    backward too: ``_Conv2d.backward`` refuses an ``SNConvState`` layer whose call counter has moved since its forward."""
+    # (the Parameter travels in a tuple: as a tensor argument it would make the output require a gradient under no_weight_grad)
+    return _SpectralNorm.apply(w, u, v, out, train, (w if master is None else master,))

@@ -9,6 +9,7 @@ the reference.
 """
 import contextlib
 
+import torch
 from torch import nn, Tensor
 
 from . import functional as F
@@ -70,13 +71,57 @@ class Conv2d(nn.Conv2d):
         return new
 
 
+class SNConv2d(nn.Module):
+    """A bias-free conv under ``torch.nn.utils.spectral_norm`` (one power iteration, eps 1e-12) with that wrapper's
+    ``state_dict`` keys: ``weight_orig`` (the Parameter), ``weight_u`` and ``weight_v`` (buffers, updated by every training-mode
+    forward).  ``functional.spectral_norm`` writes the normalised weight into one persistent buffer per layer, which the conv
+    packs from on every call (``functional.SNConvState``); the conv's weight gradient goes back to autograd as a tensor, and the
+    normalisation's backward accumulates into ``weight_orig.grad``.
+
+    One buffer per layer means one live forward per layer: ``D(a); D(b); (la + lb).backward()`` in training mode would take the
+    first call's input gradient through the second call's weight, so the conv's backward raises when the layer has run forward
+    again since (torch's wrapper keeps a weight per call).  Run the two inputs as one batch, as ``pair_loss_nhwc`` does, or
+    finish a call's backward before the next forward, as the trainer's phases do."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, act=ACT_NONE, slope=0.0):
+        super().__init__()
+        self.in_channels, self.out_channels, self.kernel_size = in_channels, out_channels, kernel_size
+        self.stride, self.padding = stride, padding
+        conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, bias=False)  # torch's default init
+        self.weight_orig = nn.Parameter(conv.weight.detach().clone())
+        rows, cols = out_channels, in_channels * kernel_size * kernel_size
+        # (torch.nn.utils.spectral_norm's start: u ~ N(0, 1) normalised, v = normalize(W^T u))
+        u = nn.functional.normalize(torch.randn(rows), dim=0, eps=1e-12)
+        v = nn.functional.normalize(self.weight_orig.detach().reshape(rows, cols).t().mv(u), dim=0, eps=1e-12)
+        self.register_buffer('weight_u', u)
+        self.register_buffer('weight_v', v)
+        self._st = F.SNConvState(in_channels, out_channels, kernel_size, stride, padding, act=act, slope=slope)
+        self._w_sn = None
+
+    def normalised_weight(self) -> Tensor:
+        """One ``functional.spectral_norm`` call (training mode: with its power iteration) into the layer's buffer."""
+        w = self.weight_orig
+        if self._w_sn is None or self._w_sn.device != w.device:
+            self._w_sn = torch.empty(w.shape, dtype=torch.float32, device=w.device)
+        self._st.sn_calls += 1
+        return F.spectral_norm(_w(w), self.weight_u, self.weight_v, self._w_sn, self.training, w)
+
+    def forward(self, x: Tensor) -> Tensor:
+        w_sn = self.normalised_weight()
+        return F.conv2d(x, w_sn, None, self._st, False, w_sn)[0]
+
+    def extra_repr(self) -> str:
+        return (f'{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, '
+                f'padding={self.padding}, spectral norm')
+
+
 def set_conv_precision(module: nn.Module, precision: str) -> None:
     """``'bf16'``: every conv of ``module`` multiplies bf16-rounded operands and accumulates in fp32 (forward
     and stride-1 data gradient) -- this package's reading of the reference's ``autocast`` region
     (srgan/trainer.py:379-383).  ``'fp32'`` restores exact fp32."""
     p = {'fp32': 0, 'bf16': 1}[precision]
     for m in module.modules():
-        if isinstance(m, Conv2d):
+        if isinstance(m, (Conv2d, SNConv2d)):
             m._st.precision = p
 
 
@@ -120,5 +165,5 @@ class Marker(nn.Module):
         return x
 
 
-__all__ = ['no_weight_grad', 'Conv2d', 'BatchNorm2d', 'PReLU', 'LeakyReLU', 'Linear', 'Marker', 'ACT_NONE',
+__all__ = ['no_weight_grad', 'Conv2d', 'SNConv2d', 'BatchNorm2d', 'PReLU', 'LeakyReLU', 'Linear', 'Marker', 'ACT_NONE',
            'ACT_RELU', 'ACT_LRELU']

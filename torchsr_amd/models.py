@@ -39,6 +39,14 @@ GENERATORS = {
 }
 
 
+DISCRIMINATORS = ('vgg', 'unet')  # train --discriminator: the model's own VGG-style critic, or Real-ESRGAN's U-Net
+
+
+def _unet_trainers() -> dict:
+    from torchsr_amd.realesrgan.trainer import UNetCompactTrainer, UNetESRGANTrainer
+    return {'esrgan': UNetESRGANTrainer, 'compact': UNetCompactTrainer}
+
+
 def model_names() -> Tuple[str, ...]:
     """Every ``--model`` the command line accepts."""
     return tuple(sorted({**MODELS, **EXTRA_MODELS}))
@@ -47,6 +55,15 @@ def model_names() -> Tuple[str, ...]:
 def select_trainer_model(args: Namespace) -> Tuple[object, int]:
     """Trainer class and crop size for ``args.model`` (case-insensitive), models.py:26-53."""
     name = args.model.lower()
+    disc = (getattr(args, 'discriminator', None) or 'vgg').lower()
+    if disc not in DISCRIMINATORS:
+        raise RuntimeError(f'discriminator {disc} not supported. Please choose from: {DISCRIMINATORS}')
+    if disc == 'unet':
+        trainers = _unet_trainers()
+        if name not in trainers:
+            raise RuntimeError(f'--discriminator unet trains with --model {" or ".join(sorted(trainers))}; --model {args.model} '
+                               'keeps its own discriminator')
+        return trainers[name], {**CROP_SIZE, **EXTRA_CROP_SIZE}[name]
     if name in MODELS:
         return MODELS[name], CROP_SIZE[name]
     if name in EXTRA_MODELS:

@@ -335,6 +335,13 @@ class SRGANTrainer:
         extra = (checkpoint or {}).get('resume')
         if not extra:
             return False
+        have, want = set(extra['discriminator']), set(self.discriminator.state_dict())
+        if have != want:
+            kind = lambda keys: 'unet' if any(k.endswith('.weight_orig') for k in keys) else 'vgg'  # noqa: E731
+            raise RuntimeError(f'the checkpoint holds a "{kind(have)}" discriminator, this run trains a "{kind(want)}" one: resume '
+                               f'with --discriminator {kind(have)} (or without the checkpoint)'
+                               if kind(have) != kind(want) else
+                               f'the checkpoint\'s discriminator does not fit this run\'s: keys {sorted(have ^ want)[:4]} ... differ')
         self.discriminator.load_state_dict(extra['discriminator'])
         for name in ('psnr_optimizer', 'gen_optimizer', 'disc_optimizer', 'gen_scheduler', 'disc_scheduler'):
             getattr(self, name).load_state_dict(extra[name])

@@ -125,6 +125,11 @@ def parse_args(argv=None) -> Namespace:
     train.add_argument('--num-conv', type=positive_integer, default=None, metavar='N',
                        help='--model compact only: the number of 64 -> 64 body convs of SRVGGNetCompact (default 32, '
                             'realesr-general-x4v3; realesr-animevideov3 has 16)')
+    train.add_argument('--discriminator', type=str, default='vgg', choices=('vgg', 'unet'),
+                       help='the critic of the GAN phase.  vgg: the model\'s own VGG-style discriminator with the relativistic '
+                            'loss (one logit per crop).  unet: Real-ESRGAN\'s UNetDiscriminatorSN -- a U-Net with spectral '
+                            'normalisation and no BatchNorm that returns a logit per pixel -- trained with the plain GAN loss, '
+                            'adversarial weight 0.1; --model esrgan and --model compact, one GPU')
     train.add_argument('--pretrain-epochs', type=int, default=PRE_EPOCHS)
     train.add_argument('--psnr-checkpoint', type=str, default=None)
     train.add_argument('--seed', type=int, default=0)
@@ -198,6 +203,9 @@ def parse_args(argv=None) -> Namespace:
             parser.error(f'--num-conv sets the depth of --model compact; --model {args.model} has none')
         if args.num_conv is None:
             args.num_conv = 32
+    if args.function == 'train' and args.discriminator == 'unet' and args.model.lower() not in ('esrgan', 'compact'):
+        parser.error(f'--discriminator unet trains with --model esrgan or --model compact; --model {args.model} keeps its own '
+                     'discriminator')
     if args.function == 'train' and args.poisson_noise_prob > 0 and not (args.device_data and args.degradation in ('blind', 'blind2')):
         parser.error('--poisson-noise-prob replaces the Gaussian noise of a blind degradation: add --device-data and '
                      '--degradation blind or --degradation blind2')
