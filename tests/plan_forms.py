@@ -35,6 +35,21 @@ C64_MULTI_ITEM = [
     # the other strip (128 + 2 columns: a ragged one) and another chunk
     dict(id='129x15x130.c64.res', shape=(129, 15, 130), cout=64, shuffle=0, res=True, min_chunks=3, min_strips=2),
 ]
+# The per-channel-PReLU instantiations (srx_conv3x3_c64_{bf16,f16}_fwd_slopes: c64_kernel<.., PC = true>, the compact generator's
+# body): each tile form <RW, CW> -- <4, 1> up to 32 pixels per row, <2, 2> up to 64, <1, 4> beyond -- one item per workgroup and
+# several (multi: more items than workgroups, as above), with and without an addend, and two channel groups (Cout 128: the
+# slopes 64..127 belong to group 1).
+C64_SLOPES = [
+    dict(id='1x37x64.c64', shape=(1, 37, 64), cout=64, res=False, form=(2, 2), multi=False),            # odd rows, the widest <2, 2> frame
+    dict(id='1x40x150.c64.res', shape=(1, 40, 150), cout=64, res=True, form=(1, 4), multi=False),       # a ragged second strip
+    dict(id='3x9x33.c128', shape=(3, 9, 33), cout=128, res=False, form=(2, 2), multi=False),            # two channel groups
+    dict(id='260x5x9.c64.res', shape=(260, 5, 9), cout=64, res=True, form=(4, 1), multi=True),          # 260 items on 256 workgroups
+    dict(id='260x6x40.c64', shape=(260, 6, 40), cout=64, res=False, form=(2, 2), multi=True),           # 260 items on 256 workgroups
+    dict(id='129x15x130.c64.res', shape=(129, 15, 130), cout=64, res=True, form=(1, 4), multi=True),    # 774 items
+    dict(id='130x5x9.c128', shape=(130, 5, 9), cout=128, res=False, form=(4, 1), multi=True),           # 130 items on 128 workgroups
+]
+C64_SLOPES_FORMS = [(4, 1), (2, 2), (1, 4)]
+
 # thin9.hip (bf16 and fp16) has no plan query; its grid is min(items, plan CUs) and items >= N x ceil(W / 128), so
 # N x ceil(W / 128) > 256 forces several items per workgroup whatever chunk height the planner takes.  (N, H, W, Cout);
 # H = 5 is shorter than the 9-row window, H = 12 longer than the ring of 10 output rows.

@@ -2,6 +2,7 @@
 restatement of ``tests/compact_ref.py``, tiled inference, and the command line.
 
 Measured on an MI355X (printed by the tests; DESIGN.md section 3 quotes them): see each test's docstring."""
+import functools
 import os
 from argparse import Namespace
 
@@ -163,7 +164,143 @@ def test_prelu_channels_refusals_launch_nothing(dev):
     assert float(big.abs().max()) == 0.0
 
 
+# ------------------------------------------------------------------------------------ 1b. per-channel PReLU at its launch limits
+PC_FWD_BLOCKS, PC_BWD_BLOCKS, PC_ROWS = 8192, 1024, 64      # compact.hip: the forward's grid cap, the backward's, rows per workgroup
+# (M, C, Cs).  180001 x 48: Q = 12 quads per row, 2 160 012 quads on 8192 x 256 lanes -- the grid-stride loop is entered, its
+# column step is 8192 * 256 mod 12 = 8 and the last pass is partial; backward: 1024 workgroups of 176 rows, the last ones short or
+# empty.  140000 x 64: the Q = 16 twin whose column step is 0; 137 rows per workgroup.
+PRELU_LIMITS = [(180001, 48, 48), (140000, 64, 64)]
+# backward only: Q = 256 (one row per pass) with C < Cs pass-through channels and C = 512; the training step's own launch
+PRELU_BWD_ONLY = [(130, 512, 1024), (65536, 64, 64)]
+
+
+@functools.lru_cache(maxsize=None)
+def _prelu_limit_case(m, c, cs):
+    """Operands and torch's results on the CPU, once per shape: y and dx in fp32 (one multiply each: bit for bit), dslopes as the fp64
+    sum with the sum of the terms' magnitudes for its bound.  Channels [c, cs) pass through."""
+    g = torch.Generator().manual_seed(m + 7 * c + cs)
+    x = torch.randn(m, cs, generator=g)
+    x[torch.rand(m, cs, generator=g) < 0.1] = 0.0            # exact zeros and -0.0: x > 0 is false for both
+    x.view(-1)[3::1001] = -0.0
+    dy = torch.randn(m, cs, generator=g)
+    a = torch.rand(c, generator=g) * 2 - 0.5
+    a[:4] = torch.tensor([0.0, -0.7, 0.25, 1.5])
+    old = torch.randn(c, generator=g) * 3
+    xc, dyc = x[:, :c], dy[:, :c]
+    y, dx = x.clone(), dy.clone()
+    y[:, :c] = torch.where(xc > 0, xc, a * xc)
+    dx[:, :c] = torch.where(xc > 0, dyc, a * dyc)
+    terms = torch.where(xc > 0, torch.zeros((), dtype=torch.float64), xc.double() * dyc.double())
+    return dict(x=x, dy=dy, a=a, old=old, y=y, dx=dx, da64=terms.sum(0), mag=terms.abs().sum(0))
+
+
+@pytest.mark.parametrize('m,c,cs', PRELU_LIMITS)
+def test_prelu_channels_fwd_grid_stride_loop(dev, m, c, cs):
+    """``srx_prelu_channels_fwd`` with more quads than 8192 x 256 lanes: bit for bit ``torch.where(x > 0, x, a * x)``, out of place
+    and in place, nothing written outside y."""
+    from guarded import SENTINEL, Guarded
+    from torchsr_amd import _lib
+    q, lanes = cs // 4, PC_FWD_BLOCKS * 256
+    total = m * q
+    assert total > lanes and total % lanes != 0 and lanes % q == (8 if q == 12 else 0)
+    r = _prelu_limit_case(m, c, cs)
+    x, a, want = r['x'].to(dev), r['a'].to(dev), r['y'].to(dev)
+    y = Guarded(dev, (m, cs), margin=SENTINEL)
+    _lib.call('srx_prelu_channels_fwd', x.data_ptr(), a.data_ptr(), y.ptr(), m, c, cs, _stream())
+    assert torch.equal(_bits(y.t), _bits(want)) and y.margins_unchanged()
+    xi = Guarded(dev, (m, cs), src=x, margin=SENTINEL)
+    _lib.call('srx_prelu_channels_fwd', xi.ptr(), a.data_ptr(), xi.ptr(), m, c, cs, _stream())
+    assert torch.equal(_bits(xi.t), _bits(want)) and xi.margins_unchanged()
+    assert torch.equal(_bits(x.cpu()), _bits(r['x']))          # the input of the out-of-place call is untouched
+
+
+@pytest.mark.parametrize('m,c,cs', PRELU_LIMITS + PRELU_BWD_ONLY)
+def test_prelu_channels_bwd_at_its_launch_limits(dev, m, c, cs):
+    """``srx_prelu_channels_bwd`` on 1024 workgroups of more than 64 rows (the last ones short), at Q = 256 with pass-through
+    channels, and at the training step's own size: dx bit for bit; dslopes against the fp64 sum.  The kernel's partial sums are
+    fp64 (the products x * dy are exact there) and only the conversion of the total and the accumulating add round to fp32, so
+
+        |dslopes - ref64| <= 2^-24 |ref64| + M 2^-52 sum |x dy|     (+ 2^-24 |old + ref64| when accumulating)
+
+    -- derived from the arithmetic, not measured.  Two calls give the same bits; the workspace has exactly the queried size and
+    lies, like every output, between sentinel bands."""
+    from guarded import SENTINEL, Guarded
+    from torchsr_amd import _lib
+    L = _lib.lib()
+    nb = min(-(-m // PC_ROWS), PC_BWD_BLOCKS)
+    rows_per_block = -(-m // nb)
+    if (m, c, cs) in PRELU_LIMITS:
+        assert nb == PC_BWD_BLOCKS and rows_per_block > PC_ROWS and nb * rows_per_block > m
+    elif cs == 1024:
+        assert cs // 4 == 256 and c == 512 and c < cs and nb > 2
+    else:
+        assert nb == PC_BWD_BLOCKS and rows_per_block == PC_ROWS and nb * rows_per_block == m
+    r = _prelu_limit_case(m, c, cs)
+    x, dy, a = r['x'].to(dev), r['dy'].to(dev), r['a'].to(dev)
+    want_dx = r['dx'].to(dev)
+    nws = L.srx_prelu_channels_ws_floats(m, c)
+    assert nws == nb * c * 2
+    base = 2.0 ** -24 * r['da64'].abs() + m * 2.0 ** -52 * r['mag']
+    outs = []
+    for accumulate in (0, 0, 1):
+        ws = Guarded(dev, (nws,), margin=SENTINEL, margin_floats=256)
+        dx = Guarded(dev, (m, cs), margin=SENTINEL)
+        da = Guarded(dev, (c,), src=r['old'].to(dev) if accumulate else None, margin=SENTINEL, margin_floats=64)
+        _lib.call('srx_prelu_channels_bwd', dy.data_ptr(), x.data_ptr(), a.data_ptr(), dx.ptr(), da.ptr(), accumulate, m, c, cs,
+                  ws.ptr(), nws, _stream())
+        torch.cuda.synchronize()
+        assert ws.margins_unchanged() and dx.margins_unchanged() and da.margins_unchanged()
+        assert torch.equal(_bits(dx.t), _bits(want_dx)), accumulate
+        got = da.t.cpu().double()
+        assert torch.isfinite(got).all()
+        ref = r['da64'] + (r['old'].double() if accumulate else 0.0)
+        bound = base + (2.0 ** -24 * ref.abs() if accumulate else 0.0)
+        err = (got - ref).abs()
+        print(f'prelu_channels_bwd {(m, c, cs)} accumulate {accumulate}: {nb} workgroups of {rows_per_block} rows, worst |err| / bound '
+              f'{float((err / bound.clamp_min(1e-300)).max()):.3f}')
+        assert bool((err <= bound).all()), (accumulate, float((err / bound.clamp_min(1e-300)).max()))
+        outs.append(da.t.clone())
+    assert torch.equal(_bits(outs[0]), _bits(outs[1]))
+
+
 # ------------------------------------------------------------------------------------------------ 2. the tail kernel
+@pytest.mark.parametrize('w', [64, 65, 131])
+@pytest.mark.parametrize('s', [2, 3, 4])
+def test_shuffle_add_nearest_block_decode(dev, s, w):
+    """``srx_shuffle_add_nearest_fwd`` / ``_bwd`` on N = 3 images of h = 4 rows of one, two and three 64-pixel segments (the last
+    ragged): the block index is decoded into (segment, row, image) with all three above 1.  Scales 2, 3 and 4 from an fp32, a bf16
+    and an fp16 source with channel stride 64 and NaN behind the 3 s^2 channels; backward into the tight stride and into 64.  Bit
+    for bit ``pixel_shuffle + interpolate(nearest)`` / ``pixel_unshuffle``; channel 3 and the padding channels zero."""
+    from guarded import SENTINEL, Guarded
+    from torchsr_amd import _lib, functional as F
+    n, h, k = 3, 4, 3 * s * s
+    assert -(-w // 64) == {64: 1, 65: 2, 131: 3}[w]
+    g = torch.Generator().manual_seed(100 * s + w)
+    t = torch.randn(n, h, w, 64, generator=g)
+    x = torch.rand(n, 3, h, w, generator=g)
+    dy = torch.randn(n, 3, h * s, w * s, generator=g)
+    x4 = F.to_nhwc(x.to(dev), 4)
+    up = TF.interpolate(x, scale_factor=s, mode='nearest')
+    for code, cast in ((0, lambda v: v), (1, lambda v: v.bfloat16()), (2, lambda v: v.half())):
+        td = cast(t).to(dev)
+        td[..., k:] = float('nan')                      # garbage behind the channels: never read into the result
+        y4 = Guarded(dev, (n, h * s, w * s, 4), margin=SENTINEL)
+        _lib.call('srx_shuffle_add_nearest_fwd', td.data_ptr(), code, 64, x4.data_ptr(), y4.ptr(), n, h, w, s, _stream())
+        want = TF.pixel_shuffle(cast(t[..., :k]).float().permute(0, 3, 1, 2), s) + up
+        got = y4.t.cpu()
+        assert torch.equal(_bits(got[..., :3].permute(0, 3, 1, 2)), _bits(want)), code
+        assert float(got[..., 3].abs().max()) == 0.0 and y4.margins_unchanged(), code
+    dy4 = F.to_nhwc(dy.to(dev), 4)
+    want_dt = TF.pixel_unshuffle(dy, s).permute(0, 2, 3, 1).contiguous()
+    for cs_b in sorted({(k + 3) // 4 * 4, 64}):
+        dt = Guarded(dev, (n, h, w, cs_b), margin=SENTINEL)
+        _lib.call('srx_shuffle_add_nearest_bwd', dy4.data_ptr(), dt.ptr(), cs_b, n, h, w, s, _stream())
+        got = dt.t.cpu()
+        assert torch.equal(_bits(got[..., :k]), _bits(want_dt)), cs_b
+        assert cs_b == k or float(got[..., k:].abs().max()) == 0.0
+        assert dt.margins_unchanged(), cs_b
+
+
 @pytest.fixture(scope='module')
 def tail_refs():
     out = {}

@@ -77,17 +77,17 @@ SENTINEL = 7.0
 
 
 class Layer:
-    """A 3x3 / stride 2 / pad 1 layer with packed weights, dy, the activation output x (mask input, in dx's layout) and the
-    fp64 data gradient of bf16-rounded (precision 1) or plain fp32 operands."""
+    """A k x k (3x3; 4x4: test_k4s2_forms_gpu.py) / stride 2 / pad 1 layer with packed weights, dy, the activation output x (mask
+    input, in dx's layout) and the fp64 data gradient of bf16-rounded (precision 1) or plain fp32 operands."""
 
-    def __init__(self, n, h, w, cin, cout, cin_s, prec, dev):
+    def __init__(self, n, h, w, cin, cout, cin_s, prec, dev, k=3):
         from torchsr_amd import _lib
         L = _lib.lib()
         self.n, self.h, self.w, self.cin, self.cout, self.cin_s, self.prec = n, h, w, cin, cout, cin_s, prec
-        self.d = _lib.Conv2dDesc(n, h, w, cin, cin_s, cout, cout, 3, 3, 2, 1, 0, 0, 0.0, 0, prec)
-        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        self.d = _lib.Conv2dDesc(n, h, w, cin, cin_s, cout, cout, k, k, 2, 1, 0, 0, 0.0, 0, prec)
+        ho, wo = (h + 2 - k) // 2 + 1, (w + 2 - k) // 2 + 1
         g = torch.Generator().manual_seed(n * 1000 + h * 37 + cin + 3 * cout)
-        wt = torch.randn(cout, cin, 3, 3, generator=g) * 0.05
+        wt = torch.randn(cout, cin, k, k, generator=g) * 0.05
         dy = torch.randn(n, ho, wo, cout, generator=g)
         self.x = torch.randn(n, h, w, cin_s, generator=g).to(dev)
         self.dy = dy.to(dev)
@@ -134,8 +134,8 @@ class Layer:
 
 
 @functools.lru_cache(maxsize=None)
-def _layer(n, h, w, cin, cout, cin_s, prec):
-    return Layer(n, h, w, cin, cout, cin_s, prec, torch.device('cuda:0'))
+def _layer(n, h, w, cin, cout, cin_s, prec, k=3):
+    return Layer(n, h, w, cin, cout, cin_s, prec, torch.device('cuda:0'), k)
 
 
 # Ragged last row tile for every BM (M = 585, 198, 126, 30), padded output columns (Cin 96 -> 128 columns, 192 -> 192),

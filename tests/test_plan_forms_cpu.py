@@ -91,6 +91,32 @@ def test_c64_cases_give_a_workgroup_several_items(lib, case):
         assert grid % chunks != 0 and (grid // chunks) % strips != 0, (chunks, strips, grid)
 
 
+@pytest.mark.parametrize('case', PF.C64_SLOPES, ids=PF.by_id(PF.C64_SLOPES))
+def test_c64_slopes_cases_reach_their_tile_form_and_item_count(lib, case):
+    """The per-channel-slope cases: the tile form follows the row length, and the multi-item ones give a workgroup several items
+    whatever chunk height the planner takes (N x strips > grid)."""
+    n, h, w = case['shape']
+    rows, chunks, strips = _c64_plan(lib, n, h, w, case['cout'])
+    grid = lib.srx_plan_cus() // (case['cout'] // 64)
+    form = (4, 1) if w <= 32 else ((2, 2) if w <= 64 else (1, 4))
+    assert form == case['form'] and strips == -(-w // (32 * form[1])), (form, strips)
+    if case['multi']:
+        assert n * chunks * strips > grid and n * strips > grid, (rows, chunks, strips, grid)
+    else:
+        assert n * chunks * strips <= grid, (rows, chunks, strips, grid)
+
+
+def test_c64_slopes_cases_cover_every_form():
+    for multi in (False, True):
+        forms = {c['form'] for c in PF.C64_SLOPES if c['multi'] == multi}
+        assert forms >= ({(2, 2), (1, 4)} if not multi else set(PF.C64_SLOPES_FORMS)), (multi, forms)
+    assert {c['form'] for c in PF.C64_SLOPES} == set(PF.C64_SLOPES_FORMS)
+    two_groups = [c for c in PF.C64_SLOPES if c['cout'] == 128]
+    assert {c['multi'] for c in two_groups} == {False, True}
+    assert {(c['res'], c['multi']) for c in PF.C64_SLOPES} == {(r, m) for r in (False, True) for m in (False, True)}
+    assert any(c['shape'][1] % 2 for c in PF.C64_SLOPES if c['form'] == (2, 2))   # odd rows under two rows per wave
+
+
 @pytest.mark.parametrize('n,h,w,cout', PF.THIN9_MULTI_ITEM)
 def test_thin9_cases_give_a_workgroup_several_items(lib, n, h, w, cout):
     assert n * -(-w // PF.THIN9_STRIP) > lib.srx_plan_cus()

@@ -440,6 +440,15 @@ def _c64_items(n, h, w, cout):
     return list(out), n * out[1] * out[2], max(1, L.srx_plan_cus() // (cout // 64))
 
 
+def _c64_slopes(cout, g):
+    """One slope per output channel, random in (-0.5, 1.5) with 0, -0.7, 0.25 and 1.5 among them; no two alike, so that a swapped
+    channel (half, group) shows."""
+    a = torch.rand(cout, generator=g) * 2 - 0.5
+    a[:4] = torch.tensor([0.0, -0.7, 0.25, 1.5])
+    assert a.unique().numel() == cout and float(a.min()) >= -0.7 and float(a.max()) <= 1.5
+    return a
+
+
 def _c64_check(dev, f16, n, h, w, cout, shuffle, res):
     """srx_conv3x3_c64_{bf16,f16}_fwd against fp64 of the same (rounded) operands, at the bounds of test_ops_gpu.py::
     test_bf16_native_conv3x3_c64 / test_fp16_inference_gpu.py::test_fp16_conv3x3_c64: one rounding of the fp32 sum -- half a bf16
@@ -489,6 +498,84 @@ def test_c64_workgroups_walk_several_items(dev, case, f16):
     plan, items, grid = _c64_items(n, h, w, case['cout'])
     assert items > grid and plan[1] >= case['min_chunks'] and plan[2] >= case['min_strips'], (plan, items, grid)
     _c64_check(dev, f16, n, h, w, case['cout'], case['shuffle'], case['res'])
+
+
+_SLOPES_SEEN = set()   # the c64_*_slopes_kernel instantiations this module's launches recorded
+
+
+def _c64_slopes_check(dev, f16, n, h, w, cout, res, form):
+    """srx_conv3x3_c64_{bf16,f16}_fwd_slopes (c64_{bf16,f16}_slopes_kernel<RW, CW>: PC = true, one PReLU slope per output channel)
+    against fp64 of the same (rounded) operands at _c64_check's bounds -- half a bf16 ulp x 1.001 + 2e-6 of the range, or half an
+    fp16 ulp + 2e-5 of it, and more than 99.5 % of the values the rounding of the right one.  With all slopes equal to 0.25, -0.5
+    and 1.0 -- the scalar kernel's three activation forms -- the result is the scalar entry point's, bit for bit."""
+    lib, L = _L()
+    s = _stream()
+    dt = torch.float16 if f16 else torch.bfloat16
+    tag = 'f16' if f16 else 'bf16'
+    g = torch.Generator().manual_seed(2000 * h + w + cout + n + (7 if f16 else 0))
+    x = (torch.rand(n, 64, h, w, generator=g) - 0.5).to(dt)
+    wt = torch.randn(cout, 64, 3, 3, generator=g) * (2.0 / 576) ** 0.5
+    b = torch.randn(cout, generator=g) * 0.1
+    a = _c64_slopes(cout, g)
+    skip = (torch.rand(n, cout, h, w, generator=g) - 0.5).to(dt) if res else None
+    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    wd, bd = wt.to(dev), b.to(dev)
+    pk = torch.empty(getattr(L, f'srx_conv3x3_c64_{tag}_packed_bytes')(cout), dtype=torch.uint8, device=dev)
+    lib.call(f'srx_conv3x3_c64_{tag}_pack', _p(wd), _p(bd), None, cout, 0, _p(pk), s)
+    sd = None if skip is None else skip.permute(0, 2, 3, 1).contiguous().to(dev)
+
+    def run(sl):
+        y = torch.full((n, h, w, cout), NAN, dtype=dt, device=dev)
+        lib.call(f'srx_conv3x3_c64_{tag}_fwd_slopes', n, h, w, cout, 0, _p(xd), _p(pk), _p(sl), _p(sd), _p(y), cout, s)
+        return y
+
+    ad = a.to(dev)
+    y, names = _run(lambda: run(ad))
+    rw, cw = form
+    assert names == [f'c64_{tag}_slopes_kernel<{rw}, {cw}> MxNxK={n * h * w}x{cout}x576'], names
+    _SLOPES_SEEN.add(names[0].split(' MxNxK=')[0])
+    z = TF.conv2d(x.double(), wt.to(dt).double(), b.double(), 1, 1)
+    z = torch.where(z > 0, z, z * a.double().view(1, -1, 1, 1))
+    if skip is not None:
+        z = z + skip.double()
+    got = y.permute(0, 3, 1, 2).float().cpu().double()
+    assert torch.isfinite(got).all()
+    err = (got - z).abs()
+    bound = z.abs() * U16 + 2e-5 * z.abs().max() if f16 else z.abs() * (2.0 ** -8 * 1.001) + 2e-6 * z.abs().max()
+    same = (z.float().to(dt).double() == got).double().mean().item()   # ... and it IS the rounding of the right value
+    print(f'  c64 slopes {tag} {(n, h, w, cout)} <{rw}, {cw}>: max err / bound {float((err / bound).max()):.3f}, same {same:.5f}')
+    assert (err <= bound).all(), ((err - bound).max().item(), err.max().item())
+    assert same > 0.995, same
+    for v in (0.25, -0.5, 1.0):
+        ys = torch.full((n, h, w, cout), NAN, dtype=dt, device=dev)
+        lib.call(f'srx_conv3x3_c64_{tag}_fwd', n, h, w, cout, 0, _p(xd), _p(pk), v, _p(sd), _p(ys), cout, s)
+        yv = run(torch.full((cout,), v, device=dev))
+        torch.cuda.synchronize()
+        assert not torch.isnan(ys).any() and torch.equal(yv.view(torch.int16), ys.view(torch.int16)), v
+
+
+@pytest.mark.parametrize('f16', [False, True], ids=['bf16', 'fp16'])
+@pytest.mark.parametrize('case', PF.C64_SLOPES, ids=PF.by_id(PF.C64_SLOPES))
+def test_c64_per_channel_slopes_in_every_tile_form(dev, case, f16):
+    """The PC = true instantiations <4, 1>, <2, 2> and <1, 4> in both types: frames wider than 64 pixels, odd rows, ragged strips,
+    two channel groups (the slopes 64..127 must reach group 1), and workgroups that walk several items with the slopes kept in
+    registers across them."""
+    n, h, w = case['shape']
+    plan, items, grid = _c64_items(n, h, w, case['cout'])
+    assert (items > grid) == case['multi'], (plan, items, grid)
+    _c64_slopes_check(dev, f16, n, h, w, case['cout'], case['res'], case['form'])
+
+
+def test_zz_every_slopes_kernel_instantiation_ran(dev):
+    """All six c64_{bf16,f16}_slopes_kernel<RW, CW> names were recorded (cases this process has not run yet run here)."""
+    want = {f'c64_{tag}_slopes_kernel<{rw}, {cw}>' for tag in ('bf16', 'f16') for rw, cw in PF.C64_SLOPES_FORMS}
+    for f16 in (False, True):
+        for form in PF.C64_SLOPES_FORMS:
+            if f'c64_{"f16" if f16 else "bf16"}_slopes_kernel<{form[0]}, {form[1]}>' not in _SLOPES_SEEN:
+                case = next(c for c in sorted(PF.C64_SLOPES, key=lambda c: c['multi']) if c['form'] == form)
+                _c64_slopes_check(dev, f16, *case['shape'], case['cout'], case['res'], form)
+    print('  c64 slopes kernels recorded:', sorted(_SLOPES_SEEN))
+    assert _SLOPES_SEEN == want and len(want) == 6
 
 
 def _thin9_check(dev, f16, n, h, w, cout):

@@ -19,6 +19,9 @@ or, where that is larger, the floor 8 * 2^-23 * max |ref64| (in brackets):
   spectral norm (512, 4096) train:  u 4.8e-08 [1.4e-07]  v 3.9e-08  sigma 5.6e-08  W_sn 5.6e-09  dW 3.3e-07 [3.2e-06]
   spectral norm, eval:              u, v 0 (unchanged)  sigma 1.0e-09 .. 1.1e-08  W_sn 6.0e-08 .. 3.3e-06  dW 6.5e-07 .. 3.3e-03
                                     (random u and v: sigma ~ 0.02, so W_sn and dW are large; dW floors 8.0e-06 .. 5.5e-03)
+  spectral norm, ragged rows:       (100, 44), (520, 68), (1, 576), (3, 8), (256, 4608), (128, 1024) train: u, v 0 .. 1.5e-07
+                                    sigma 6.2e-08 .. 3.9e-07  W_sn 7.8e-09 .. 6.3e-08  dW 1.1e-07 .. 5.6e-07; eval: sigma 5.9e-10 .. 2.9e-08
+                                    W_sn 1.5e-07 .. 9.2e-05  dW 3.6e-06 .. 4.5e-02 (sigma down to 0.006: W_sn up to 22, dW up to 4.6e+03)
   bilinear x2:                      0 .. 2.4e-07: the floor decides
   conv 4x4 s2 64 -> 128:            y 2.1e-06  dx 1.7e-06  dw 3.6e-05   (the bf16 recipe's reference: 9.8e-07, 9.4e-07, 1.4e-05)
   conv 4x4 s2 256 -> 512:           y 1.7e-06  dx 2.1e-06  dw 7.1e-06   (1.0e-06, 1.0e-06, 3.3e-06)
@@ -92,10 +95,18 @@ def _sn_reference(w, u, v, g, train: bool, calls: int = 1):
     return out
 
 
+# (rows, cols).  The first three fill whole 16-row chunks of pass 1 (sn_wtu_kernel).  Then: 100 rows -- 7 chunks of 15, the last of
+# 10; 520 rows -- 32 chunks planned, 17 rows each, so 31 are launched and the workspace keeps a 32nd partial row nobody writes or
+# reads; 1 and 3 rows -- fewer than the 4 the uv_keep offset roundup(rows, 4) rounds to; and the network's own 256 x 4608 (conv3's
+# 512 x 4096 is above) and 128 x 1024.
+SN_CHUNK_SHAPES = [(8, 36), (64, 576), (512, 4096)]
+SN_RAGGED_SHAPES = [(100, 44), (520, 68), (1, 576), (3, 8), (256, 4608), (128, 1024)]
+
+
 @pytest.fixture(scope='module')
 def sn_cases():
     cases = {}
-    for rows, cols in ((8, 36), (64, 576), (512, 4096)):
+    for rows, cols in SN_CHUNK_SHAPES + SN_RAGGED_SHAPES:
         gen = torch.Generator().manual_seed(rows + cols)
         w = torch.randn(rows, cols, generator=gen) * (2.0 / cols) ** 0.5
         u = TF.normalize(torch.randn(rows, generator=gen), dim=0)
@@ -130,7 +141,7 @@ def _sn_sigma(dev, w, u, v, train: bool):
     return sigma
 
 
-@pytest.mark.parametrize('shape', [(8, 36), (64, 576), (512, 4096)])
+@pytest.mark.parametrize('shape', SN_CHUNK_SHAPES + SN_RAGGED_SHAPES)
 @pytest.mark.parametrize('train', [True, False])
 def test_spectral_norm_forward_and_backward_against_fp64(dev, sn_cases, shape, train):
     w, u, v, g = sn_cases[shape]
@@ -172,6 +183,57 @@ def test_spectral_norm_sigma_output_and_accumulating_backward(dev, sn_cases):
                   dw.data_ptr(), acc, 64, 576, ws.data_ptr(), nws, s)
     _close('sn dW (kernel)', dw0, ref[torch.float32][1], ref[torch.float64][1])
     assert torch.equal(dw1, dw0 + base)
+
+
+@pytest.mark.parametrize('shape', SN_CHUNK_SHAPES + SN_RAGGED_SHAPES)
+@pytest.mark.parametrize('train', [True, False])
+def test_spectral_norm_entry_points_stay_inside_their_buffers(dev, sn_cases, shape, train):
+    """``srx_spectral_norm_fwd`` / ``_bwd`` through the C ABI with a workspace of exactly ``srx_spectral_norm_ws_floats`` floats, W_sn,
+    uv_keep (``roundup(rows, 4) + cols`` floats) and dW each between two sentinel bands: a write past the chunk partials, past s,
+    past v_keep or past the last row fails here.  u, v, sigma, W_sn and dW (through uv_keep) by the module's rule, unchanged."""
+    from guarded import SENTINEL, Guarded
+    from torchsr_amd import _lib
+    rows, cols = shape
+    w, u, v, g = sn_cases[shape]
+    ref = _sn_reference(w, u, v, g, train)
+    (steps64, dw64), (steps32, dw32) = ref[torch.float64], ref[torch.float32]
+    (u64, v64, s64, wsn64), (u32, v32, s32, wsn32) = steps64[0], steps32[0]
+    chunks = min(-(-rows // 16), 32)
+    r4 = (rows + 3) // 4 * 4
+    nws = _lib.lib().srx_spectral_norm_ws_floats(rows, cols)
+    assert nws == max(chunks * cols + r4, 256), (nws, chunks)
+    if shape == (520, 68):      # 17 rows per chunk: 31 chunks are launched, the 32nd partial row stays as it was
+        assert -(-rows // -(-rows // chunks)) == chunks - 1
+    wd, gd = w.to(dev), g.to(dev)
+    s = torch.cuda.current_stream().cuda_stream
+    band = dict(margin=SENTINEL, margin_floats=256)
+    ud, vd = Guarded(dev, (rows,), src=u.to(dev), **band), Guarded(dev, (cols,), src=v.to(dev), **band)
+    out, keep, sigma = Guarded(dev, (rows, cols), **band), Guarded(dev, (r4 + cols,), **band), Guarded(dev, (4,), **band)
+    ws = Guarded(dev, (nws,), **band)
+    _lib.call('srx_spectral_norm_fwd', wd.data_ptr(), ud.ptr(), vd.ptr(), out.ptr(), sigma.ptr(), keep.ptr(), rows, cols, int(train),
+              ws.ptr(), nws, s)
+    torch.cuda.synchronize()
+    for name, buf in (('u', ud), ('v', vd), ('W_sn', out), ('uv_keep', keep), ('sigma', sigma), ('workspace', ws)):
+        assert buf.margins_unchanged(), name
+    assert torch.isnan(sigma.t[1:]).all()
+    tag = f'sn raw {shape} train={train}'
+    _close(f'{tag} u', ud.t, u32, u64)
+    _close(f'{tag} v', vd.t, v32, v64)
+    _close(f'{tag} sigma', sigma.t[:1], s32, s64)
+    _close(f'{tag} W_sn', out.t, wsn32, wsn64)
+    assert torch.equal(keep.t[:rows], ud.t) and torch.equal(keep.t[r4:], vd.t)
+    if not train:
+        assert torch.equal(ud.t.cpu(), u) and torch.equal(vd.t.cpu(), v)
+    dws = []
+    for _ in range(2):
+        ws2, dw = Guarded(dev, (nws,), **band), Guarded(dev, (rows, cols), **band)
+        _lib.call('srx_spectral_norm_bwd', gd.data_ptr(), wd.data_ptr(), keep.ptr(), keep.t.data_ptr() + 4 * r4, sigma.ptr(), dw.ptr(), 0,
+                  rows, cols, ws2.ptr(), nws, s)
+        torch.cuda.synchronize()
+        assert ws2.margins_unchanged() and dw.margins_unchanged()
+        dws.append(dw.t.clone())
+    _close(f'{tag} dW', dws[0], dw32, dw64)
+    assert torch.equal(dws[0], dws[1])
 
 
 def test_three_chained_training_forwards_track_torchs_three(dev, sn_cases):

@@ -1,6 +1,7 @@
 """Every launch form of the weight gradient (wgrad.hip): the seven slab kernels -- wgrad_kernel<0>, wgrad_dma_kernel<0, 0> / <1, 0> /
 <1, 1>, wgrad_kernel<1>, wgrad_rows_bf16_kernel<32> / <16> -- and the two reduce kernels, forced through srx_wgrad_force (row splits)
-and srx_wgrad_force_kernels (which kernel) and held to the form by srx_wgrad_plan.
+and srx_wgrad_force_kernels (which kernel) and held to the form by srx_wgrad_plan.  Rows K1..K3: the 4 x 4 / stride 2 / pad 1 layers of
+the U-Net critic (test_k4s2_forms_cpu.py ties the training step's own plans for them to these rows).
 
 Data only.  test_wgrad_forms_cpu.py holds every case to the form it is here for through the host-only planner (a planner change that
 makes a case vacuous fails there, without a GPU); test_wgrad_forms_gpu.py runs the launches against fp64.
@@ -114,10 +115,24 @@ for _ns in (1, 6):
 # R4: per-output scales on the image-row kernel, R1's geometry; the model cuts 8 splits of two rows (the last: one)
 _add('R4.scaled.3x5x16', _geo(3, 5, 16, 32, 64), _R16, (8, 32), model=True, call='scaled', nprob=2, scales=(0.04, 1.0), split_norows=(2, 128))
 
+# ------------------------------------------------------------------------------------------- 4 x 4 / stride 2 / pad 1 (even kernel)
+# The U-Net critic's conv1..conv3: every output pixel gathers a 4 x 4 patch that starts one row and column outside the image at
+# the top / left border and ends one outside at the bottom / right.  WIDE (64 | Cin), F32 (DMA staging off) and BF16 each.
+_K4 = dict(k=4, stride=2, pad=1)
+# K1: 64 -> 128 on 3 x 26 x 30: 585 output pixels in rows of 15 -- one split, and 2 x 320, 4 x 160, 5 x 128 pixels, every cut
+# in the middle of an output row (320 = 21 x 15 + 5, 160 = 10 x 15 + 10, 128 = 8 x 15 + 8); two 64-column tiles
+for _ns, _rps in ((1, 608), (2, 320), (4, 160), (5, 128)):
+    _add(f'K1.3x26x30.k4s2.s{_ns}', _geo(3, 26, 30, 64, 128, **_K4), _GEN_WIDE, (_ns, _rps), nsplit=_ns)
+# K2: 128 -> 256 of a 136-strided buffer, 198 pixels in 2 splits (the second: 70), accumulating into existing gradients
+_add('K2.2x22x18.k4s2.acc', _geo(2, 22, 18, 128, 256, cin_s=136, **_K4), _GEN_WIDE, (2, 128), nsplit=2, accumulate=1)
+# K3: 96 input channels (not whole 64-channel k-tiles per tap: wgrad_dma_kernel<0, 0>), 126 pixels: one split shorter than its chunks
+_add('K3.2x14x18.k4s2.96', _geo(2, 14, 18, 96, 256, cin_s=100, **_K4), _GEN, (1, 128), nsplit=1)
+
 # ------------------------------------------------------------------------------------------------------------------- refusals
 # (geometry, precision, forced splits): splits the rows cannot take -- 15 image rows into 10 (8 + 7 are 2 splits), 15 into 16; the
-# generic kernels' own rule: 286 pixels into 4 splits of fewer than 128
-REFUSED_SPLITS = [(_geo(3, 5, 16, 32, 64), 1, 10), (_geo(3, 5, 16, 32, 64), 1, 16), (_geo(2, 11, 13, 24, 40), 0, 4)]
+# generic kernels' own rule: 286 pixels into 4 splits of fewer than 128, and the 4 x 4 stride-2 layer's 198 into 4
+REFUSED_SPLITS = [(_geo(3, 5, 16, 32, 64), 1, 10), (_geo(3, 5, 16, 32, 64), 1, 16), (_geo(2, 11, 13, 24, 40), 0, 4),
+                  (_geo(2, 22, 18, 128, 256, cin_s=136, **_K4), 0, 4)]
 BAD_FORCE_KERNELS = [(2, -1, -1), (-1, -2, -1), (-1, -1, 2), (0, 0, 5)]
 # srx_wgrad_plan(d, nprob, per_out, .): (nprob, per_out)
 BAD_PLAN_ARGS = [(0, 1), (WG_MAXP + 1, 1), (4, 3), (2, 0)]
