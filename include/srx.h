@@ -637,6 +637,25 @@ int srx_add_poisson_noise(const float* in_nchw, float* out_nchw, const float* sc
  * refused), N <= 65535; quantize != 0 rounds the result to 8 bits. */
 int srx_jpeg_sim(const float* in_nchw, float* out_nchw, const int32_t* quality, int N, int H, int W, int quantize,
                  void* stream);
+/* srx_jpeg_sim with 4:2:0 chroma subsampling per sample ('Chroma subsampling').  chroma420: int32 [N].
+ * chroma420[n] == 0: sample n gets srx_jpeg_sim's arithmetic and its bits.  Any other value: Y is coded as there; the integer
+ * Cb and Cr are averaged 2 x 2 as libjpeg's h2v2_downsample does -- (a + b + c + d + bias) >> 2, bias 1, 2, 1, 2, ... along
+ * each row of the H/2 x W/2 plane -- the plane is edge-replicated to whole 8 x 8 blocks (a partial 16 x 16 MCU), coded with the
+ * chrominance table, and brought back by libjpeg's h2v2_fancy_upsample in floating point: with c the decoded sample over a
+ * pixel, v and h its vertical and horizontal neighbours on the pixel's side and d the diagonal one, each the plane's edge
+ * sample where it would lie outside the H/2 x W/2 plane, fma(3, fma(3, c, v), fma(3, h, d)) / 16.  A quality outside 1..100
+ * copies the sample whatever its flag.
+ * workspace: DEVICE, at least srx_jpeg_sim2_workspace(N, H, W) bytes, the decoded chroma planes between the two launches;
+ * every word that is read is written first, so its contents before the call do not matter.  The library allocates nothing.
+ * quot_out: nullable; DEVICE float [N][3][H W], coefficient / step before the rounding, block after block in raster order, 64
+ * values [vertical][horizontal frequency] each: a 4:4:4 sample's Y, Cb and Cr blocks from [n][0], [n][1] and [n][2]; a 4:2:0
+ * sample's Y blocks from [n][0] and the ceil(H / 16) x ceil(W / 16) blocks of Cb from [n][1] and of Cr from [n][2], the rest
+ * of those two planes untouched, as is all of a copied sample's.
+ * A chroma and a luma launch.  Refused before either: a null pointer other than quot_out and stream, N outside 1..65535, H or W
+ * not a positive multiple of 8, H / 8 > 65535, H W >= 2^31, a workspace that is too small. */
+size_t srx_jpeg_sim2_workspace(int N, int H, int W);
+int srx_jpeg_sim2(const float* in_nchw, float* out_nchw, const int32_t* quality, const int32_t* chroma420, int N, int H, int W,
+                  int quantize, void* workspace, size_t workspace_bytes, float* quot_out, void* stream);
 
 /* ------------------------------------------------- sharpened targets (usm.hip) */
 /* Real-ESRGAN's USMSharp on float planes in [0, 1] ('Sharpened targets').  G is the separable correlation with

@@ -243,6 +243,8 @@ _SIGS = {
     'srx_add_gaussian_noise': (_I, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _I, _I, _P]),
     'srx_add_poisson_noise': (_I, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _I, _I, _I, _I, _P]),
     'srx_jpeg_sim': (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    'srx_jpeg_sim2_workspace': (_Z, [_I, _I, _I]),
+    'srx_jpeg_sim2': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P, _P]),
     'srx_usm_sharpen': (_I, [_P, _P, _P, _P, _P, _I, _L, _I, _I, _F, _F, _P]),
     'srx_pool_exchange': (_I, [_P, _P, _L, _P, _P, _L, _P, _I, _I, _I, _P]),
     'srx_act_bwd_from_out': (_I, [_P, _P, _P, _L, _I, _F, _P]),

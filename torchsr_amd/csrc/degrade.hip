@@ -1,6 +1,7 @@
 // Blind degradation of the training data on the device ('Blind degradation'): the first-order model of
 // BSRGAN / Real-ESRGAN -- blur, resize, sensor noise, JPEG -- around augment.hip's srx_bicubic_down, and the table-driven
-// filter of its second-order model ('Second-order degradation'), and its Poisson noise ('Poisson noise').  Kernels over a
+// filter of its second-order model ('Second-order degradation'), its Poisson noise ('Poisson noise') and its 4:2:0 JPEG
+// ('Chroma subsampling').  Kernels over a
 // batch of float NCHW images in [0, 1]; every per-sample parameter is read on the device, so each kernel is safe for any
 // value it finds there (a kernel size outside the legal set is clamped into it, a quality outside 1..100 passes through).
 #include "srx_common.h"
@@ -419,6 +420,161 @@ __global__ __launch_bounds__(64) void jpeg_sim_kernel(const float* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ JPEG, 4:2:0 per sample
+// srx_jpeg_sim2 ('Chroma subsampling').  The pieces below restate jpeg_sim_kernel's arithmetic expression for
+// expression, so that a sample whose flag is 0 leaves srx_jpeg_sim2 with the bits srx_jpeg_sim gives it.
+__device__ __forceinline__ int jpeg_level(float f) { return (int)fminf(fmaxf(rintf(f * 255.f), 0.f), 255.f); }
+
+// The codec of P planes of one 8 x 8 block held one sample per lane in v[]: DCT, quantise, dequantise, inverse DCT, in place.
+// Plane p takes the chrominance table when first_table + p > 0.  quot (nullable): coefficient / step before the rounding goes
+// to quot[p * quot_stride + lane].  Every lane of the workgroup's one wave must arrive (the passes meet at barriers).
+template <int P>
+__device__ __forceinline__ void jpeg_codec(float (*buf)[64], float (&v)[P], int lane, int scale, int first_table,
+                                           float* __restrict__ quot, size_t quot_stride) {
+  const int a = lane >> 3, b = lane & 7;
+#pragma unroll
+  for (int p = 0; p < P; ++p) buf[p][lane] = v[p];
+  __syncthreads();
+  // forward, columns: T[a][b] = sum_m D[a][m] X[m][b]
+  float t[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) t[p] = 0.f;
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int p = 0; p < P; ++p) t[p] = fmaf(kDct[a * 8 + m], buf[p][m * 8 + b], t[p]);
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < P; ++p) buf[p][lane] = t[p];
+  __syncthreads();
+  // forward, rows: F[a][b] = sum_m T[a][m] D[b][m]; then quantise and dequantise
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    float f = 0.f;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) f = fmaf(buf[p][a * 8 + m], kDct[b * 8 + m], f);
+    const int step = min(max((kJpegBase[(first_table + p) ? 1 : 0][lane] * scale + 50) / 100, 1), 255);
+    const float quotient = f / (float)step;
+    if (quot) quot[p * quot_stride + lane] = quotient;
+    t[p] = rintf(quotient) * (float)step;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < P; ++p) buf[p][lane] = t[p];
+  __syncthreads();
+  // inverse, columns: U[a][b] = sum_k D[k][a] F[k][b]
+#pragma unroll
+  for (int p = 0; p < P; ++p) t[p] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+#pragma unroll
+    for (int p = 0; p < P; ++p) t[p] = fmaf(kDct[k * 8 + a], buf[p][k * 8 + b], t[p]);
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < P; ++p) buf[p][lane] = t[p];
+  __syncthreads();
+  // inverse, rows: X[a][b] = sum_k U[a][k] D[k][b]; the decoded samples stay unrounded
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    float x = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x = fmaf(buf[p][a * 8 + k], kDct[k * 8 + b], x);
+    v[p] = x;
+  }
+}
+
+// The padded chroma planes of srx_jpeg_sim2's workspace: float [N][2][8 CHB][8 CWB], CHB = ceil(H / 16), CWB = ceil(W / 16)
+__host__ __device__ __forceinline__ int jpeg420_blocks(int extent) { return (extent + 15) / 16; }
+
+// The chroma launch: one wave per 8 x 8 block of the padded H/2 x W/2 chroma planes, lane = sample.  A lane gathers the 2 x 2
+// pixels under its sample -- under the plane's edge sample where the block reaches past the plane: the replication that
+// pads a partial 16 x 16 MCU -- averages their integer Cb and Cr as libjpeg's h2v2_downsample does, and writes the decoded
+// block to ws.  Samples that are not 4:2:0 (flag 0, or a quality outside 1..100) are left to the luma launch.
+// grid (CWB, CHB, N), 64 threads.
+__global__ __launch_bounds__(64) void jpeg420_chroma_kernel(const float* __restrict__ in, const int* __restrict__ quality,
+                                                            const int* __restrict__ chroma420, float* __restrict__ ws,
+                                                            float* __restrict__ quot_out, int H, int W) {
+  __shared__ float buf[2][64];
+  const int n = blockIdx.z, lane = threadIdx.x, a = lane >> 3, b = lane & 7;
+  const int q = quality[n];
+  if (q < 1 || q > 100 || chroma420[n] == 0) return;  // the whole wave
+  const size_t HW = (size_t)H * W;
+  const int cy = min((int)blockIdx.y * 8 + a, H / 2 - 1), cx = min((int)blockIdx.x * 8 + b, W / 2 - 1);
+  const float* src = in + (size_t)n * 3 * HW + (size_t)(2 * cy) * W + 2 * cx;
+  int cb = 0, cr = 0;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int R = jpeg_level(src[i * W + j]), G = jpeg_level(src[HW + i * W + j]), B = jpeg_level(src[2 * HW + i * W + j]);
+      cb += (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
+      cr += (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
+    }
+  const int bias = 1 + (cx & 1);  // 1, 2, 1, 2, ... along a row
+  float v[2] = {(float)(((cb + bias) >> 2) - 128), (float)(((cr + bias) >> 2) - 128)};
+  const int scale = q < 50 ? 5000 / q : 200 - 2 * q;
+  const int cwb = gridDim.x, chb = gridDim.y;
+  float* quot = quot_out ? quot_out + (size_t)n * 3 * HW + HW + (size_t)(blockIdx.y * cwb + blockIdx.x) * 64 : nullptr;
+  jpeg_codec<2>(buf, v, lane, scale, 1, quot, HW);
+  const size_t plane = (size_t)chb * cwb * 64;
+  float* dst = ws + (size_t)n * 2 * plane + (size_t)(blockIdx.y * 8 + a) * (cwb * 8) + blockIdx.x * 8 + b;
+  dst[0] = v[0], dst[plane] = v[1];
+}
+
+// The luma launch: one wave per 8 x 8 block of the image, lane = pixel.  A 4:4:4 sample takes jpeg_sim_kernel's path; a 4:2:0
+// sample codes Y alone and takes its chroma from ws through libjpeg's h2v2_fancy_upsample in floating point: with c the
+// sample over the pixel, v and h its vertical and horizontal neighbours on the pixel's side and d the diagonal one (the
+// plane's edge sample beyond the H/2 x W/2 plane), fma(3, fma(3, c, v), fma(3, h, d)) / 16.  grid (W / 8, H / 8, N), 64 threads.
+__global__ __launch_bounds__(64) void jpeg420_luma_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                          const int* __restrict__ quality, const int* __restrict__ chroma420,
+                                                          const float* __restrict__ ws, float* __restrict__ quot_out, int H,
+                                                          int W, int quantize) {
+  __shared__ float buf[3][64];
+  const int n = blockIdx.z, lane = threadIdx.x, a = lane >> 3, b = lane & 7;
+  const size_t HW = (size_t)H * W;
+  const int y = blockIdx.y * 8 + a, x = blockIdx.x * 8 + b;
+  const size_t at = (size_t)n * 3 * HW + (size_t)y * W + x;
+  const float fr = in[at], fg = in[at + HW], fb = in[at + 2 * HW];
+  const int q = quality[n];
+  if (q < 1 || q > 100) {  // not a JPEG quality: the sample passes through, bit for bit (the whole wave takes this branch)
+    out[at] = fr, out[at + HW] = fg, out[at + 2 * HW] = fb;
+    return;
+  }
+  const int R = jpeg_level(fr), G = jpeg_level(fg), B = jpeg_level(fb);
+  const int scale = q < 50 ? 5000 / q : 200 - 2 * q;  // libjpeg's jpeg_quality_scaling
+  float* quot = quot_out ? quot_out + (size_t)n * 3 * HW + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 64 : nullptr;
+  float v[3];
+  if (chroma420[n] == 0) {  // the whole wave
+    v[0] = (float)(((19595 * R + 38470 * G + 7471 * B + 32768) >> 16) - 128);
+    v[1] = (float)(((-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16) - 128);
+    v[2] = (float)(((32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16) - 128);
+    jpeg_codec<3>(buf, v, lane, scale, 0, quot, HW);
+  } else {
+    float luma[1] = {(float)(((19595 * R + 38470 * G + 7471 * B + 32768) >> 16) - 128)};
+    jpeg_codec<1>(buf, luma, lane, scale, 0, quot, HW);
+    v[0] = luma[0];
+    const int pitch = jpeg420_blocks(W) * 8;
+    const size_t plane = (size_t)jpeg420_blocks(H) * 8 * pitch;
+    const int cy = y >> 1, cx = x >> 1;
+    const int ny = min(max(cy + ((y & 1) ? 1 : -1), 0), H / 2 - 1), nx = min(max(cx + ((x & 1) ? 1 : -1), 0), W / 2 - 1);
+    const float* cw = ws + (size_t)n * 2 * plane;
+#pragma unroll
+    for (int p = 0; p < 2; ++p, cw += plane) {
+      const float c = cw[(size_t)cy * pitch + cx], vn = cw[(size_t)ny * pitch + cx], hn = cw[(size_t)cy * pitch + nx],
+                  dn = cw[(size_t)ny * pitch + nx];
+      v[1 + p] = fmaf(3.f, fmaf(3.f, c, vn), fmaf(3.f, hn, dn)) * 0.0625f;
+    }
+  }
+  const float yy = v[0] + 128.f;
+  float rgb[3] = {yy + 1.402f * v[2], yy - 0.344136286f * v[1] - 0.714136286f * v[2], yy + 1.772f * v[1]};
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    float o = fminf(fmaxf(rgb[p] * (1.0f / 255.0f), 0.f), 1.f);
+    if (quantize) o = rintf(o * 255.f) * (1.0f / 255.0f);
+    out[at + p * HW] = o;
+  }
+}
+
 unsigned grid_for(int64_t n) {
   int64_t b = (n + 255) / 256;
   return (unsigned)(b < 1 ? 1 : (b > 65535 ? 65535 : b));
@@ -496,5 +652,30 @@ extern "C" int srx_jpeg_sim(const float* in_nchw, float* out_nchw, const int32_t
   hipLaunchKernelGGL(jpeg_sim_kernel, dim3(W / 8, H / 8, N), dim3(64), 0, srx_stream(stream), in_nchw, out_nchw, quality, H,
                      W, quantize);
   SRX_CHECK_LAUNCH("jpeg_sim_kernel");
+  return SRX_OK;
+}
+
+extern "C" size_t srx_jpeg_sim2_workspace(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)N * 2 * jpeg420_blocks(H) * 8 * jpeg420_blocks(W) * 8 * sizeof(float);
+}
+
+extern "C" int srx_jpeg_sim2(const float* in_nchw, float* out_nchw, const int32_t* quality, const int32_t* chroma420, int N,
+                             int H, int W, int quantize, void* workspace, size_t workspace_bytes, float* quot_out,
+                             void* stream) {
+  SRX_REQUIRE(in_nchw && out_nchw && quality && chroma420 && workspace, "jpeg_sim2: null pointer");
+  SRX_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0, "jpeg_sim2: bad shape");
+  SRX_REQUIRE(H % 8 == 0 && W % 8 == 0, "jpeg_sim2: %d x %d planes: whole 8 x 8 blocks only", H, W);
+  SRX_REQUIRE(H / 8 <= 65535 && (int64_t)H * W <= 0x7fffffff, "jpeg_sim2: planes too large");
+  const size_t need = srx_jpeg_sim2_workspace(N, H, W);
+  SRX_REQUIRE(workspace_bytes >= need, "jpeg_sim2: workspace of %zu bytes, %zu needed (srx_jpeg_sim2_workspace)", workspace_bytes,
+              need);
+  hipStream_t st = srx_stream(stream);
+  hipLaunchKernelGGL(jpeg420_chroma_kernel, dim3(jpeg420_blocks(W), jpeg420_blocks(H), N), dim3(64), 0, st, in_nchw, quality,
+                     chroma420, (float*)workspace, quot_out, H, W);
+  SRX_CHECK_LAUNCH("jpeg420_chroma_kernel");
+  hipLaunchKernelGGL(jpeg420_luma_kernel, dim3(W / 8, H / 8, N), dim3(64), 0, st, in_nchw, out_nchw, quality, chroma420,
+                     (const float*)workspace, quot_out, H, W, quantize);
+  SRX_CHECK_LAUNCH("jpeg420_luma_kernel");
   return SRX_OK;
 }

@@ -93,7 +93,7 @@ class DeviceLoader:
 
     def __init__(self, images, device, batch_size: int, crop_size: int, upscale_factor: int, test: bool, seed: int,
                  multiplier: int = 1, rank: int = 0, world_size: int = 1, gt_usm: bool = False, pair_pool: int = 0,
-                 poisson_prob: float = 0.0, degradation: str = 'bicubic'):
+                 jpeg420_prob: float = 0.0, poisson_prob: float = 0.0, degradation: str = 'bicubic'):
         from . import _lib
         if degradation not in DEGRADATIONS:
             raise ValueError(f'DeviceLoader: degradation must be one of {DEGRADATIONS}, got {degradation!r}')
@@ -117,6 +117,11 @@ class DeviceLoader:
             raise ValueError(f'DeviceLoader: poisson_prob must be a number in [0, 1], got {poisson_prob!r}')
         if poisson_prob > 0 and degradation not in ('blind', 'blind2'):
             raise ValueError(f'DeviceLoader: poisson_prob needs degradation blind or blind2 (bicubic adds no noise), got '
+                             f'{degradation!r}')
+        if isinstance(jpeg420_prob, bool) or not isinstance(jpeg420_prob, (int, float)) or not 0.0 <= jpeg420_prob <= 1.0:
+            raise ValueError(f'DeviceLoader: jpeg420_prob must be a number in [0, 1], got {jpeg420_prob!r}')
+        if jpeg420_prob > 0 and degradation not in ('blind', 'blind2'):
+            raise ValueError(f'DeviceLoader: jpeg420_prob needs degradation blind or blind2 (bicubic has no JPEG stage), got '
                              f'{degradation!r}')
         if isinstance(pair_pool, bool) or not isinstance(pair_pool, int) or pair_pool < 0:
             raise ValueError(f'DeviceLoader: pair_pool must be a non-negative int (pairs in the pool; 0: off), got {pair_pool!r}')
@@ -153,6 +158,10 @@ class DeviceLoader:
         # pairs they produce without a pool; only the order in which pairs reach the trainer changes ('Training pair pool')
         self.pair_pool = pair_pool
         self.pool_rng = random.Random(seed * 49979687 + rank + 715225739) if pair_pool > 0 else None
+        # ``blind`` / ``blind2`` train batches with ``jpeg420_prob`` > 0 only: which samples of a JPEG stage are stored 4:2:0 comes from
+        # a fifth stream, so the four above are what they were ('Chroma subsampling')
+        self.jpeg420_prob = float(jpeg420_prob)
+        self.j420_rng = random.Random(seed * 67867967 + rank + 236887691) if self.jpeg420_prob > 0 else None
         self.pool_lr = self.pool_hr = None     # [pair_pool, 3, crop / scale, crop / scale] and [pair_pool, 3, crop, crop], made at the first batch
         self.pool_filled = 0                   # pairs stored so far; the pool outlives the epochs
         self.last_degradation = None
@@ -323,6 +332,21 @@ class DeviceLoader:
         deg['poisson_scale'] = scale
         return deg
 
+    def _draw_jpeg420(self, deg: dict) -> dict:
+        """The chroma subsampling of a drawn batch, from its own stream; ``deg`` is changed in place and returned.  Per SAMPLE, per
+        JPEG STAGE of the recipe (one for ``blind``, two for ``blind2``): one uniform (< ``jpeg420_prob``: 4:2:0), drawn whether or not
+        the stage's quality is a JPEG quality, so the stream's position depends on no outcome.  ``deg`` gains ``chroma420``, int32
+        shaped like ``quality``: 1 where 4:2:0 was chosen, else 0."""
+        import numpy as np
+        rng, quality = self.j420_rng, deg['quality']
+        flags = np.zeros(quality.shape, dtype=np.int32)
+        fl = flags.reshape(-1, quality.shape[-1])   # a view: [stages][n]
+        for i in range(fl.shape[1]):
+            for stage in range(fl.shape[0]):
+                fl[stage, i] = int(rng.random() < self.jpeg420_prob)
+        deg['chroma420'] = flags
+        return deg
+
     def _draw_pool_slots(self):
         """The pool's part of the next train batch: ``(slots, mode)`` for ``srx_pool_exchange``.  While the pool fills -- its first
         ``pair_pool / batch`` batches -- the next free slots in order and mode 0 (store: the batch is yielded as generated, what
@@ -349,7 +373,7 @@ class DeviceLoader:
     def _plan(self):
         """Host side of one epoch: per batch the sample indices, the crop / flip rows and -- ``blind`` and ``blind2`` train batches
         only, and after the rows, from the other stream -- the degradation parameters (else None); with ``poisson_prob`` > 0 their
-        Poisson branch after them, from the third."""
+        Poisson branch after them, from the third; with ``jpeg420_prob`` > 0 their chroma subsampling last, from the fifth."""
         order = list(self.order)
         if not self.test:
             random.Random(self.epoch * 104729 + 17).shuffle(order)  # same permutation on every rank
@@ -361,7 +385,11 @@ class DeviceLoader:
             blind = self.degradation == 'blind' and not self.test   # the test set stays bicubic: PSNR comparable across runs
             blind2 = self.degradation == 'blind2' and not self.test
             deg = self._draw_degradation(len(idx)) if blind else self._draw_degradation2(len(idx)) if blind2 else None
-            yield idx, meta, self._draw_poisson(deg) if deg is not None and self.poi_rng is not None else deg
+            if deg is not None and self.poi_rng is not None:
+                deg = self._draw_poisson(deg)
+            if deg is not None and self.j420_rng is not None:
+                deg = self._draw_jpeg420(deg)
+            yield idx, meta, deg
 
     def _poisson(self, x, scale, gray_dev, seed, scale_dev=None):
         """The Poisson half of a noise step: ``x`` with ``srx_add_poisson_noise(quantize=0)`` on the samples that drew it, under the
@@ -375,11 +403,35 @@ class DeviceLoader:
         with torch.no_grad():
             return F.add_poisson_noise(x, torch.from_numpy(scale).to(x.device) if scale_dev is None else scale_dev, gray_dev, seed)[0]
 
+    def _jpeg_params(self, deg, dev):
+        """``(quality, chroma420)`` of a batch on the device, shaped as drawn: the flags ride in the quality's copy, and are None
+        -- the batch then takes ``srx_jpeg_sim``, as a loader without ``jpeg420_prob`` does -- unless a sample drew 4:2:0."""
+        import numpy as np
+        flags = deg.get('chroma420')
+        if flags is None or not flags.any():
+            return torch.from_numpy(deg['quality']).to(dev), None
+        both = torch.from_numpy(np.stack([deg['quality'], flags])).to(dev)
+        return both[0], both[1]
+
+    def _jpeg(self, x, out, quality, flags, stream):
+        """One JPEG stage, 8-bit result: ``srx_jpeg_sim``, or ``srx_jpeg_sim2`` when the batch has 4:2:0 flags (``flags`` on the
+        device, else None).  The workspace is taken per call: torch's caching allocator hands the same block back."""
+        n, _, h, w = x.shape
+        if flags is None:
+            self._lib.call('srx_jpeg_sim', x.data_ptr(), out.data_ptr(), quality.data_ptr(), n, h, w, 1, stream)
+            return out
+        nbytes = self._lib.call('srx_jpeg_sim2_workspace', n, h, w)
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+        self._lib.call('srx_jpeg_sim2', x.data_ptr(), out.data_ptr(), quality.data_ptr(), flags.data_ptr(), n, h, w, 1,
+                       ws.data_ptr(), nbytes, None, stream)
+        return out
+
     def _degrade(self, hr, deg, stream):
         """``blind``: blur -> bicubic x1/scale (unquantised) -> Poisson or Gaussian noise -> 8 bits -> JPEG -> 8 bits."""
         call, dev, n = self._lib.call, self.device, hr.shape[0]
         lc = self.crop // self.up
-        on_dev = {k: torch.from_numpy(deg[k]).to(dev) for k in ('parm', 'ksize', 'sigma_n', 'gray', 'quality')}
+        on_dev = {k: torch.from_numpy(deg[k]).to(dev) for k in ('parm', 'ksize', 'sigma_n', 'gray')}
+        on_dev['quality'], flags = self._jpeg_params(deg, dev)
         blurred = torch.empty_like(hr)
         call('srx_blur_aniso', hr.data_ptr(), blurred.data_ptr(), on_dev['parm'].data_ptr(), on_dev['ksize'].data_ptr(),
              n, 3, self.crop, self.crop, stream)
@@ -389,8 +441,7 @@ class DeviceLoader:
         lr = self._poisson(lr, deg.get('poisson_scale'), on_dev['gray'], deg['seed'])
         call('srx_add_gaussian_noise', lr.data_ptr(), noisy.data_ptr(), on_dev['sigma_n'].data_ptr(), on_dev['gray'].data_ptr(),
              deg['seed'] & 0xFFFFFFFF, deg['seed'] >> 32, n, lc, lc, 1, stream)
-        call('srx_jpeg_sim', noisy.data_ptr(), lr.data_ptr(), on_dev['quality'].data_ptr(), n, lc, lc, 1, stream)
-        return lr
+        return self._jpeg(noisy, lr, on_dev['quality'], flags, stream)
 
     def _degrade2(self, hr, deg, stream):
         """``blind2``: filter -> resize -> noise -> JPEG, twice, the second JPEG and the final sinc filter around the resize to
@@ -398,7 +449,8 @@ class DeviceLoader:
         from . import functional as F
         call, dev, n = self._lib.call, self.device, hr.shape[0]
         weights = torch.from_numpy(deg['weights']).to(dev)  # the three tables in one copy
-        ksize, sigma_n, gray, quality = (torch.from_numpy(deg[k]).to(dev) for k in ('ksize', 'sigma_n', 'gray', 'quality'))
+        ksize, sigma_n, gray = (torch.from_numpy(deg[k]).to(dev) for k in ('ksize', 'sigma_n', 'gray'))
+        quality, flags = self._jpeg_params(deg, dev)
         (s1, s2, lc), modes = deg['sizes'], deg['modes']
         pscale = deg.get('poisson_scale')
         if pscale is not None and pscale.any():
@@ -419,9 +471,7 @@ class DeviceLoader:
             return out
 
         def jpeg(x, stage):
-            out = torch.empty_like(x)
-            call('srx_jpeg_sim', x.data_ptr(), out.data_ptr(), quality[stage].data_ptr(), n, x.shape[2], x.shape[3], 1, stream)
-            return out
+            return self._jpeg(x, torch.empty_like(x), quality[stage], None if flags is None else flags[stage], stream)
 
         with torch.no_grad():
             x = jpeg(noise(F.resize(filt(hr, 0, 0), (s1, s1), modes[0]), 0, deg['seed1']), 0)
@@ -467,13 +517,14 @@ def _decode(path: str) -> torch.Tensor:
 def initialize_device_datasets(train_directory: str, device, batch_size: int = 64, crop_size: int = 96,
                                upscale_factor: int = 4, dataset_multiplier: int = 1, distributed: bool = False,
                                seed: int = 0, rank: int = 0, world_size: int = 1, gt_usm: bool = False, pair_pool: int = 0,
-                               poisson_prob: float = 0.0, degradation: str = 'bicubic'):
+                               jpeg420_prob: float = 0.0, poisson_prob: float = 0.0, degradation: str = 'bicubic'):
     """``initialize_datasets`` with the augmentation on the device (``--device-data``).  ``synthetic:N`` draws N
     seeded random 2*crop x 2*crop images.  ``degradation='blind'`` degrades the TRAIN batches' low-resolution side with blur,
     noise and JPEG (``--degradation``), ``'blind2'`` with the second-order recipe; ``gt_usm`` unsharp-masks the TRAIN batches'
     high-resolution crop, which is then both the target and what is degraded (``--gt-usm``); ``poisson_prob`` gives each sample of
     each noise stage of ``blind`` / ``blind2`` Poisson noise with that probability in place of the Gaussian one
-    (``--poisson-noise-prob``); ``pair_pool`` > 0 sends the TRAIN batches through a pool of that many pairs, so that a step sees
+    (``--poisson-noise-prob``); ``jpeg420_prob`` stores each sample of each JPEG stage of ``blind`` / ``blind2`` with 4:2:0 chroma
+    subsampling with that probability (``--jpeg-420-prob``); ``pair_pool`` > 0 sends the TRAIN batches through a pool of that many pairs, so that a step sees
     pairs of several generated batches (``--pair-pool``); the test loader stays bicubic and unsharpened and never has a pool."""
     if train_directory.startswith('synthetic:'):
         n = int(train_directory.split(':')[1])
@@ -491,7 +542,7 @@ def initialize_device_datasets(train_directory: str, device, batch_size: int = 6
         rank, world_size = 0, 1
     train = DeviceLoader(images[n_test:] or images, device, batch_size, crop_size, upscale_factor, False, seed,
                          dataset_multiplier, rank, world_size, degradation=degradation, gt_usm=gt_usm, poisson_prob=poisson_prob,
-                         pair_pool=pair_pool)
+                         pair_pool=pair_pool, jpeg420_prob=jpeg420_prob)
     # dataset.py:343-360: the test set is multiplied like the train set, sharded over the ranks, nothing dropped
     test = DeviceLoader(images[:n_test], device, batch_size, crop_size, upscale_factor, True, seed + 1,
                         dataset_multiplier, rank, world_size)

@@ -159,6 +159,11 @@ def parse_args(argv=None) -> Namespace:
                        help='with --device-data and --degradation blind or blind2: the probability with which a sample of a '
                             'noise stage gets signal-dependent Poisson (shot) noise, the noise of dark photos, in place of the '
                             'stage\'s Gaussian noise.  Real-ESRGAN uses 0.5; the default 0 leaves the degradation as it was')
+    train.add_argument('--jpeg-420-prob', type=probability, default=0.0, metavar='FLOAT',
+                       help='with --device-data and --degradation blind or blind2: the probability with which a sample of a '
+                            'JPEG stage is stored with 4:2:0 chroma subsampling, as nearly every real JPEG is: chroma averaged '
+                            '2 x 2, coded in blocks that cover 16 x 16 pixels and interpolated back.  Real-ESRGAN\'s JPEG layer '
+                            'always subsamples (1.0); the default 0 leaves the degradation as it was')
     train.add_argument('--pair-pool', type=non_negative_integer, default=0, metavar='N',
                        help='with --device-data and --degradation blind or blind2: keep a pool of N degraded training pairs in HBM '
                             '(Real-ESRGAN\'s training pair pool).  blind2 draws its resize factors, modes and order once per batch; '
@@ -208,6 +213,9 @@ def parse_args(argv=None) -> Namespace:
                      'discriminator')
     if args.function == 'train' and args.poisson_noise_prob > 0 and not (args.device_data and args.degradation in ('blind', 'blind2')):
         parser.error('--poisson-noise-prob replaces the Gaussian noise of a blind degradation: add --device-data and '
+                     '--degradation blind or --degradation blind2')
+    if args.function == 'train' and args.jpeg_420_prob > 0 and not (args.device_data and args.degradation in ('blind', 'blind2')):
+        parser.error('--jpeg-420-prob subsamples the chroma of a blind degradation\'s JPEG: add --device-data and '
                      '--degradation blind or --degradation blind2')
     if args.function == 'train' and args.pair_pool > 0:
         if not (args.device_data and args.degradation in ('blind', 'blind2')):
@@ -270,7 +278,8 @@ def main(argv=None) -> None:
             args.train_dir, device, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=4,
             dataset_multiplier=args.dataset_multiplier, distributed=distributed, seed=args.seed,
             rank=max(int(args.rank), 0) if distributed else 0, world_size=int(args.world_size) if distributed else 1,
-            degradation=args.degradation, gt_usm=args.gt_usm, poisson_prob=args.poisson_noise_prob, pair_pool=args.pair_pool)
+            degradation=args.degradation, gt_usm=args.gt_usm, poisson_prob=args.poisson_noise_prob, pair_pool=args.pair_pool,
+            jpeg420_prob=args.jpeg_420_prob)
         if args.pair_pool and args.rank in [-1, 0]:
             per_pair = 4 * 3 * (crop_size * crop_size + (crop_size // 4) ** 2)
             print(f'training pair pool: {args.pair_pool} pairs per process, {args.pair_pool * per_pair / 1e6:.1f} MB of HBM; the first '
