@@ -249,6 +249,24 @@ int srx_linear_force(int form, int splits);
  * workgroups.  SRX_E_UNSUPPORTED when the layer does not take that path, or is forced to a form it has no kernel for. */
 int srx_thin_plan(const srx_conv2d_t* d, int which, int* out);
 
+/* RRDBNet's x2 input layer (unshuffle.hip): y = conv3x3_pad1(pixel_unshuffle(pad(x), 2), w) + bias in one launch, nothing in
+ * between written.  x: the NHWC-4 image [N][H][W][4] (channel 3 is not read); an odd H / W is padded by one reflected row /
+ * column at the bottom / right inside the gather (RealESRGANer.pre_process): Hp = H + (H & 1), Wp = W + (W & 1); y: fp32
+ * [N][Hp / 2][Wp / 2][64]; bias [64] or NULL; no activation.  The layer is the 6x6 / stride 2 / pad 2 conv over the image with
+ * v[o][c][2 ky + dy][2 kx + dx] = w[o][4 c + 2 dy + dx][ky][kx].
+ *   pack: w OIHW fp32 [64][12][3][3] -> wpk, srx_unshuffle2_conv_packed_floats() = 108 x 64 floats ([k = (tap, channel)][64]).
+ *   fwd:  precision 0: exact fp32 MFMAs; 1: operands rounded to bf16, fp32 products and sums.  Recorded for srx_prof_get as
+ *         "unshuffle2_conv_fwd_kernel<precision> MxNxK=<N Hp/2 Wp/2>x64x108".
+ *   plan: host only, by the function the launch plans with (under srx_set_reserved_cus): out[2] = {tiles of 32 output pixels,
+ *         workgroups}; a wave walks tile = 4 workgroup + wave, += 4 workgroups.
+ * Refused with SRX_E_BADARG, nothing launched: a null x / wpk / y, N, H or W < 1, an odd H or W below 3 (no row to reflect),
+ * N Hp Wp >= 2^24 pixels, a precision other than 0 / 1. */
+size_t srx_unshuffle2_conv_packed_floats(void);
+int srx_unshuffle2_conv_pack(const float* w_oihw, float* wpk, void* stream);
+int srx_unshuffle2_conv_fwd(int N, int H, int W, const float* x, const float* wpk, const float* bias, float* y, int precision,
+                            void* stream);
+int srx_unshuffle2_conv_plan(int N, int H, int W, int* out);
+
 /* Launch plan of nn.Linear (linear.hip), computed by the function the launches themselves plan with; host code only.  which = 0
  * forward, 1 data gradient: out[6] = {splits launched (slabs of partial sums), contraction elements per split (k / j), launches
  * of up to 64 rows, 16-row blocks NB of the last launch, form of the first launch (1 plain, 2 fast), form of the last launch}.

@@ -12,7 +12,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('SRX_LIB') or os.path.join(CSRC, 'libsrx_hip.so')  # SRX_LIB: developer A/B builds on one GPU box
-SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'degrade.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip', 'resample.hip', 'usm.hip', 'pool.hip', 'colorfix.hip', 'compact.hip', 'specnorm.hip']
+SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'degrade.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip', 'resample.hip', 'usm.hip', 'pool.hip', 'colorfix.hip', 'compact.hip', 'specnorm.hip', 'unshuffle.hip']
 # headers the sources include, relative to CSRC: part of the build's digest and of every object's cache key
 HEADERS = ['srx_common.h', 'conv_host.h', os.path.join('..', '..', 'include', 'srx.h')]
 
@@ -175,6 +175,10 @@ _SIGS = {
     'srx_conv2d_force_plan': (_I, [_I, _I, _I, _I]),
     'srx_thin_plan': (_I, [_D, _I, C.POINTER(C.c_int)]),
     'srx_thin_force_rows': (_I, [_I]),
+    'srx_unshuffle2_conv_packed_floats': (_Z, []),
+    'srx_unshuffle2_conv_pack': (_I, [_P, _P, _P]),
+    'srx_unshuffle2_conv_fwd': (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P]),
+    'srx_unshuffle2_conv_plan': (_I, [_I, _I, _I, C.POINTER(C.c_int)]),
     'srx_conv2d_force_s2': (_I, [_I, _I, _I]),
     'srx_wgrad_force': (_I, [_I, _I]),
     'srx_wgrad_force_kernels': (_I, [_I, _I, _I]),

@@ -1252,6 +1252,32 @@ def conv2d(x: Tensor, weight: Tensor, bias: Optional[Tensor], st: ConvState, wan
     return _Conv2d.apply(x, weight, bias, st, want_stats, weight if master is None else master, in_act, act_bwd_folded)
 
 
+def unshuffle2_conv(x4: Tensor, weight: Tensor, bias: Optional[Tensor], st: ConvState) -> Tensor:
+    """RRDBNet's x2 input layer, ``conv2d(pixel_unshuffle(pad(x), 2), weight, bias, padding=1)``, as one launch on the NHWC-4
+    image (csrc/unshuffle.hip): ``x4`` [N,H,W,4], ``weight`` OIHW [64,12,3,3] -> [N,Hp/2,Wp/2,64] with an odd H / W padded by
+    one reflected row / column inside the gather.  Inference only (no autograd node); ``st.precision`` 0 or 1.  The weights
+    are packed once through ``st.direct`` (``WeightPack.ensure``, keyed like every other layer's)."""
+    if torch.is_grad_enabled():
+        raise RuntimeError('unshuffle2_conv: the x2 input layer is inference-only; run it under torch.no_grad() on an eval-mode model')
+    if st.precision not in (0, 1):
+        raise RuntimeError(f"unshuffle2_conv: precision {st.precision} has no kernel ('fp32' and 'bf16' do)")
+    x4 = _chk(x4, 'unshuffle2_conv.input')
+    n, h, w, cs = x4.shape
+    if cs != 4 or tuple(weight.shape) != (64, 12, 3, 3):
+        raise RuntimeError(f'unshuffle2_conv: expected an NHWC-4 image and a [64, 12, 3, 3] weight, got {tuple(x4.shape)} and '
+                           f'{tuple(weight.shape)}')
+    if (h & 1 and h < 3) or (w & 1 and w < 3):
+        raise RuntimeError(f'unshuffle2_conv: an odd height or width is padded by reflection and must be at least 3, got {h} x {w}')
+    st.direct.ensure(st.pack_key(weight), weight.device, False,
+                     lambda: (_lib.lib().srx_unshuffle2_conv_packed_floats(), 0, torch.float32),
+                     lambda fwd, bwd, _: call('srx_unshuffle2_conv_pack', _p(_chk(weight.detach(), 'unshuffle2_conv.weight')), _p(fwd),
+                                              _stream()))
+    b = None if bias is None else _chk(bias.detach(), 'unshuffle2_conv.bias')
+    y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, 64), dtype=torch.float32, device=x4.device)
+    call('srx_unshuffle2_conv_fwd', n, h, w, _p(x4), _p(st.direct.fwd), _p(b), _p(y), st.precision, _stream())
+    return y
+
+
 # --------------------------------------------------------------------------- batch norm (+act, +residual)
 class _BNAct(Function):
     @staticmethod

@@ -71,6 +71,27 @@ class Conv2d(nn.Conv2d):
         return new
 
 
+class Unshuffle2Conv2d(Conv2d):
+    """RRDBNet's input layer at x2: ``nn.Conv2d(12, 64, 3, 1, 1)`` behind ``pixel_unshuffle(x, 2)``, with that module's
+    ``weight`` [64, 12, 3, 3] and ``bias`` -- a published x2 state_dict loads key for key.  ``forward`` takes the NHWC-4 IMAGE
+    [N,H,W,4] and returns [N,Hp/2,Wp/2,64] from one launch that gathers the unshuffled (and, for an odd H / W, reflect-padded)
+    pixels itself (``functional.unshuffle2_conv``).  Inference only: training mode or autograd raises."""
+
+    def __init__(self):
+        super().__init__(12, 64, kernel_size=3, stride=1, padding=1)
+
+    def forward(self, x4: Tensor) -> Tensor:
+        if not F.inference_mode(self):
+            raise RuntimeError('Unshuffle2Conv2d: the x2 input layer is inference-only (eval mode, no autograd); '
+                               'the training path is x4')
+        return F.unshuffle2_conv(x4, self.weight, self.bias, self._st)
+
+    def __deepcopy__(self, memo):
+        new = Unshuffle2Conv2d()
+        new.load_state_dict(self.state_dict())
+        return new
+
+
 class SNConv2d(nn.Module):
     """A bias-free conv under ``torch.nn.utils.spectral_norm`` (one power iteration, eps 1e-12) with that wrapper's
     ``state_dict`` keys: ``weight_orig`` (the Parameter), ``weight_u`` and ``weight_v`` (buffers, updated by every training-mode
@@ -165,5 +186,5 @@ class Marker(nn.Module):
         return x
 
 
-__all__ = ['no_weight_grad', 'Conv2d', 'SNConv2d', 'BatchNorm2d', 'PReLU', 'LeakyReLU', 'Linear', 'Marker', 'ACT_NONE',
+__all__ = ['no_weight_grad', 'Conv2d', 'Unshuffle2Conv2d', 'SNConv2d', 'BatchNorm2d', 'PReLU', 'LeakyReLU', 'Linear', 'Marker', 'ACT_NONE',
            'ACT_RELU', 'ACT_LRELU']

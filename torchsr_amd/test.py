@@ -22,7 +22,9 @@ from collections import OrderedDict
 import torch
 from torch import Tensor
 
-HALO = 48            # LR pixels: default when the generator does not name its own (``Generator.halo``)
+from .rrdbnet import generator_to_rrdbnet_state, rrdbnet_geometry, rrdbnet_to_generator_state  # noqa: F401  (host code)
+
+HALO = 48           # LR pixels: default when the generator does not name its own (``Generator.halo``)
 MAX_TILE_PIXELS = 600 * 1000  # LR pixels per tile (x16 HR pixels must stay < 2^24)
 TRUNK_MAX_PIXELS = 8 * 1000 * 1000  # LR pixels the staged path runs untiled (x256 floats of the sub-pixel conv < 2^31)
 
@@ -51,7 +53,9 @@ def compact_num_conv(state) -> int:
 def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
             max_tile_pixels: int = MAX_TILE_PIXELS, scale: int = 4, precision: str = None, staged: bool = True,
             self_ensemble: int = 0, outscale: float = None, color_fix: str = None) -> Tensor:
-    """``generator(low_res)`` in eval mode, tiled when the image is large.  ``low_res``: [N,3,h,w].
+    """``generator(low_res)`` in eval mode, tiled when the image is large.  ``low_res``: [N,3,h,w].  ``scale``: the generator's
+    factor (4; 2 for ``esrgan.Generator(scale_factor=2)``).  A generator with a ``tile_align`` attribute (that x2 net: 2) gets
+    tiles whose origins, sizes and halo are multiples of it (``tile_plan``).
 
     ``precision``: ``'fp32'`` (exact; the reference's ``test`` runs no autocast, test.py:57-62), ``'bf16'`` (bf16
     products with fp32 accumulation in every conv but the 3-channel INPUT conv) or ``'fp16'``
@@ -135,20 +139,37 @@ def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
         return generator(low_res)
     if staged and hasattr(generator, 'infer_trunk_nhwc') and n * h * w <= TRUNK_MAX_PIXELS:
         return _upscale_staged(generator, low_res, max_tile_pixels * scale * scale, scale)
-    rows = max(1, -(-h * w * n // max_tile_pixels))
-    th = -(-h // int(rows ** 0.5 + 0.999))
-    tw = max(1, max_tile_pixels // (n * (th + 2 * halo))) - 2 * halo
-    tw = max(64, min(tw, w))
+    _, _, _, tiles = tile_plan(h, w, halo, max_tile_pixels, int(getattr(generator, 'tile_align', 1)), n)
     out = torch.empty((n, c, h * scale, w * scale), dtype=low_res.dtype, device=low_res.device)
+    for y0, y1, x0, x1, ya, yb, xa, xb in tiles:
+        sr = generator(low_res[:, :, ya:yb, xa:xb].contiguous())
+        out[:, :, y0 * scale:y1 * scale, x0 * scale:x1 * scale] = \
+            sr[:, :, (y0 - ya) * scale:(y1 - ya) * scale, (x0 - xa) * scale:(x1 - xa) * scale]
+    return out
+
+
+def tile_plan(h: int, w: int, halo: int, max_tile_pixels: int, tile_align: int = 1, n: int = 1):
+    """The halo tiling of an ``n`` x ``h`` x ``w`` image as a pure function: ``(th, tw, halo, tiles)`` -- the interior tile size,
+    the halo used, and per tile ``(y0, y1, x0, x1, ya, yb, xa, xb)``: the interior rows / columns it owns and the rows / columns
+    the generator runs on, rows outermost.  ``tile_align`` (a generator's ``tile_align``, default 1): tile height, tile width and
+    halo are rounded UP to its multiples, so that every tile and every halo starts at a multiple of it -- at 2 the
+    pixel-unshuffle phase of a tile is the phase of the whole image, and only a tile at the image's bottom / right edge can have
+    an odd size, the image's own.  With 1 nothing is rounded."""
+    def up(v):
+        return -(-v // tile_align) * tile_align
+    halo = up(halo)
+    rows = max(1, -(-h * w * n // max_tile_pixels))
+    th = up(-(-h // int(rows ** 0.5 + 0.999)))
+    tw = max(1, max_tile_pixels // (n * (th + 2 * halo))) - 2 * halo
+    tw = up(max(64, min(tw, w)))
+    tiles = []
     for y0 in range(0, h, th):
         for x0 in range(0, w, tw):
             y1, x1 = min(h, y0 + th), min(w, x0 + tw)
             ya, xa = max(0, y0 - halo), max(0, x0 - halo)
             yb, xb = min(h, y1 + halo), min(w, x1 + halo)
-            sr = generator(low_res[:, :, ya:yb, xa:xb].contiguous())
-            out[:, :, y0 * scale:y1 * scale, x0 * scale:x1 * scale] = \
-                sr[:, :, (y0 - ya) * scale:(y1 - ya) * scale, (x0 - xa) * scale:(x1 - xa) * scale]
-    return out
+            tiles.append((y0, y1, x0, x1, ya, yb, xa, xb))
+    return th, tw, halo, tiles
 
 
 def _outscale_size(low_res: Tensor, outscale, scale: int):
@@ -220,14 +241,22 @@ def test(args: Namespace, model: object, device) -> None:
     from PIL import Image
     from .srgan.trainer import save_image
     state = load_generator_state(getattr(args, 'weights', None) or f'{args.model.lower()}-gan-best.pth')
+    scale = 4
     if args.model.lower() == 'compact':  # a 16-conv and a 32-conv file both load: the depth is the file's
         generator = model(num_conv=compact_num_conv(state)).to(device)
+    elif args.model.lower() == 'esrgan':
+        # a published RRDBNet file (BasicSR / Real-ESRGAN or xinntao/ESRGAN key names) or one of this package's: the number
+        # of blocks (23, or 6 for the anime model) and the scale (x4, or x2 behind pixel_unshuffle) are the file's
+        state = rrdbnet_to_generator_state(state)
+        num_blocks, scale = rrdbnet_geometry(state)
+        generator = model(num_rrdb_blocks=num_blocks, scale_factor=scale).to(device)
+        scale = generator.scale_factor
     else:
         generator = model().to(device)
     generator.load_state_dict(state)
     image = np.asarray(Image.open(args.image).convert('RGB'), dtype='float32') / 255.0
     low_res = torch.from_numpy(image).permute(2, 0, 1).unsqueeze(0).contiguous().to(device)
-    super_res = upscale(generator, low_res, precision=getattr(args, 'precision', None) or 'fp32',
+    super_res = upscale(generator, low_res, scale=scale, precision=getattr(args, 'precision', None) or 'fp32',
                         self_ensemble=getattr(args, 'self_ensemble', 0) or 0, outscale=getattr(args, 'outscale', None),
                         color_fix=getattr(args, 'color_fix', None))
     head, tail = os.path.split(args.image)

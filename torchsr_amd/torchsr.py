@@ -183,7 +183,10 @@ def parse_args(argv=None) -> Namespace:
     test.add_argument('--weights', type=str, default=None, metavar='PATH',
                       help='the checkpoint to load (default: <model>-gan-best.pth in the working directory): a bare state_dict, '
                            'this package\'s {"state": ...} or Real-ESRGAN\'s {"params_ema": ...} / {"params": ...}.  For --model '
-                           'compact the number of body convs is read off the file')
+                           'compact the number of body convs is read off the file.  --model esrgan takes every published '
+                           'RRDBNet file -- RealESRGAN_x4plus, ESRGAN_SRx4_DF2KOST_official, RealESRGAN_x4plus_anime_6B, '
+                           'RealESRGAN_x2plus -- in BasicSR / Real-ESRGAN or xinntao/ESRGAN key names as well as this '
+                           'package\'s own: the number of blocks and the scale (x4, or x2) are read off the file')
     test.add_argument('--precision', type=str, default='fp32', choices=('fp32', 'bf16', 'fp16'),
                       help='conv arithmetic of the generator forward: exact fp32 (the reference runs no autocast here), '
                            'bf16 products with fp32 accumulation, or fp16 products and fp16-stored activations with fp32 '
@@ -193,12 +196,12 @@ def parse_args(argv=None) -> Namespace:
                            'flips only), map every result back and average them.  Costs N generator forwards instead of '
                            'one; needs no other weights; combines with every --precision and either --model')
     test.add_argument('--outscale', type=positive_float, default=None, metavar='FLOAT',
-                      help='total factor from the image to the result (default: the model\'s 4).  The model always runs at '
-                           'x4; its result is then resampled once, on the GPU, with the antialiased bicubic filter the '
-                           'training data was reduced with (2: a 4K picture from a 1080p one).  Combines with every '
-                           '--precision, --self-ensemble and either --model')
+                      help='total factor from the image to the result (default: the model\'s own, 4, or 2 for an x2 RRDBNet '
+                           'file).  The model always runs at its own scale; its result is then resampled once, on the GPU, '
+                           'with the antialiased bicubic filter the training data was reduced with (2 with an x4 model: a 4K '
+                           'picture from a 1080p one).  Combines with every --precision, --self-ensemble and every --model')
     test.add_argument('--color-fix', type=str, default=None, choices=('wavelet', 'adain'),
-                      help='correct the colour of the x4 result against the image, on the GPU (default: off).  wavelet: keep '
+                      help='correct the colour of the model\'s result against the image, on the GPU (default: off).  wavelet: keep '
                            'the result\'s detail and take the low frequencies -- five levels of a dilated 3x3 blur -- from the '
                            'enlarged image; adain: map every channel to the image\'s mean and standard deviation.  Runs behind '
                            'the ensemble average and before --outscale; combines with every other option')
