@@ -1,10 +1,28 @@
 """Device tensors with owned surroundings, and the elementwise comparison, for the tests that watch what a kernel reads and writes
-next to its tensors (test_linear_forms_gpu.py, test_head_gpu.py)."""
+next to its tensors (test_linear_forms_gpu.py, test_head_gpu.py); and the plain NaN-guarded output of the degradation kernels'
+tests (test_degrade_gpu.py, test_degrade2_gpu.py, test_usm_gpu.py)."""
 import ctypes as C
+import math
 
 import torch
 
 SENTINEL = 12345.6789
+GUARD = 64  # floats of NaN on either side of a _guarded output: a store outside the tensor shows
+
+
+def _guarded(shape, dev):
+    """``(buf, out)``: an output of ``shape``, all NaN, between GUARD NaN floats on either side."""
+    n = math.prod(shape)
+    buf = torch.full((GUARD + n + GUARD,), float('nan'), device=dev)
+    return buf, buf[GUARD:GUARD + n].view(shape)
+
+
+def _band_kept(buf):
+    return bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[-GUARD:]).all())
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
 
 
 class Guarded:

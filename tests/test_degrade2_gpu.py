@@ -10,24 +10,10 @@ import torch
 
 import degrade2_ref as R2
 import degrade_ref as R
+from degrade_chain import blind2_by_hand, write_images
+from guarded import _band_kept, _guarded, _stream
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64  # floats of NaN on either side of every output: a store outside the tensor shows
-
-
-def _guarded(shape, dev):
-    n = int(np.prod(shape))
-    buf = torch.full((GUARD + n + GUARD,), float('nan'), device=dev)
-    return buf, buf[GUARD:GUARD + n].view(shape)
-
-
-def _band_kept(buf):
-    return bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[-GUARD:]).all())
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def gpu_filter(x, slots, ksize, quantize, dev):
@@ -138,6 +124,19 @@ def test_filter2d_reads_only_the_centred_window(dev):
     assert np.abs(clean.astype(np.float64) - R2.filter2d(x, slots, ksize)).max() <= R2.filter2d_tolerance(slots, ksize, 1.0)
 
 
+@pytest.mark.parametrize('quantize', [False, True])
+def test_functional_filter2d(dev, quantize):
+    """The launcher against the raw call, bit for bit: [2, 3, 12, 16] with sizes 7 and 21, then 21 and a copy."""
+    from torchsr_amd import functional as F
+    slots, _ = _slots(['sinc7', 'sinc21'])
+    x = torch.rand((2, 3, 12, 16), generator=torch.Generator().manual_seed(3)).numpy()
+    for ksize in ([7, 21], [21, 0]):
+        got = F.filter2d(torch.from_numpy(x).to(dev), torch.from_numpy(slots).to(dev), torch.tensor(ksize, dtype=torch.int32).to(dev),
+                         quantize)
+        want = gpu_filter(x, slots, ksize, int(quantize), dev)
+        assert torch.equal(got.cpu(), want) and not np.array_equal(want[0].numpy(), x[0])
+
+
 # ---------------------------------------------------------------------------------------------------------------- resize
 RESIZE_CASES = [((2, 3, 24, 40), (16, 56)), ((1, 3, 96, 96), (144, 16)), ((2, 3, 17, 11), (17, 11))]
 
@@ -165,66 +164,18 @@ def test_resize_against_interpolate(dev, shape, size, mode):
 
 
 # ---------------------------------------------------------------------------------------------------------------- loader
-SIZES = [(120, 150), (97, 96), (200, 130), (96, 96), (140, 101), (60, 80), (128, 128), (110, 99), (100, 100), (150, 97)]
 # chosen on the CPU (the draw is host-only): the smallest seed whose six batches of three epochs hold everything below
 LOADER_SEED = 1
 
 
 @pytest.fixture(scope='module')
 def image_dir(tmp_path_factory):
-    """The ten random PNGs of test_degrade_gpu.py."""
-    from PIL import Image
-    d = tmp_path_factory.mktemp('degrade2') / 'imgs'
-    os.makedirs(d)
-    rng = np.random.RandomState(0)
-    for i, (h, w) in enumerate(SIZES):
-        Image.fromarray((rng.rand(h, w, 3) * 255).astype('uint8')).save(str(d / f'{i}.png'))
-    return str(d)
+    return write_images(tmp_path_factory.mktemp('degrade2') / 'imgs')
 
 
 def _train_loader(image_dir, dev, degradation, seed=LOADER_SEED):
     from torchsr_amd.dataset import initialize_device_datasets
     return initialize_device_datasets(image_dir, dev, batch_size=4, crop_size=96, seed=seed, degradation=degradation)[0]
-
-
-def by_hand(hr, deg, dev):
-    """The chain of ABI / ``functional.resize`` calls of one ``blind2`` batch, from what the loader kept."""
-    from torchsr_amd import _lib
-    from torchsr_amd import functional as F
-    s, n = _stream(), hr.shape[0]
-    dv = {k: torch.from_numpy(deg[k]).to(dev) for k in ('weights', 'ksize', 'sigma_n', 'gray', 'quality')}
-    (s1, s2, lc), modes = deg['sizes'], deg['modes']
-
-    def filt(x, stage, quantize):
-        out = torch.empty_like(x)
-        _lib.call('srx_filter2d', x.data_ptr(), out.data_ptr(), dv['weights'][stage].data_ptr(), dv['ksize'][stage].data_ptr(), n, 3,
-                  x.shape[2], x.shape[3], quantize, s)
-        return out
-
-    def noise(x, stage, seed):
-        out = torch.empty_like(x)
-        _lib.call('srx_add_gaussian_noise', x.data_ptr(), out.data_ptr(), dv['sigma_n'][stage].data_ptr(), dv['gray'][stage].data_ptr(),
-                  seed & 0xFFFFFFFF, seed >> 32, n, x.shape[2], x.shape[3], 1, s)
-        return out
-
-    def jpeg(x, stage):
-        out = torch.empty_like(x)
-        _lib.call('srx_jpeg_sim', x.data_ptr(), out.data_ptr(), dv['quality'][stage].data_ptr(), n, x.shape[2], x.shape[3], 1, s)
-        return out
-
-    with torch.no_grad():
-        a = filt(hr, 0, 0)
-        b = F.resize(a, (s1, s1), modes[0])
-        c = noise(b, 0, deg['seed1'])
-        d = jpeg(c, 0)
-        e = filt(d, 1, 0)
-        f = F.resize(e, (s2, s2), modes[1])
-        g = noise(f, 1, deg['seed2'])
-        assert tuple(d.shape) == (n, 3, s1, s1) and tuple(g.shape) == (n, 3, s2, s2)
-        assert not torch.equal(a, hr) and not torch.equal(c, b) and not torch.equal(d, c) and not torch.equal(g, f)
-        if deg['order'] == 'A':
-            return jpeg(filt(F.resize(g, (lc, lc), modes[2]), 2, 0), 1)
-        return filt(F.resize(jpeg(g, 1), (lc, lc), modes[2]), 2, 1)
 
 
 def test_blind2_loader(dev, image_dir):
@@ -239,7 +190,7 @@ def test_blind2_loader(dev, image_dir):
             levels = lr.double() * 255
             assert float(lr.min()) >= 0 and float(lr.max()) <= 1 and float((levels - levels.round()).abs().max()) < 1e-4
             deg = blind2.last_degradation
-            assert torch.equal(lr, by_hand(hr, deg, dev))
+            assert torch.equal(lr, blind2_by_hand(hr, deg, dev))
             seen.append(deg)
     # what the seed was chosen for -- a changed draw order is noticed here
     assert len(seen) == 6 and {d['order'] for d in seen} == {'A', 'B'}

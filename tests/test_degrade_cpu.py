@@ -160,6 +160,58 @@ def test_cli_degradation_flag(capsys):
         parse_args(['train', '--device-data', '--degradation', 'sinc'])
 
 
+# ------------------------------------------------------------------------------------------------------- the launchers
+def _launcher_cases():
+    """Per launcher of the device data path: legal arguments (on the CPU), and argument lists a ValueError refuses."""
+    x = torch.zeros(2, 3, 16, 16)
+    f, i = (lambda *s: torch.zeros(s)), (lambda *s: torch.zeros(s, dtype=torch.int32))
+    return {
+        'bicubic_down': ((x, 4, True), [(x[0], 4, True), (x, 0, True), (x, 1.5, True), (x, True, True)]),
+        'blur_aniso': ((x, f(2, 4), i(2)), [(x[0], f(2, 4), i(2)), (x[:, :2], f(2, 4), i(2)), (x, f(2, 3), i(2)), (x, f(3, 4), i(2)),
+                                            (x, f(2, 4), i(3)), (x, i(2, 4), i(2)), (x, f(2, 4), f(2)), (x, f(4, 2).t(), i(2))]),
+        'filter2d': ((x, f(2, 21, 21), i(2), False), [(x[:, :1], f(2, 21, 21), i(2), False), (x, f(2, 7, 7), i(2), False),
+                                                     (x, f(3, 2, 21, 21)[0, :, :, :20], i(2), False), (x, f(2, 21, 21), i(2, 1), False),
+                                                     (x, f(2, 21, 21).double(), i(2), False)]),
+        'add_gaussian_noise': ((x, f(2), i(2), 5), [(x[0], f(2), i(2), 5), (x, f(1), i(2), 5), (x, f(2), i(2, 2), 5), (x, f(2), f(2), 5),
+                                                    (x, i(2), i(2), 5), (x, f(2), i(2), -1), (x, f(2), i(2), 1 << 64),
+                                                    (x, f(2), i(2), 0.5), (x, f(2), i(2), True)]),
+        'jpeg_sim': ((x, i(2), i(2)), [(x[:, :2], i(2)), (x, i(3)), (x, f(2)), (x, i(2), i(1)), (x, i(2), f(2)), (x, i(2, 2)[:, 0])]),
+    }
+
+
+@pytest.mark.parametrize('name', ['bicubic_down', 'blur_aniso', 'filter2d', 'add_gaussian_noise', 'jpeg_sim'])
+def test_functional_launchers_check_arguments_before_the_device(name, monkeypatch):
+    from torchsr_amd import functional as F
+    monkeypatch.setattr(F, 'call', lambda *a: pytest.fail(f'{name} reached the library: {a[0]}'))
+    fn, (ok, bad) = getattr(F, name), _launcher_cases()[name]
+    for args in bad:
+        with pytest.raises(ValueError, match=name):
+            fn(*args)
+    grad = (ok[0].clone().requires_grad_(),) + ok[1:]
+    with pytest.raises(RuntimeError, match='no backward'):
+        fn(*grad)
+    with torch.no_grad(), pytest.raises(RuntimeError, match='no CPU fallback'):   # refused under grad mode only
+        fn(*grad)
+    with pytest.raises(RuntimeError, match='no CPU fallback'):   # legal arguments: the tensor's device is what is refused
+        fn(*ok)
+
+
+def test_functional_crop_flip_checks_arguments_before_the_device(monkeypatch):
+    from torchsr_amd import functional as F
+    monkeypatch.setattr(F, 'call', lambda *a: pytest.fail(f'crop_flip reached the library: {a[0]}'))
+    images = [torch.zeros((20, 31, 3), dtype=torch.uint8), torch.zeros((40, 17, 3), dtype=torch.uint8)]
+    meta = [[20, 31, 4, 15, 1, 0], [40, 17, 24, 1, 0, 1]]                   # both crops of 16 touch an edge of their image
+    edit = lambda n, k, v: [row if j != n else row[:k] + [v] + row[k + 1:] for j, row in enumerate(meta)]  # noqa: E731
+    for im, rows, crop in (([], [], 16), (images, meta[:1], 16), (images[:1], meta, 16), (images, [row[:5] for row in meta], 16),
+                           (images, edit(0, 2, 5), 16), (images, edit(0, 2, -1), 16), (images, edit(1, 3, 2), 16), (images, meta, 18),
+                           (images, edit(0, 0, 21), 16), (images, edit(1, 1, 16), 16), ([images[0], images[1].float()], meta, 16),
+                           ([images[0], images[1].transpose(0, 1)], [meta[0], [17, 40, 1, 24, 0, 1]], 16)):   # not contiguous
+        with pytest.raises(ValueError, match='crop_flip'):
+            F.crop_flip(im, rows, crop)
+    with pytest.raises(RuntimeError, match='no CPU fallback'):
+        F.crop_flip(images, meta, 16)
+
+
 # ------------------------------------------------------------------------------------------------------- the ABI
 def test_abi_refuses_bad_degradation_arguments_without_a_gpu():
     """srx_blur_aniso / srx_add_gaussian_noise / srx_jpeg_sim refuse null pointers and the shapes their kernels are not

@@ -1,6 +1,7 @@
 """``--degradation blind`` on the GPU: ``srx_blur_aniso``, ``srx_add_gaussian_noise`` and ``srx_jpeg_sim`` against their
-float64 restatements (degrade_ref.py) with derived bounds, the real JPEG codec, the ``blind`` DeviceLoader against the four
-ABI calls made by hand and against the ``bicubic`` loader, and the CLI."""
+float64 restatements (degrade_ref.py) with derived bounds, the real JPEG codec, ``functional``'s launchers of the data path
+against the raw calls, the ``blind`` DeviceLoader against the four ABI calls made by hand (degrade_chain.py) and against the
+``bicubic`` loader, and the CLI."""
 import os
 
 import numpy as np
@@ -8,24 +9,10 @@ import pytest
 import torch
 
 import degrade_ref as R
+from degrade_chain import bicubic_by_hand, blind_by_hand, write_images
+from guarded import _band_kept, _guarded, _stream
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64  # floats of NaN on either side of every output: a store outside the tensor shows
-
-
-def _guarded(shape, dev):
-    n = int(np.prod(shape))
-    buf = torch.full((GUARD + n + GUARD,), float('nan'), device=dev)
-    return buf, buf[GUARD:GUARD + n].view(shape)
-
-
-def _band_kept(buf):
-    return bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[-GUARD:]).all())
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def gpu_blur(x, parm, ksize, dev):
@@ -228,20 +215,96 @@ def test_jpeg_quantised_at_the_cpu_tests_qualities(dev):
     assert min(ratios) >= 3.0
 
 
+# ---------------------------------------------------------------------------------------------------------------- functional
+# The launchers of torchsr_amd.functional against the raw ABI call on the same inputs, bit for bit, at the smallest legal shapes.
+def test_functional_blur_aniso(dev):
+    from torchsr_amd import functional as F
+    x = torch.rand((2, 3, 12, 16), generator=torch.Generator().manual_seed(1))     # more than 10 rows, not square
+    parm, ksize = [ORIENTED, (1.7, 1.7, 0.0, 0.0)], [7, 21]
+    got = F.blur_aniso(x.to(dev), torch.tensor(parm, dtype=torch.float32).to(dev), torch.tensor(ksize, dtype=torch.int32).to(dev))
+    want = gpu_blur(x, parm, ksize, dev)
+    assert torch.equal(got.cpu(), want) and not torch.equal(want, x)
+
+
+@pytest.mark.parametrize('quantize', [False, True])
+def test_functional_bicubic_down(dev, quantize):
+    from torchsr_amd import _lib
+    from torchsr_amd import functional as F
+    x = torch.rand((2, 3, 32, 48), generator=torch.Generator().manual_seed(2)).to(dev)
+    buf, want = _guarded((2, 3, 8, 12), dev)
+    _lib.call('srx_bicubic_down', x.data_ptr(), want.data_ptr(), 2, 3, 32, 48, 4, int(quantize), _stream())
+    got = F.bicubic_down(x, 4, quantize)
+    torch.cuda.synchronize()
+    assert _band_kept(buf) and got.shape == (2, 3, 8, 12) and torch.equal(got, want)
+    levels = got.double() * 255
+    assert (float((levels - levels.round()).abs().max()) < 1e-4) == quantize
+
+
+def test_functional_add_gaussian_noise(dev):
+    from torchsr_amd import functional as F
+    assert SEED & 0xFFFFFFFF and SEED >> 32                                        # both halves of the key count
+    x = torch.from_numpy(R.jpeg_images(2, 8, 16, seed=3))
+    sigma, gray = [10 / 255, 25 / 255], [1, 0]                                     # one grey and one colour sample
+    sd, gd = torch.tensor(sigma, dtype=torch.float32).to(dev), torch.tensor(gray, dtype=torch.int32).to(dev)
+    quantised = F.add_gaussian_noise(x.to(dev), sd, gd, SEED)
+    assert torch.equal(quantised.cpu(), gpu_noise(x, sigma, gray, SEED, 1, dev))
+    raw = F.add_gaussian_noise(x.to(dev), sd, gd, SEED, quantize=False)
+    assert torch.equal(raw.cpu(), gpu_noise(x, sigma, gray, SEED, 0, dev)) and not torch.equal(raw, quantised)
+    assert not torch.equal(F.add_gaussian_noise(x.to(dev), sd, gd, SEED ^ (1 << 40)), quantised)
+
+
+@pytest.mark.parametrize('shape', [(2, 3, 8, 16), (2, 3, 16, 8)])
+def test_functional_jpeg_sim(dev, shape, monkeypatch):
+    """``chroma420`` None: exactly one ``srx_jpeg_sim`` call; given -- all 0 or mixed -- ``srx_jpeg_sim2`` on a workspace of the
+    size the library asks for."""
+    from step_layers import record_op_calls
+    from torchsr_amd import _lib
+    from torchsr_amd import functional as F
+    n, _, h, w = shape
+    quality = [30, 95]
+    x = torch.from_numpy(R.jpeg_images(n, h, w, seed=4))
+    xd, qd = x.to(dev), torch.tensor(quality, dtype=torch.int32).to(dev)
+    got = {}
+    calls = record_op_calls(monkeypatch, lambda: got.update(plain=F.jpeg_sim(xd, qd)))
+    assert calls == [('srx_jpeg_sim', (n, h, w, 1))]
+    assert torch.equal(got['plain'].cpu(), gpu_jpeg(x, quality, 1, dev))
+    assert torch.equal(F.jpeg_sim(xd, qd, quantize=False).cpu(), gpu_jpeg(x, quality, 0, dev))
+    nbytes = _lib.call('srx_jpeg_sim2_workspace', n, h, w)
+    for flags in ([0, 0], [0, 1]):
+        fd = torch.tensor(flags, dtype=torch.int32).to(dev)
+        calls = record_op_calls(monkeypatch, lambda: got.update(sub=F.jpeg_sim(xd, qd, fd)))
+        assert [name for name, _ in calls] == ['srx_jpeg_sim2_workspace', 'srx_jpeg_sim2']
+        buf, want = _guarded(shape, dev)
+        wbuf, ws = _guarded((nbytes // 4,), dev)
+        _lib.call('srx_jpeg_sim2', xd.data_ptr(), want.data_ptr(), qd.data_ptr(), fd.data_ptr(), n, h, w, 1, ws.data_ptr(), nbytes,
+                  None, _stream())
+        torch.cuda.synchronize()
+        assert _band_kept(buf) and _band_kept(wbuf) and torch.equal(got['sub'], want)
+        assert torch.equal(got['sub'], got['plain']) == (not any(flags))           # no flag set: srx_jpeg_sim's bits
+
+
+def test_functional_crop_flip(dev):
+    from torchsr_amd import _lib
+    from torchsr_amd import functional as F
+    g = torch.Generator().manual_seed(5)
+    images = [torch.randint(0, 256, s, generator=g, dtype=torch.uint8).to(dev) for s in ((20, 31, 3), (40, 17, 3))]
+    meta = [[20, 31, 3, 9, 1, 0], [40, 17, 24, 1, 0, 1]]                           # one flipped each way; the second crop ends at H
+    ptrs = torch.tensor([im.data_ptr() for im in images], dtype=torch.int64).to(dev)
+    meta_t = torch.tensor(meta, dtype=torch.int32).to(dev)
+    buf, want = _guarded((2, 3, 16, 16), dev)
+    _lib.call('srx_crop_flip_u8', ptrs.data_ptr(), meta_t.data_ptr(), want.data_ptr(), 2, 16, _stream())
+    got = F.crop_flip(images, meta, 16)
+    torch.cuda.synchronize()
+    assert _band_kept(buf) and got.shape == (2, 3, 16, 16) and torch.equal(got, want)
+    crop = images[0][3:19, 9:25].flip(1).permute(2, 0, 1)                          # hflip: the columns reversed
+    assert torch.equal((got[0] * 255).round().to(torch.uint8), crop)
+    assert torch.equal((got[1] * 255).round().to(torch.uint8), images[1][24:40, 1:17].flip(0).permute(2, 0, 1))
+
+
 # ---------------------------------------------------------------------------------------------------------------- loader
-SIZES = [(120, 150), (97, 96), (200, 130), (96, 96), (140, 101), (60, 80), (128, 128), (110, 99), (100, 100), (150, 97)]
-
-
 @pytest.fixture(scope='module')
 def image_dir(tmp_path_factory):
-    """The ten random PNGs of test_device_data_pipeline_cli."""
-    from PIL import Image
-    d = tmp_path_factory.mktemp('degrade') / 'imgs'
-    os.makedirs(d)
-    rng = np.random.RandomState(0)
-    for i, (h, w) in enumerate(SIZES):
-        Image.fromarray((rng.rand(h, w, 3) * 255).astype('uint8')).save(str(d / f'{i}.png'))
-    return str(d)
+    return write_images(tmp_path_factory.mktemp('degrade') / 'imgs')
 
 
 def _train_loader(image_dir, dev, degradation, seed=5):
@@ -250,10 +313,8 @@ def _train_loader(image_dir, dev, degradation, seed=5):
 
 
 def test_blind_loader(dev, image_dir):
-    from torchsr_amd import _lib
     blind, twin, plain = (_train_loader(image_dir, dev, d) for d in ('blind', 'blind', 'bicubic'))
     assert len(blind) == 2 and plain.last_degradation is None
-    s = _stream()
     seen = []
     for _ in range(2):  # epochs
         for (lr, hr), (lr2, hr2), (lr_p, hr_p) in zip(blind, twin, plain):
@@ -262,17 +323,9 @@ def test_blind_loader(dev, image_dir):
             assert torch.equal(lr, lr2) and torch.equal(hr, hr2)          # same seed: the same bits
             levels = lr.double() * 255
             assert float(lr.min()) >= 0 and float(lr.max()) <= 1 and float((levels - levels.round()).abs().max()) < 1e-4
-            # the four ABI calls by hand with the parameters the loader kept
+            # the four ABI calls by hand with the parameters the loader kept (every stage does something: asserted there)
             deg = blind.last_degradation
-            dv = {k: torch.from_numpy(deg[k]).to(dev) for k in ('parm', 'ksize', 'sigma_n', 'gray', 'quality')}
-            a, b, c, d = torch.empty_like(hr), torch.empty_like(lr), torch.empty_like(lr), torch.empty_like(lr)
-            _lib.call('srx_blur_aniso', hr.data_ptr(), a.data_ptr(), dv['parm'].data_ptr(), dv['ksize'].data_ptr(), 4, 3, 96, 96, s)
-            _lib.call('srx_bicubic_down', a.data_ptr(), b.data_ptr(), 4, 3, 96, 96, 4, 0, s)
-            _lib.call('srx_add_gaussian_noise', b.data_ptr(), c.data_ptr(), dv['sigma_n'].data_ptr(), dv['gray'].data_ptr(),
-                      deg['seed'] & 0xFFFFFFFF, deg['seed'] >> 32, 4, 24, 24, 1, s)
-            _lib.call('srx_jpeg_sim', c.data_ptr(), d.data_ptr(), dv['quality'].data_ptr(), 4, 24, 24, 1, s)
-            assert torch.equal(lr, d)
-            assert not torch.equal(a, hr) and not torch.equal(c, b) and not torch.equal(d, c)  # every stage does something
+            assert torch.equal(lr, blind_by_hand(hr, deg, dev))
             seen.append(deg['seed'])
     assert len(set(seen)) == 4  # a fresh noise seed per batch
     assert not any(torch.equal(x, y) for x, y in zip(next(iter(_train_loader(image_dir, dev, 'blind', seed=6))), (lr, hr)))
@@ -289,10 +342,9 @@ def test_bicubic_loader_did_not_move(dev, image_dir):
         assert deg is None
         ptrs = torch.tensor([twin.images[i].data_ptr() for i in idx], dtype=torch.int64).to(dev)
         meta_t = torch.tensor(meta, dtype=torch.int32).to(dev)
-        hr2, lr2 = torch.empty_like(hr), torch.empty_like(lr)
+        hr2 = torch.empty_like(hr)
         _lib.call('srx_crop_flip_u8', ptrs.data_ptr(), meta_t.data_ptr(), hr2.data_ptr(), 4, 96, s)
-        _lib.call('srx_bicubic_down', hr2.data_ptr(), lr2.data_ptr(), 4, 3, 96, 96, 4, 1, s)
-        assert torch.equal(hr, hr2) and torch.equal(lr, lr2)
+        assert torch.equal(hr, hr2) and torch.equal(lr, bicubic_by_hand(hr2, 4, dev))
         batches += 1
     assert batches == 2 and loader.last_degradation is None
 

@@ -8,6 +8,8 @@ import pytest
 import torch
 
 import jpeg420_ref as J
+from degrade_chain import blind2_by_hand, blind_by_hand, write_images
+from guarded import _stream
 
 pytestmark = pytest.mark.gpu
 
@@ -22,10 +24,6 @@ def _guarded(n, dev, fill=float('nan')):
 
 def _band_kept(buf):
     return bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[-GUARD:]).all())
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def gpu_jpeg2(x, quality, flags, quantize, dev, ws_fill=float('nan'), with_quot=True):
@@ -200,19 +198,9 @@ def test_refusals_launch_nothing(dev):
 
 
 # ---------------------------------------------------------------------------------------------------------------- loader
-SIZES = [(120, 150), (97, 96), (200, 130), (96, 96), (140, 101), (60, 80), (128, 128), (110, 99), (100, 100), (150, 97)]
-
-
 @pytest.fixture(scope='module')
 def image_dir(tmp_path_factory):
-    """The ten random PNGs of test_device_data_pipeline_cli."""
-    from PIL import Image
-    d = tmp_path_factory.mktemp('jpeg420') / 'imgs'
-    os.makedirs(d)
-    rng = np.random.RandomState(0)
-    for i, (h, w) in enumerate(SIZES):
-        Image.fromarray((rng.rand(h, w, 3) * 255).astype('uint8')).save(str(d / f'{i}.png'))
-    return str(d)
+    return write_images(tmp_path_factory.mktemp('jpeg420') / 'imgs')
 
 
 def _train_loader(image_dir, dev, degradation, seed=5, **kw):
@@ -223,11 +211,10 @@ def _train_loader(image_dir, dev, degradation, seed=5, **kw):
 @pytest.mark.parametrize('degradation', ['blind', 'blind2'])
 def test_loader(dev, image_dir, degradation):
     """Crop 96 / x4, batch 4.  Probability 0: the batches of a loader without the argument, bit for bit.  Probability 1: the same
-    ``hr``, every flag set and another ``lr``; for ``blind`` that ``lr`` is the restatement of the chain's last step on what the
-    first three kernels, called by hand with the recorded parameters, hand to it -- within the 8-bit step."""
-    from torchsr_amd import _lib
+    ``hr``, every flag set and another ``lr``, which is the chain of calls made by hand with the recorded parameters, bit for bit;
+    for ``blind`` that ``lr`` is also the restatement of the chain's last step on what the first three kernels, called by hand,
+    hand to it -- within the 8-bit step."""
     plain, off, one = (_train_loader(image_dir, dev, degradation, **kw) for kw in ({}, {'jpeg420_prob': 0.0}, {'jpeg420_prob': 1.0}))
-    s = _stream()
     batches = 0
     for (lr_p, hr_p), (lr_0, hr_0), (lr_1, hr_1) in zip(plain, off, one):
         assert torch.equal(lr_p, lr_0) and torch.equal(hr_p, hr_0) and 'chroma420' not in off.last_degradation
@@ -239,16 +226,14 @@ def test_loader(dev, image_dir, degradation):
         assert lr_1.shape == (4, 3, 24, 24) and float(lr_1.min()) >= 0 and float(lr_1.max()) <= 1
         assert float((levels - levels.round()).abs().max()) < 1e-4
         if degradation == 'blind':
-            dv = {k: torch.from_numpy(deg[k]).to(dev) for k in ('parm', 'ksize', 'sigma_n', 'gray')}
-            a, b, c = torch.empty_like(hr_1), torch.empty_like(lr_1), torch.empty_like(lr_1)
-            _lib.call('srx_blur_aniso', hr_1.data_ptr(), a.data_ptr(), dv['parm'].data_ptr(), dv['ksize'].data_ptr(), 4, 3, 96, 96, s)
-            _lib.call('srx_bicubic_down', a.data_ptr(), b.data_ptr(), 4, 3, 96, 96, 4, 0, s)
-            _lib.call('srx_add_gaussian_noise', b.data_ptr(), c.data_ptr(), dv['sigma_n'].data_ptr(), dv['gray'].data_ptr(),
-                      deg['seed'] & 0xFFFFFFFF, deg['seed'] >> 32, 4, 24, 24, 1, s)
+            _, _, c, d = blind_by_hand(hr_1, deg, dev, stages=True)
+            assert torch.equal(lr_1, d)
             want, _ = J.jpeg420_sim(c.cpu().numpy(), deg['quality'], deg['chroma420'], 1)
             err = np.abs(lr_1.cpu().numpy().astype(np.float64) - want).max() * 255
             print(f'blind lr against the restatement on the kernel chain\'s input: {err:.3f} grey levels at most')
             assert err <= 1 + 1e-4
+        else:
+            assert torch.equal(lr_1, blind2_by_hand(hr_1, deg, dev))
         batches += 1
     assert batches == 2
 

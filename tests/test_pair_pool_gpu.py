@@ -8,15 +8,13 @@ import pytest
 import torch
 
 import pool_ref as R
+from degrade_chain import same_draws
+from guarded import _stream
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 64            # words of a sentinel on either side of every buffer: a store outside it shows
 SENTINEL = 0x5A5A5A5A
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _guarded(words, shape, dev):
@@ -186,12 +184,6 @@ def _spy_slots(loader):
     return drawn
 
 
-def _same_degradation(a, b):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert np.array_equal(a[k], b[k]) if isinstance(a[k], np.ndarray) else a[k] == b[k], k
-
-
 @pytest.mark.parametrize('gt_usm', [False, True])
 def test_pair_pool_loader(dev, gt_usm):
     """Two epochs of a ``blind2`` loader with a pool of two batches beside the same loader without one: every yielded sample is,
@@ -208,7 +200,7 @@ def test_pair_pool_loader(dev, gt_usm):
     for epoch in range(c['epochs']):
         for (lr, hr), (lr_g, hr_g) in zip(pooled, plain):
             assert lr.shape == lr_g.shape == (b, 3, c['crop'] // c['scale'], c['crop'] // c['scale']) and hr.shape == hr_g.shape
-            _same_degradation(pooled.last_degradation, plain.last_degradation)        # it describes the batch that was GENERATED
+            same_draws(pooled.last_degradation, plain.last_degradation)        # it describes the batch that was GENERATED
             generated.append((lr_g, hr_g))
             yielded.append((lr, hr))
         assert len(yielded) == (epoch + 1) * len(plain)

@@ -9,14 +9,12 @@ import pytest
 import torch
 
 import poisson_ref as P
+from degrade_chain import blind2_by_hand, blind_by_hand, same_draws
+from guarded import _stream
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 64  # floats of NaN on either side of the output: a store outside the tensor shows
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def gpu_poisson(x, scale, gray, seed, dev, quantize=0):
@@ -193,66 +191,6 @@ def _loaders(dev, degradation, **kw):
     return initialize_device_datasets('synthetic:16', dev, batch_size=4, crop_size=96, seed=LOADER_SEED, degradation=degradation, **kw)[:2]
 
 
-def _noise_by_hand(x, deg, stage, seed, dev):
-    """One noise step from what the loader kept: the Poisson call when a sample of the stage drew it, then the Gaussian one."""
-    from torchsr_amd import _lib
-    from torchsr_amd import functional as F
-    pick = (lambda a: a) if stage is None else (lambda a: a[stage])
-    n, _, h, w = x.shape
-    scale, gray, sigma = pick(deg['poisson_scale']), pick(deg['gray']), pick(deg['sigma_n'])
-    assert ((scale > 0) != (sigma > 0)).all()                              # each sample has exactly one of the two
-    gd = torch.from_numpy(gray).to(dev)
-    if scale.any():
-        sd, levels, mid = torch.from_numpy(scale).to(dev), torch.empty((n, 8), dtype=torch.int32, device=dev), torch.empty_like(x)
-        _lib.call('srx_add_poisson_noise', x.data_ptr(), mid.data_ptr(), sd.data_ptr(), gd.data_ptr(), F.poisson_tables(dev).data_ptr(),
-                  levels.data_ptr(), seed & 0xFFFFFFFF, seed >> 32, n, h, w, 0, _stream())
-        x = mid
-    out = torch.empty_like(x)
-    _lib.call('srx_add_gaussian_noise', x.data_ptr(), out.data_ptr(), torch.from_numpy(sigma).to(dev).data_ptr(), gd.data_ptr(),
-              seed & 0xFFFFFFFF, seed >> 32, n, h, w, 1, _stream())
-    return out
-
-
-def blind_by_hand(hr, deg, dev):
-    from torchsr_amd import _lib
-    s, n = _stream(), hr.shape[0]
-    dv = {k: torch.from_numpy(deg[k]).to(dev) for k in ('parm', 'ksize', 'quality')}
-    a = torch.empty_like(hr)
-    b, d = (torch.empty((n, 3, 24, 24), device=dev) for _ in range(2))
-    _lib.call('srx_blur_aniso', hr.data_ptr(), a.data_ptr(), dv['parm'].data_ptr(), dv['ksize'].data_ptr(), n, 3, 96, 96, s)
-    _lib.call('srx_bicubic_down', a.data_ptr(), b.data_ptr(), n, 3, 96, 96, 4, 0, s)
-    c = _noise_by_hand(b, deg, None, deg['seed'], dev)
-    _lib.call('srx_jpeg_sim', c.data_ptr(), d.data_ptr(), dv['quality'].data_ptr(), n, 24, 24, 1, s)
-    return d
-
-
-def blind2_by_hand(hr, deg, dev):
-    """``by_hand`` of test_degrade2_gpu.py with the noise steps above."""
-    from torchsr_amd import _lib
-    from torchsr_amd import functional as F
-    s, n = _stream(), hr.shape[0]
-    dv = {k: torch.from_numpy(deg[k]).to(dev) for k in ('weights', 'ksize', 'quality')}
-    (s1, s2, lc), modes = deg['sizes'], deg['modes']
-
-    def filt(x, stage, quantize):
-        out = torch.empty_like(x)
-        _lib.call('srx_filter2d', x.data_ptr(), out.data_ptr(), dv['weights'][stage].data_ptr(), dv['ksize'][stage].data_ptr(), n, 3,
-                  x.shape[2], x.shape[3], quantize, s)
-        return out
-
-    def jpeg(x, stage):
-        out = torch.empty_like(x)
-        _lib.call('srx_jpeg_sim', x.data_ptr(), out.data_ptr(), dv['quality'][stage].data_ptr(), n, x.shape[2], x.shape[3], 1, s)
-        return out
-
-    with torch.no_grad():
-        x = jpeg(_noise_by_hand(F.resize(filt(hr, 0, 0), (s1, s1), modes[0]), deg, 0, deg['seed1'], dev), 0)
-        x = _noise_by_hand(F.resize(filt(x, 1, 0), (s2, s2), modes[1]), deg, 1, deg['seed2'], dev)
-        if deg['order'] == 'A':
-            return jpeg(filt(F.resize(x, (lc, lc), modes[2]), 2, 0), 1)
-        return filt(F.resize(jpeg(x, 1), (lc, lc), modes[2]), 2, 1)
-
-
 @pytest.mark.parametrize('prob', [0.5, 1.0])
 @pytest.mark.parametrize('degradation', ['blind', 'blind2'])
 def test_poisson_loader(dev, degradation, prob):
@@ -264,9 +202,7 @@ def test_poisson_loader(dev, degradation, prob):
         assert lr.shape == (4, 3, 24, 24) and torch.equal(hr, hr_p)        # the target is the plain loader's
         deg, deg_p = noisy.last_degradation, plain.last_degradation
         assert deg.keys() == deg_p.keys() | {'poisson_scale'}
-        for key in deg_p:
-            if key != 'sigma_n':
-                assert np.array_equal(deg[key], deg_p[key]) if isinstance(deg[key], np.ndarray) else deg[key] == deg_p[key], key
+        same_draws(deg, deg_p, but=('sigma_n', 'poisson_scale'))
         assert np.array_equal(deg['sigma_n'], np.where(deg['poisson_scale'] > 0, 0, deg_p['sigma_n']))
         assert torch.equal(lr, by_hand(hr, deg, dev))
         levels = lr.double() * 255

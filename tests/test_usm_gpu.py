@@ -9,24 +9,10 @@ import pytest
 import torch
 
 import usm_ref as U
+from degrade_chain import bicubic_by_hand, blind2_by_hand, blind_by_hand, same_draws, write_images
+from guarded import _band_kept, _guarded, _stream
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64  # floats of NaN on either side of every output: a store outside the tensor shows
-
-
-def _guarded(shape, dev):
-    n = int(np.prod(shape))
-    buf = torch.full((GUARD + n + GUARD,), float('nan'), device=dev)
-    return buf, buf[GUARD:GUARD + n].view(shape)
-
-
-def _band_kept(buf):
-    return bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[-GUARD:]).all())
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def gpu_usm(x, ksize, sigma, weight, threshold, dev):
@@ -153,96 +139,17 @@ def test_functional_usm_sharpen(dev):
 
 
 # ---------------------------------------------------------------------------------------------------------------- loader
-SIZES = [(120, 150), (97, 96), (200, 130), (96, 96), (140, 101), (60, 80), (128, 128), (110, 99), (100, 100), (150, 97)]
 LOADER_SEED = 1
 
 
 @pytest.fixture(scope='module')
 def image_dir(tmp_path_factory):
-    """The ten random PNGs of test_degrade2_gpu.py."""
-    from PIL import Image
-    d = tmp_path_factory.mktemp('usm') / 'imgs'
-    os.makedirs(d)
-    rng = np.random.RandomState(0)
-    for i, (h, w) in enumerate(SIZES):
-        Image.fromarray((rng.rand(h, w, 3) * 255).astype('uint8')).save(str(d / f'{i}.png'))
-    return str(d)
+    return write_images(tmp_path_factory.mktemp('usm') / 'imgs')
 
 
 def _loaders(image_dir, dev, degradation, **kw):
     from torchsr_amd.dataset import initialize_device_datasets
     return initialize_device_datasets(image_dir, dev, batch_size=4, crop_size=96, seed=LOADER_SEED, degradation=degradation, **kw)[:2]
-
-
-def bicubic_by_hand(hr, dev):
-    from torchsr_amd import _lib
-    lr = torch.empty((hr.shape[0], 3, 24, 24), device=dev)
-    _lib.call('srx_bicubic_down', hr.data_ptr(), lr.data_ptr(), hr.shape[0], 3, 96, 96, 4, 1, _stream())
-    return lr
-
-
-def blind_by_hand(hr, deg, dev):
-    """The four ABI calls of one ``blind`` batch, from what the loader kept."""
-    from torchsr_amd import _lib
-    s, n = _stream(), hr.shape[0]
-    dv = {k: torch.from_numpy(deg[k]).to(dev) for k in ('parm', 'ksize', 'sigma_n', 'gray', 'quality')}
-    a = torch.empty_like(hr)
-    b, c, d = (torch.empty((n, 3, 24, 24), device=dev) for _ in range(3))
-    _lib.call('srx_blur_aniso', hr.data_ptr(), a.data_ptr(), dv['parm'].data_ptr(), dv['ksize'].data_ptr(), n, 3, 96, 96, s)
-    _lib.call('srx_bicubic_down', a.data_ptr(), b.data_ptr(), n, 3, 96, 96, 4, 0, s)
-    _lib.call('srx_add_gaussian_noise', b.data_ptr(), c.data_ptr(), dv['sigma_n'].data_ptr(), dv['gray'].data_ptr(),
-              deg['seed'] & 0xFFFFFFFF, deg['seed'] >> 32, n, 24, 24, 1, s)
-    _lib.call('srx_jpeg_sim', c.data_ptr(), d.data_ptr(), dv['quality'].data_ptr(), n, 24, 24, 1, s)
-    return d
-
-
-def blind2_by_hand(hr, deg, dev):
-    """The chain of ABI / ``functional.resize`` calls of one ``blind2`` batch, from what the loader kept (``by_hand`` of
-    test_degrade2_gpu.py)."""
-    from torchsr_amd import _lib
-    from torchsr_amd import functional as F
-    s, n = _stream(), hr.shape[0]
-    dv = {k: torch.from_numpy(deg[k]).to(dev) for k in ('weights', 'ksize', 'sigma_n', 'gray', 'quality')}
-    (s1, s2, lc), modes = deg['sizes'], deg['modes']
-
-    def filt(x, stage, quantize):
-        out = torch.empty_like(x)
-        _lib.call('srx_filter2d', x.data_ptr(), out.data_ptr(), dv['weights'][stage].data_ptr(), dv['ksize'][stage].data_ptr(), n, 3,
-                  x.shape[2], x.shape[3], quantize, s)
-        return out
-
-    def noise(x, stage, seed):
-        out = torch.empty_like(x)
-        _lib.call('srx_add_gaussian_noise', x.data_ptr(), out.data_ptr(), dv['sigma_n'][stage].data_ptr(), dv['gray'][stage].data_ptr(),
-                  seed & 0xFFFFFFFF, seed >> 32, n, x.shape[2], x.shape[3], 1, s)
-        return out
-
-    def jpeg(x, stage):
-        out = torch.empty_like(x)
-        _lib.call('srx_jpeg_sim', x.data_ptr(), out.data_ptr(), dv['quality'][stage].data_ptr(), n, x.shape[2], x.shape[3], 1, s)
-        return out
-
-    with torch.no_grad():
-        a = filt(hr, 0, 0)
-        b = F.resize(a, (s1, s1), modes[0])
-        c = noise(b, 0, deg['seed1'])
-        d = jpeg(c, 0)
-        e = filt(d, 1, 0)
-        f = F.resize(e, (s2, s2), modes[1])
-        g = noise(f, 1, deg['seed2'])
-        assert tuple(d.shape) == (n, 3, s1, s1) and tuple(g.shape) == (n, 3, s2, s2)
-        if deg['order'] == 'A':
-            return jpeg(filt(F.resize(g, (lc, lc), modes[2]), 2, 0), 1)
-        return filt(F.resize(jpeg(g, 1), (lc, lc), modes[2]), 2, 1)
-
-
-def _same_draws(a, b):
-    assert a.keys() == b.keys()
-    for k in a:
-        if isinstance(a[k], np.ndarray):
-            assert np.array_equal(a[k], b[k]), k
-        else:
-            assert a[k] == b[k], k
 
 
 @pytest.mark.parametrize('degradation', ['bicubic', 'blind', 'blind2'])
@@ -260,9 +167,9 @@ def test_gt_usm_loader(dev, image_dir, degradation):
             assert float(lr.min()) >= 0 and float(lr.max()) <= 1 and float((levels - levels.round()).abs().max()) < 1e-4
             if degradation == 'bicubic':
                 assert usm.last_degradation is None
-                assert torch.equal(lr, bicubic_by_hand(hr, dev))
+                assert torch.equal(lr, bicubic_by_hand(hr, 4, dev))
             else:
-                _same_draws(usm.last_degradation, plain.last_degradation)                   # it consumed no random numbers
+                same_draws(usm.last_degradation, plain.last_degradation)                   # it consumed no random numbers
                 by_hand = blind_by_hand if degradation == 'blind' else blind2_by_hand
                 assert torch.equal(lr, by_hand(hr, usm.last_degradation, dev))
             assert not torch.equal(lr, lr_p)                                                # the degradation saw the sharpened crop

@@ -15,6 +15,8 @@ import torch
 from torch.utils.data import DataLoader, Dataset
 from torch.utils.data.distributed import DistributedSampler
 
+from . import functional as F
+
 SUPPORTED_IMAGES = ('.jpg', '.jpeg', '.png', '.bmp')  # dataset.py:29
 # how DeviceLoader makes a low-resolution train batch ('Blind degradation' and 'Second-order degradation')
 DEGRADATIONS = ('bicubic', 'blind', 'blind2')
@@ -76,6 +78,11 @@ class _Synthetic(Dataset):
         return lr, hr
 
 
+def _needs_blind(what: str, why: str, degradation: str) -> None:
+    if degradation not in ('blind', 'blind2'):
+        raise ValueError(f'DeviceLoader: {what} needs degradation blind or blind2 ({why}), got {degradation!r}')
+
+
 class DeviceLoader:
     """Train / test batches produced ON the MI355X.
 
@@ -94,7 +101,6 @@ class DeviceLoader:
     def __init__(self, images, device, batch_size: int, crop_size: int, upscale_factor: int, test: bool, seed: int,
                  multiplier: int = 1, rank: int = 0, world_size: int = 1, gt_usm: bool = False, pair_pool: int = 0,
                  jpeg420_prob: float = 0.0, poisson_prob: float = 0.0, degradation: str = 'bicubic'):
-        from . import _lib
         if degradation not in DEGRADATIONS:
             raise ValueError(f'DeviceLoader: degradation must be one of {DEGRADATIONS}, got {degradation!r}')
         if degradation in ('blind', 'blind2') and (crop_size <= 10 or crop_size % upscale_factor or (crop_size // upscale_factor) % 8):
@@ -113,30 +119,23 @@ class DeviceLoader:
         if gt_usm and crop_size <= 25:
             raise ValueError(f'DeviceLoader: gt_usm needs a crop of more than 25 pixels (the 51-tap unsharp mask reflects 25), '
                              f'got crop {crop_size}')
-        if isinstance(poisson_prob, bool) or not isinstance(poisson_prob, (int, float)) or not 0.0 <= poisson_prob <= 1.0:
-            raise ValueError(f'DeviceLoader: poisson_prob must be a number in [0, 1], got {poisson_prob!r}')
-        if poisson_prob > 0 and degradation not in ('blind', 'blind2'):
-            raise ValueError(f'DeviceLoader: poisson_prob needs degradation blind or blind2 (bicubic adds no noise), got '
-                             f'{degradation!r}')
-        if isinstance(jpeg420_prob, bool) or not isinstance(jpeg420_prob, (int, float)) or not 0.0 <= jpeg420_prob <= 1.0:
-            raise ValueError(f'DeviceLoader: jpeg420_prob must be a number in [0, 1], got {jpeg420_prob!r}')
-        if jpeg420_prob > 0 and degradation not in ('blind', 'blind2'):
-            raise ValueError(f'DeviceLoader: jpeg420_prob needs degradation blind or blind2 (bicubic has no JPEG stage), got '
-                             f'{degradation!r}')
+        for name, prob, why in (('poisson_prob', poisson_prob, 'bicubic adds no noise'),
+                                ('jpeg420_prob', jpeg420_prob, 'bicubic has no JPEG stage')):
+            if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 <= prob <= 1.0:
+                raise ValueError(f'DeviceLoader: {name} must be a number in [0, 1], got {prob!r}')
+            if prob > 0:
+                _needs_blind(name, why, degradation)
         if isinstance(pair_pool, bool) or not isinstance(pair_pool, int) or pair_pool < 0:
             raise ValueError(f'DeviceLoader: pair_pool must be a non-negative int (pairs in the pool; 0: off), got {pair_pool!r}')
         if pair_pool > 0:
             if test:
                 raise ValueError('DeviceLoader: pair_pool is for train loaders (a test loader yields its own batches)')
-            if degradation not in ('blind', 'blind2'):
-                raise ValueError(f'DeviceLoader: pair_pool needs degradation blind or blind2 (bicubic batches share no drawn '
-                                 f'parameters to mix), got {degradation!r}')
+            _needs_blind('pair_pool', 'bicubic batches share no drawn parameters to mix', degradation)
             if batch_size < 1 or pair_pool % batch_size:
                 b = max(batch_size, 1)
                 below, above = pair_pool // b * b, -(-pair_pool // b) * b
                 raise ValueError(f'DeviceLoader: pair_pool must be a multiple of the batch size {batch_size} (every step takes a whole '
                                  f'batch out of a full pool), got {pair_pool}; the nearest are {below}{"" if below else " (off)"} and {above}')
-        self._lib = _lib
         self.device, self.batch, self.crop, self.up, self.test = device, batch_size, crop_size, upscale_factor, test
         self.images = [self._fit(im).to(device) for im in images]          # uint8 [H][W][3]
         self.sizes = [(int(im.shape[0]), int(im.shape[1])) for im in self.images]
@@ -362,7 +361,6 @@ class DeviceLoader:
     def _pool(self, lr, hr):
         """A generated train batch through the pair pool: stored (while the pool fills) or exchanged in place for ``batch`` pooled
         pairs; returns ``(lr, hr)``, the tensors it was given.  The pool tensors are made at the first batch."""
-        from . import functional as F
         if self.pool_lr is None:
             self.pool_lr = torch.empty((self.pair_pool,) + tuple(lr.shape[1:]), dtype=torch.float32, device=lr.device)
             self.pool_hr = torch.empty((self.pair_pool,) + tuple(hr.shape[1:]), dtype=torch.float32, device=hr.device)
@@ -391,115 +389,69 @@ class DeviceLoader:
                 deg = self._draw_jpeg420(deg)
             yield idx, meta, deg
 
-    def _poisson(self, x, scale, gray_dev, seed, scale_dev=None):
-        """The Poisson half of a noise step: ``x`` with ``srx_add_poisson_noise(quantize=0)`` on the samples that drew it, under the
-        stage's seed; ``x`` itself -- and nothing is uploaded or launched -- when the batch has no ``poisson_scale`` (``scale`` is
-        None) or no sample of the stage drew Poisson.  The Gaussian call that follows adds exactly 0 to those samples (their sigma
-        is 0) and does the 8-bit rounding for all.  ``scale``: the stage's host array; ``gray_dev``: the grey flags on the device;
-        ``scale_dev``: the scales there, when the caller has already copied them."""
-        if scale is None or not scale.any():
-            return x
-        from . import functional as F
-        with torch.no_grad():
-            return F.add_poisson_noise(x, torch.from_numpy(scale).to(x.device) if scale_dev is None else scale_dev, gray_dev, seed)[0]
-
-    def _jpeg_params(self, deg, dev):
-        """``(quality, chroma420)`` of a batch on the device, shaped as drawn: the flags ride in the quality's copy, and are None
-        -- the batch then takes ``srx_jpeg_sim``, as a loader without ``jpeg420_prob`` does -- unless a sample drew 4:2:0."""
+    def _upload(self, deg, keys):
+        """The drawn tables of a batch on the device, shaped as drawn, in as few copies as the batch allows: one per key of ``keys``;
+        ``quality`` with the 4:2:0 flags riding in its copy -- ``chroma420`` is None, and the batch then takes ``srx_jpeg_sim`` as a
+        loader without ``jpeg420_prob`` does, unless a sample drew 4:2:0; ``poisson_scale``, every stage in one copy, only when a
+        sample drew Poisson (else None)."""
         import numpy as np
-        flags = deg.get('chroma420')
+        dev = self.device
+        t = {k: torch.from_numpy(deg[k]).to(dev) for k in keys}
+        flags, scale = deg.get('chroma420'), deg.get('poisson_scale')
         if flags is None or not flags.any():
-            return torch.from_numpy(deg['quality']).to(dev), None
-        both = torch.from_numpy(np.stack([deg['quality'], flags])).to(dev)
-        return both[0], both[1]
+            t['quality'], t['chroma420'] = torch.from_numpy(deg['quality']).to(dev), None
+        else:
+            t['quality'], t['chroma420'] = torch.from_numpy(np.stack([deg['quality'], flags])).to(dev)
+        t['poisson_scale'] = torch.from_numpy(scale).to(dev) if scale is not None and scale.any() else None
+        return t
 
-    def _jpeg(self, x, out, quality, flags, stream):
-        """One JPEG stage, 8-bit result: ``srx_jpeg_sim``, or ``srx_jpeg_sim2`` when the batch has 4:2:0 flags (``flags`` on the
-        device, else None).  The workspace is taken per call: torch's caching allocator hands the same block back."""
-        n, _, h, w = x.shape
-        if flags is None:
-            self._lib.call('srx_jpeg_sim', x.data_ptr(), out.data_ptr(), quality.data_ptr(), n, h, w, 1, stream)
-            return out
-        nbytes = self._lib.call('srx_jpeg_sim2_workspace', n, h, w)
-        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-        self._lib.call('srx_jpeg_sim2', x.data_ptr(), out.data_ptr(), quality.data_ptr(), flags.data_ptr(), n, h, w, 1,
-                       ws.data_ptr(), nbytes, None, stream)
-        return out
+    def _noise(self, x, deg, t, seed, stage=None):
+        """One noise stage, 8-bit result (``stage``: its row in the tables; None: they have one stage).  ``F.add_poisson_noise``,
+        unquantised, on the samples that drew it -- nothing is launched unless a sample of THIS stage did -- then
+        ``F.add_gaussian_noise``, which adds exactly 0 to those samples (their sigma is 0) and rounds all to 8 bits."""
+        at = (lambda a: a) if stage is None else (lambda a: a[stage])
+        gray = at(t['gray'])
+        if t['poisson_scale'] is not None and at(deg['poisson_scale']).any():
+            x = F.add_poisson_noise(x, at(t['poisson_scale']), gray, seed)[0]
+        return F.add_gaussian_noise(x, at(t['sigma_n']), gray, seed)
 
-    def _degrade(self, hr, deg, stream):
+    def _degrade(self, hr, deg):
         """``blind``: blur -> bicubic x1/scale (unquantised) -> Poisson or Gaussian noise -> 8 bits -> JPEG -> 8 bits."""
-        call, dev, n = self._lib.call, self.device, hr.shape[0]
-        lc = self.crop // self.up
-        on_dev = {k: torch.from_numpy(deg[k]).to(dev) for k in ('parm', 'ksize', 'sigma_n', 'gray')}
-        on_dev['quality'], flags = self._jpeg_params(deg, dev)
-        blurred = torch.empty_like(hr)
-        call('srx_blur_aniso', hr.data_ptr(), blurred.data_ptr(), on_dev['parm'].data_ptr(), on_dev['ksize'].data_ptr(),
-             n, 3, self.crop, self.crop, stream)
-        lr = torch.empty((n, 3, lc, lc), dtype=torch.float32, device=dev)
-        call('srx_bicubic_down', blurred.data_ptr(), lr.data_ptr(), n, 3, self.crop, self.crop, self.up, 0, stream)
-        noisy = torch.empty_like(lr)
-        lr = self._poisson(lr, deg.get('poisson_scale'), on_dev['gray'], deg['seed'])
-        call('srx_add_gaussian_noise', lr.data_ptr(), noisy.data_ptr(), on_dev['sigma_n'].data_ptr(), on_dev['gray'].data_ptr(),
-             deg['seed'] & 0xFFFFFFFF, deg['seed'] >> 32, n, lc, lc, 1, stream)
-        return self._jpeg(noisy, lr, on_dev['quality'], flags, stream)
+        t = self._upload(deg, ('parm', 'ksize', 'sigma_n', 'gray'))
+        lr = F.bicubic_down(F.blur_aniso(hr, t['parm'], t['ksize']), self.up, False)
+        return F.jpeg_sim(self._noise(lr, deg, t, deg['seed']), t['quality'], t['chroma420'])
 
-    def _degrade2(self, hr, deg, stream):
+    def _degrade2(self, hr, deg):
         """``blind2``: filter -> resize -> noise -> JPEG, twice, the second JPEG and the final sinc filter around the resize to
         the low-resolution size in either order ('Second-order degradation')."""
-        from . import functional as F
-        call, dev, n = self._lib.call, self.device, hr.shape[0]
-        weights = torch.from_numpy(deg['weights']).to(dev)  # the three tables in one copy
-        ksize, sigma_n, gray = (torch.from_numpy(deg[k]).to(dev) for k in ('ksize', 'sigma_n', 'gray'))
-        quality, flags = self._jpeg_params(deg, dev)
+        t = self._upload(deg, ('weights', 'ksize', 'sigma_n', 'gray'))  # the three weight tables in one copy
         (s1, s2, lc), modes = deg['sizes'], deg['modes']
-        pscale = deg.get('poisson_scale')
-        if pscale is not None and pscale.any():
-            pscale = (pscale, torch.from_numpy(pscale).to(dev))  # both stages in one copy, and only when a sample drew Poisson
 
         def filt(x, stage, quantize):
-            out = torch.empty_like(x)
-            call('srx_filter2d', x.data_ptr(), out.data_ptr(), weights[stage].data_ptr(), ksize[stage].data_ptr(), n, 3,
-                 x.shape[2], x.shape[3], quantize, stream)
-            return out
-
-        def noise(x, stage, seed):
-            out = torch.empty_like(x)
-            if isinstance(pscale, tuple):
-                x = self._poisson(x, pscale[0][stage], gray[stage], seed, pscale[1][stage])
-            call('srx_add_gaussian_noise', x.data_ptr(), out.data_ptr(), sigma_n[stage].data_ptr(), gray[stage].data_ptr(),
-                 seed & 0xFFFFFFFF, seed >> 32, n, x.shape[2], x.shape[3], 1, stream)
-            return out
+            return F.filter2d(x, t['weights'][stage], t['ksize'][stage], quantize)
 
         def jpeg(x, stage):
-            return self._jpeg(x, torch.empty_like(x), quality[stage], None if flags is None else flags[stage], stream)
+            return F.jpeg_sim(x, t['quality'][stage], None if t['chroma420'] is None else t['chroma420'][stage])
 
         with torch.no_grad():
-            x = jpeg(noise(F.resize(filt(hr, 0, 0), (s1, s1), modes[0]), 0, deg['seed1']), 0)
-            x = noise(F.resize(filt(x, 1, 0), (s2, s2), modes[1]), 1, deg['seed2'])
+            x = jpeg(self._noise(F.resize(filt(hr, 0, False), (s1, s1), modes[0]), deg, t, deg['seed1'], 0), 0)
+            x = self._noise(F.resize(filt(x, 1, False), (s2, s2), modes[1]), deg, t, deg['seed2'], 1)
             if deg['order'] == 'A':
-                return jpeg(filt(F.resize(x, (lc, lc), modes[2]), 2, 0), 1)
-            return filt(F.resize(jpeg(x, 1), (lc, lc), modes[2]), 2, 1)
+                return jpeg(filt(F.resize(x, (lc, lc), modes[2]), 2, False), 1)
+            return filt(F.resize(jpeg(x, 1), (lc, lc), modes[2]), 2, True)
 
     def __iter__(self):
-        call, dev = self._lib.call, self.device
         for idx, meta, deg in self._plan():
-            ptrs = torch.tensor([self.images[i].data_ptr() for i in idx], dtype=torch.int64).to(dev)
-            meta_t = torch.tensor(meta, dtype=torch.int32).to(dev)
-            stream = torch.cuda.current_stream().cuda_stream
-            hr = torch.empty((len(idx), 3, self.crop, self.crop), dtype=torch.float32, device=dev)
-            call('srx_crop_flip_u8', ptrs.data_ptr(), meta_t.data_ptr(), hr.data_ptr(), len(idx), self.crop, stream)
+            hr = F.crop_flip([self.images[i] for i in idx], meta, self.crop)
             if self.gt_usm and not self.test:
-                from . import functional as F
                 with torch.no_grad():
                     hr = F.usm_sharpen(hr)
             if deg is not None:
                 self.last_degradation = deg
-                lr = (self._degrade2 if self.degradation == 'blind2' else self._degrade)(hr, deg, stream)
+                lr = (self._degrade2 if self.degradation == 'blind2' else self._degrade)(hr, deg)
                 yield self._pool(lr, hr) if self.pair_pool else (lr, hr)
                 continue
-            lc = self.crop // self.up
-            lr = torch.empty((len(idx), 3, lc, lc), dtype=torch.float32, device=dev)
-            call('srx_bicubic_down', hr.data_ptr(), lr.data_ptr(), len(idx), 3, self.crop, self.crop, self.up, 1, stream)
+            lr = F.bicubic_down(hr, self.up, True)
             if self.test:  # the bicubic up-sampled image of TestData (dataset.py:175-190): only ever displayed
                 bic = torch.nn.functional.interpolate(lr, size=(self.crop, self.crop), mode='bicubic',
                                                       align_corners=False).clamp(0, 1)
