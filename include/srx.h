@@ -832,6 +832,38 @@ int srx_maxpool2x2_bwd(const float* dy, const float* x, float* dx, int N, int H,
 /* max-pool backward followed by the backward of the ReLU that produced x (conv, ReLU, MaxPool in cfg 'E') */
 int srx_maxpool2x2_relu_bwd(const float* dy, const float* x, float* dx, int N, int H, int W, int C, void* stream);
 
+/* ------------------------------------------- multi-layer perceptual loss (csrc/percep.hip) */
+/* Real-ESRGAN's perceptual loss (BasicSR PerceptualLoss: conv1_2, conv2_2, conv3_4, conv4_4, conv5_4 of VGG19 BEFORE their ReLU,
+ * ImageNet-normalised inputs, weighted L1).  In cfg 'E' every tap but the last sits in front of a max-pool, and ReLU and max
+ * commute (maxpool(relu(x)) == relu(maxpool(x))), so a tap conv writes its pre-activation once and the pool applies the ReLU.
+ * These are the streaming kernels around the taps; the convs are the stack's own.  No floating-point atomics, fixed grids and
+ * fixed reduction trees: every result is a fixed function of its arguments.  `void*` tensors are fp32 or bf16 as their flag says. */
+/* out[0:N] = (src - mean) * inv_std, out[N:2N] = the same of tgt (tgt NULL: a batch of N); [.,H,W,4] images, channel 3 written as 0.
+ * The product is formed in fp64 and rounded once. */
+int srx_normalize_pair_nhwc4(const float* src, const float* tgt, float* out, int N, int H, int W, const float mean[3],
+                             const float inv_std[3], void* stream);
+/* dsrc = dout * inv_std per channel (dout: the first N images' gradient), channel 3 written as 0 */
+int srx_normalize_nhwc4_bwd(const float* dout, float* dsrc, int N, int H, int W, const float inv_std[3], void* stream);
+/* y = relu(maxpool2x2(x)): x fp32 [N_tot][H][W][C] pre-ReLU, y [N_tot][H/2][W/2][C] fp32 or bf16 (the maximum is chosen on the fp32
+ * values and rounded once).  partial != NULL (needs N_tot == 2 * N_src): a workgroup takes sample i together with sample i + N_src
+ * and writes partial[workgroup] = its sum of |x[i] - x[i + N_src]| over the windows it loaded; srx_tap_blocks workgroups. */
+int srx_tap_blocks(int N_src, int H, int W, int C);
+int srx_maxpool2x2_relu_fwd_tap(const float* x, void* y, int y_is_bf16, int N_src, int N_tot, int H, int W, int C, float* partial,
+                                void* stream);
+/* loss[0] = (accumulate ? loss[0] : 0) + (float)(scale * sum(partial[0:n_partial])); the sum is an fp64 tree of one workgroup */
+int srx_tap_l1_finalize(const float* partial, int n_partial, double scale, float* loss, int accumulate, void* stream);
+/* the tap without a pool behind it, and taps against precomputed target features:
+ * loss[0] = (accumulate ? loss[0] : 0) + weight * mean|a - b|; n a multiple of 4, ws >= 1024 floats */
+int srx_tap_l1_fwd(const float* a, const float* b, int64_t n, double weight, float* loss, int accumulate, float* ws, void* stream);
+/* dx = poolrelu_bwd(dy; x_src) + coef * gscale[0] * sign(x_src - x_tgt): the first term is srx_maxpool2x2_relu_bwd's on the
+ * pre-ReLU x_src (gradient to the first maximum in scan order when that maximum is > 0), the second srx_l1_bwd's (sign(0) = 0).
+ * dy [N_src][H/2][W/2][C], x_src, x_tgt fp32 and dx [N_src][H][W][C]; bf16 forms: the sum is formed in fp32 and rounded once. */
+int srx_maxpool2x2_relu_bwd_tap(const void* dy, int dy_is_bf16, const float* x_src, const float* x_tgt, void* dx, int dx_is_bf16,
+                                float coef, const float* gscale, int N_src, int H, int W, int C, void* stream);
+/* g = coef * gscale[0] * sign(fs - ft): the gradient entering at the last tap; n a multiple of 4 */
+int srx_tap_l1_bwd_top(const float* fs, const float* ft, void* g, int g_is_bf16, float coef, const float* gscale, int64_t n,
+                       void* stream);
+
 /* ------------------------------------------------------------------ linear */
 /* nn.Linear (srgan/discriminator.py:65,67; esrgan/discriminator.py:73,75).
  * x [B][K], w [J][K] (reference layout), y [B][J] = act(x w^T + bias)

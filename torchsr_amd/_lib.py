@@ -12,7 +12,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('SRX_LIB') or os.path.join(CSRC, 'libsrx_hip.so')  # SRX_LIB: developer A/B builds on one GPU box
-SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'degrade.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip', 'resample.hip', 'usm.hip', 'pool.hip', 'colorfix.hip', 'compact.hip', 'specnorm.hip', 'unshuffle.hip']
+SOURCES = ['api.cpp', 'gconv.hip', 'wgrad.hip', 'convpack.hip', 'c64.hip', 'thin9.hip', 'rdb.hip', 'thin.hip', 'rowtile.hip', 'augment.hip', 'degrade.hip', 'norm.hip', 'eltwise.hip', 'linear.hip', 'loss.hip', 'head.hip', 'wino.hip', 'optim.hip', 'dihedral.hip', 'resample.hip', 'usm.hip', 'pool.hip', 'colorfix.hip', 'compact.hip', 'specnorm.hip', 'unshuffle.hip', 'percep.hip']
 # headers the sources include, relative to CSRC: part of the build's digest and of every object's cache key
 HEADERS = ['srx_common.h', 'conv_host.h', os.path.join('..', '..', 'include', 'srx.h')]
 
@@ -327,9 +327,17 @@ _SIGS = {
     'srx_spectral_norm_ws_floats': (_Z, [_I, _I]),
     'srx_spectral_norm_fwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     'srx_spectral_norm_bwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    'srx_normalize_pair_nhwc4': (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P]),
+    'srx_normalize_nhwc4_bwd': (_I, [_P, _P, _I, _I, _I, C.POINTER(_F), _P]),
+    'srx_tap_blocks': (_I, [_I, _I, _I, _I]),
+    'srx_maxpool2x2_relu_fwd_tap': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    'srx_tap_l1_finalize': (_I, [_P, _I, C.c_double, _P, _I, _P]),
+    'srx_tap_l1_fwd': (_I, [_P, _P, _L, C.c_double, _P, _I, _P, _P]),
+    'srx_maxpool2x2_relu_bwd_tap': (_I, [_P, _I, _P, _P, _P, _I, _F, _P, _I, _I, _I, _I, _P]),
+    'srx_tap_l1_bwd_top': (_I, [_P, _P, _P, _I, _F, _P, _L, _P]),
 }
 # functions whose int return value is data, not a status
-_UNCHECKED = {'srx_wino_applicable', 'srx_wino_infer_applicable', 'srx_conv3x3_bf16s_applicable', 'srx_wino_stat_rows', 'srx_conv2d_bwd_data_bn_rows', 'srx_conv2d_fwd_bn_in_ok', 'srx_conv2d_bwd_data_bn_in_ok', 'srx_pack_table_bytes', 'srx_version', 'srx_last_error', 'srx_device_cus', 'srx_plan_cus', 'srx_prof_stop', 'srx_conv2d_stat_rows', 'srx_bn_stat_rows', 'srx_bn_rows_per_block', 'srx_plane_moments_blocks'}
+_UNCHECKED = {'srx_wino_applicable', 'srx_wino_infer_applicable', 'srx_conv3x3_bf16s_applicable', 'srx_wino_stat_rows', 'srx_conv2d_bwd_data_bn_rows', 'srx_conv2d_fwd_bn_in_ok', 'srx_conv2d_bwd_data_bn_in_ok', 'srx_pack_table_bytes', 'srx_version', 'srx_last_error', 'srx_device_cus', 'srx_plan_cus', 'srx_prof_stop', 'srx_conv2d_stat_rows', 'srx_bn_stat_rows', 'srx_bn_rows_per_block', 'srx_plane_moments_blocks', 'srx_tap_blocks'}
 
 EXPORTS = tuple(_SIGS.keys())
 

@@ -38,6 +38,16 @@ class ESRGANTrainer(SRGANTrainer):
         self.pixel_loss = F.l1_loss
         self.bce_loss = F.bce_with_logits
 
+    def _perceptual_loss(self):
+        """``--perceptual single``: the reference's ``VGGLoss``; ``realesrgan``: Real-ESRGAN's five-layer pre-ReLU term
+        under the same name and call (it holds no trainable parameter and no state either)."""
+        if self.perceptual == 'realesrgan':
+            from ..realesrgan.loss import PerceptualLoss
+            return PerceptualLoss(weights=self.vgg_weights)
+        if self.perceptual != 'single':
+            raise RuntimeError(f'perceptual loss "{self.perceptual}" not supported. Please choose from: single, realesrgan')
+        return super()._perceptual_loss()
+
     def _phase_disc(self) -> None:
         """esrgan/trainer.py:444-455 (optimizer step is issued by ``_phase_gen`` after the all-reduce)."""
         self._phase_disc_gen()

@@ -2129,6 +2129,242 @@ def frozen_conv_stack(source: Tensor, target: Optional[Tensor], layers):
     return _FrozenConvStack.apply(source, target, layers, *weights)
 
 
+def _bf16_tap_stack_ok(layers, taps, shape) -> bool:
+    """``_bf16_stack_ok`` for a stack whose tap convs carry no activation of their own (``_FrozenTapStack``): the same
+    conditions on the same descriptors, a tap's ReLU being the pool's."""
+    if _dev.NO_BF16S or len(layers) < 2 or layers[0][0] != 'conv' or layers[-1][0] != 'conv' or layers[1][0] != 'conv':
+        return False
+    L = _lib.lib()
+    n, h, w, _c = shape
+    for i, (kind, conv) in enumerate(layers):
+        if kind == 'pool':
+            if layers[i - 1][0] != 'conv' or layers[i + 1][0] != 'conv' or h % 2 or w % 2:
+                return False
+            h, w = h // 2, w // 2
+            continue
+        st = conv._st
+        if st.precision != 1 or st.act != (ACT_NONE if i in taps else ACT_RELU) or st.stride != 1 or st.shuffle or st.k != 3 or st.pad != 1:
+            return False
+        if i == 0:
+            if st.cin > 4 or st.cout != 64:
+                return False
+        elif L.srx_conv3x3_bf16s_applicable(C.byref(st.desc(n, h, w))) != 1:
+            return False
+    return True
+
+
+def _tap_stack_check(layers, taps) -> None:
+    """The shape ``_FrozenTapStack`` is built for (VGG19 cfg 'E' with Real-ESRGAN's taps): 3x3 / stride 1 convs with a fused ReLU,
+    except the taps, which write their pre-activation and are the last layer or sit in front of a pool; every pool behind a tap."""
+    last = len(layers) - 1
+    if not layers or layers[0][0] != 'conv' or 0 in taps or last not in taps or any(i < 0 or i > last for i in taps):
+        raise RuntimeError('tap_stack: the stack starts with a conv that is no tap and ends with a tap')
+    for i, (kind, conv) in enumerate(layers):
+        if kind == 'pool':
+            if i - 1 not in taps:
+                raise RuntimeError('tap_stack: every pool follows a tap conv (the pool applies that tap\'s ReLU)')
+            continue
+        st = conv._st
+        if st.stride != 1 or st.shuffle or st.act != (ACT_NONE if i in taps else ACT_RELU):
+            raise RuntimeError('tap_stack: stride-1 convs, act NONE at the taps and a fused ReLU everywhere else')
+        if i in taps and i != last and layers[i + 1][0] != 'pool':
+            raise RuntimeError('tap_stack: a tap is the last layer or sits in front of a pool')
+
+
+def _tap_stack_run(x: Tensor, n_src: int, layers, taps, tfeats, loss: Optional[Tensor], need_bwd: bool):
+    """The forward launches of ``_FrozenTapStack`` on the normalised batch ``x`` (``[source; target]`` when it holds
+    ``2 * n_src`` images).  ``loss`` given: every tap's ``weight * mean|fs - ft|`` is accumulated into it, ``ft`` being the target
+    half or ``tfeats[k]``.  Returns ``(saved, plan, bf16s)``: every layer's input and the last output, as ``_FrozenConvStack``."""
+    L, s = _lib.lib(), _stream()
+    pair = x.shape[0] == 2 * n_src
+    bf16s = _bf16_tap_stack_ok(layers, taps, x.shape)
+    act16 = torch.bfloat16 if bf16s else torch.float32
+    ws = _ws(1024, x) if loss is not None else None
+    saved, plan, k, first = [x], [], 0, 1
+
+    def tap_l1(a: Tensor, b: Tensor, weight: float) -> None:
+        nonlocal first
+        if a.shape != b.shape:
+            raise RuntimeError(f'tap_stack: target feature of shape {tuple(b.shape)}, the tap has {tuple(a.shape)}')
+        call('srx_tap_l1_fwd', _p(a), _p(b), a.numel(), weight, _p(loss), 0 if first else 1, _p(ws), s)
+        first = 0
+
+    for i, (kind, conv) in enumerate(layers):
+        n, h, w, c = x.shape
+        if kind == 'pool':                                  # x: the fp32 pre-activation of the tap conv below
+            y = torch.empty((n, h // 2, w // 2, c), dtype=act16, device=x.device)
+            fused = loss is not None and pair
+            call('srx_maxpool2x2_relu_fwd_tap', _p(x), _p(y), 1 if bf16s else 0, n_src, n, h, w, c, _p(ws) if fused else None, s)
+            if fused:
+                call('srx_tap_l1_finalize', _p(ws), L.srx_tap_blocks(n_src, h, w, c), taps[i - 1] / float(n_src * h * w * c), _p(loss),
+                     0 if first else 1, s)
+                first = 0
+            elif loss is not None:
+                tap_l1(x[:n_src], tfeats[k], taps[i - 1])
+            k += 1
+            plan.append(('pool', None, None))
+        else:
+            st = conv._st
+            d = st.desc(n, h, w)
+            dref = C.byref(d)
+            tap = i in taps
+            to_f32 = tap or not bf16s
+            y = torch.empty(st.out_shape(n, h, w), dtype=torch.float32 if to_f32 else torch.bfloat16, device=x.device)
+            b = None if conv.bias is None else _chk(conv.bias.detach(), 'tap_stack.bias')
+            if bf16s and i == 0:   # the 3 -> 64 first layer: fp32 image in, its own kernel
+                st.pack(conv.weight, d)
+                call('srx_conv2d_fwd_first3_to_bf16', dref, _p(x), _p(st.wpk_fwd), _p(b), _p(y), s)
+                plan.append(('conv', st, None))
+            elif bf16s:
+                st.pack_bf16s(conv.weight, d, need_bwd)
+                nws = L.srx_conv3x3_bf16s_ws_floats(dref, 0)
+                cws = _ws(nws, x) if nws else None
+                call('srx_conv3x3_bf16s_fwd', dref, _p(x), _p(st.bf16s_fwd), _p(b), 0 if tap else 1, _p(y), 0 if to_f32 else 1, _p(cws),
+                     nws, s)
+                plan.append(('conv', st, None))
+            elif wino_layer_ok(st, d):
+                st.pack_wino(conv.weight, d, need_bwd=need_bwd)
+                _wino_fwd(d, x, st.wino_fwd, b, y, None, s)
+                plan.append(('conv', st, ('wino', st.wino_bwd)))
+            else:
+                st.pack(conv.weight, d)
+                _conv_fwd(d, _p(x), _p(st.wpk_fwd), _p(b), _p(y), x, s)
+                plan.append(('conv', st, st.wpk_bwd))
+        saved.append(y)
+        x = y
+    if loss is not None:
+        tap_l1(x[:n_src], x[n_src:] if pair else tfeats[k], taps[len(layers) - 1])
+    return saved, plan, bf16s
+
+
+class _FrozenTapStack(Function):
+    """Real-ESRGAN's perceptual loss (BasicSR ``PerceptualLoss``: L1 on five VGG19 layers BEFORE their ReLU, ImageNet-normalised
+    inputs) as ONE autograd node that returns the scalar ``sum_k w_k * mean|fs_k - ft_k|``; the feature tensors never leave it.
+
+    In cfg 'E' the taps are the last conv in front of each pool plus the last conv, and ``maxpool(relu(x)) == relu(maxpool(x))``
+    bit for bit: a tap conv writes its pre-activation (epilogue act NONE), the pool behind it applies the ReLU after the maximum
+    and sums ``|fs - ft|`` over the windows it has loaded anyway (``srx_maxpool2x2_relu_fwd_tap``); the other convs keep their
+    fused ReLU.  The convs, their plans and the choice between the fp32 path (Winograd where ``wino_layer_ok``) and the
+    bf16-storage path are ``_FrozenConvStack``'s; there the tap layers are exactly the ones that write fp32.
+
+    Backward, source half only: the loss gradient enters at the last tap (``srx_tap_l1_bwd_top``), descends through the same
+    data-gradient calls with the non-tap ReLUs folded, and every pool backward adds its tap's L1 gradient in the same pass
+    (``srx_maxpool2x2_relu_bwd_tap``)."""
+
+    @staticmethod
+    def forward(ctx, source: Tensor, target: Optional[Tensor], layers, taps, mean, inv_std, tfeats, *weights):
+        ctx.set_materialize_grads(False)
+        source = _chk(source, 'tap_stack.source')
+        n, h, w, c = source.shape
+        if c != 4:
+            raise RuntimeError(f'tap_stack: NHWC images with 4 stored channels, got {c}')
+        if target is not None:
+            target = _chk(target, 'tap_stack.target')
+            if target.shape != source.shape:
+                raise RuntimeError(f'tap_stack: target of shape {tuple(target.shape)}, source {tuple(source.shape)}')
+        x = torch.empty((n if target is None else 2 * n, h, w, 4), dtype=torch.float32, device=source.device)
+        call('srx_normalize_pair_nhwc4', _p(source), _p(target), _p(x), n, h, w, mean, inv_std, _stream())
+        loss = torch.empty((), dtype=torch.float32, device=source.device)
+        saved, ctx.plan, ctx.bf16s = _tap_stack_run(x, n, layers, taps, tfeats, loss, ctx.needs_input_grad[0])
+        ctx.n_src, ctx.taps, ctx.inv_std, ctx.n_feats = n, taps, inv_std, 0 if tfeats is None else len(tfeats)
+        ctx.masters = [conv.weight if kind == 'conv' else None for kind, conv in layers]
+        ctx.save_for_backward(*saved, *(tfeats or ()))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        if g is None or not ctx.needs_input_grad[0]:
+            return (None,) * len(ctx.needs_input_grad)
+        plan, n, taps, bf16s = ctx.plan, ctx.n_src, ctx.taps, ctx.bf16s
+        saved = ctx.saved_tensors[:len(plan) + 1]
+        tfeats = ctx.saved_tensors[len(plan) + 1:]
+        L, s = _lib.lib(), _stream()
+        gscale = _chk(g, 'tap_stack.grad')
+        k = len(taps) - 1                          # the tap whose L1 term enters next, topmost first
+
+        def target_of(feat: Tensor) -> Tensor:     # the other operand of tap k: the batch's second half, or the precomputed one
+            return tfeats[k] if ctx.n_feats else feat[n:]
+
+        top = saved[-1]
+        fs = top[:n]
+        g = torch.empty(fs.shape, dtype=torch.bfloat16 if bf16s else torch.float32, device=fs.device)
+        call('srx_tap_l1_bwd_top', _p(fs), _p(target_of(top)), _p(g), 1 if bf16s else 0, taps[len(plan) - 1] / float(fs.numel()),
+             _p(gscale), fs.numel(), s)
+        for i in range(len(plan) - 1, -1, -1):
+            kind, st, wpk_bwd = plan[i]
+            x = saved[i][:n]                       # this layer's input (source half: batch-major, so a prefix)
+            _, h, w, c = x.shape
+            if kind == 'pool':                     # x: the fp32 pre-activation of tap i - 1
+                k -= 1
+                dx = torch.empty(x.shape, dtype=g.dtype, device=x.device)
+                call('srx_maxpool2x2_relu_bwd_tap', _p(g), 1 if bf16s else 0, _p(x), _p(target_of(saved[i])), _p(dx), 1 if bf16s else 0,
+                     taps[i - 1] / float(x.numel()), _p(gscale), n, h, w, c, s)
+                g = dx
+                continue
+            d = st.desc(n, h, w)
+            fold = i > 0 and plan[i - 1][0] == 'conv'   # x = relu(conv below), never a tap: fold that ReLU's backward in
+            if not bf16s:
+                wino = isinstance(wpk_bwd, tuple)
+                g, _ = _layer_dgrad(st, d, ctx.masters[i], wino, wpk_bwd[1] if wino else None, None if wino else wpk_bwd, g, x,
+                                    plan[i - 1][1] if fold else None, s)
+            elif i == 0:
+                dx = torch.empty_like(x)
+                _conv_dgrad(d, _p(g), _p(st.wpk_bwd), _p(dx), x, s)
+                g = dx
+            else:
+                dref = C.byref(d)
+                to_f32 = i == 1                    # the first layer's data gradient (3-channel kernel) reads fp32
+                dx = torch.empty(x.shape, dtype=torch.float32 if to_f32 else torch.bfloat16, device=x.device)
+                nws = L.srx_conv3x3_bf16s_ws_floats(dref, 1)
+                ws = _ws(nws, dx) if nws else None
+                call('srx_conv3x3_bf16s_bwd_data', dref, _p(g), _p(st.bf16s_bwd), _p(x) if fold else None, _p(dx), 0 if to_f32 else 1,
+                     _p(ws), nws, s)
+                g = dx
+        dsrc = torch.empty_like(g)
+        call('srx_normalize_nhwc4_bwd', _p(g), _p(dsrc), n, g.shape[1], g.shape[2], ctx.inv_std, s)
+        return (dsrc,) + (None,) * (len(ctx.needs_input_grad) - 1)
+
+
+def _tap_stack_args(layers, taps, mean, std):
+    weights = [p for _, m in layers if m is not None for p in (m.weight, m.bias) if p is not None]
+    if any(p.requires_grad for p in weights):
+        raise RuntimeError('frozen_tap_stack: the stack must be frozen (requires_grad = False on every parameter)')
+    taps = {int(i): float(wt) for i, wt in taps.items()}
+    _tap_stack_check(layers, taps)
+    f3 = C.c_float * 3
+    return weights, taps, f3(*[float(m) for m in mean]), f3(*[1.0 / float(v) for v in std])
+
+
+def frozen_tap_stack(source: Tensor, target: Optional[Tensor], layers, taps, mean, std, target_features=None) -> Tensor:
+    """``sum_k taps[i_k] * mean|f_k(source) - f_k(target)|`` over the pre-activation outputs ``f_k`` of the convs at positions
+    ``i_k`` of ``layers`` ([('conv', layers.Conv2d) | ('pool', None)]), both images normalised by ``mean`` / ``std`` first.
+    ``target`` None: ``target_features`` holds the taps' precomputed target features (``frozen_tap_features``), shallow to deep."""
+    weights, taps, mean, inv_std = _tap_stack_args(layers, taps, mean, std)
+    if (target is None) == (target_features is None):
+        raise RuntimeError('frozen_tap_stack: pass either target or target_features')
+    tfeats = None
+    if target_features is not None:
+        tfeats = [_chk(t, 'tap_stack.target_features') for t in target_features]
+        if len(tfeats) != len(taps):
+            raise RuntimeError(f'frozen_tap_stack: {len(taps)} taps, {len(tfeats)} target features')
+    return _FrozenTapStack.apply(source, target, layers, taps, mean, inv_std, tfeats, *weights)
+
+
+@torch.no_grad()
+def frozen_tap_features(image: Tensor, layers, taps, mean, std):
+    """The taps' pre-activation features of ``image`` (a detached target), shallow to deep: ``frozen_tap_stack``'s forward
+    launches on a batch of its own, no loss and no autograd state."""
+    _, taps, mean, inv_std = _tap_stack_args(layers, taps, mean, std)
+    image = _chk(image, 'tap_stack.image')
+    n, h, w, c = image.shape
+    if c != 4:
+        raise RuntimeError(f'tap_stack: NHWC images with 4 stored channels, got {c}')
+    x = torch.empty_like(image)
+    call('srx_normalize_pair_nhwc4', _p(image), None, _p(x), n, h, w, mean, inv_std, _stream())
+    saved, _, _ = _tap_stack_run(x, n, layers, taps, None, None, False)
+    return [saved[i + 1] for i in sorted(taps)]
+
+
 # --------------------------------------------------------------------------- linear
 class _Linear(Function):
     @staticmethod

@@ -169,6 +169,7 @@ class SRGANTrainer:
         self.main_process = args.rank in [-1, 0]
         self.use_graphs = bool(getattr(args, 'use_graphs', True))
         self.vgg_weights = getattr(args, 'vgg_weights', None)
+        self.perceptual = getattr(args, 'perceptual', None) or 'single'  # train --perceptual (ESRGAN and compact trainers)
         self.clip_grad_norm = getattr(args, 'clip_grad_norm', None)
         self.skip_nonfinite_steps = bool(getattr(args, 'skip_nonfinite_steps', False))
         # issue the gradient all-reduces even at world size 1 (a one-GPU rehearsal of the RCCL path)
@@ -246,7 +247,14 @@ class SRGANTrainer:
         self.mse_loss = F.mse_loss
         self.pixel_loss = F.mse_loss  # pre-training objective (trainer.py:384)
         self.bce_loss = F.bce_loss
-        self.vgg_loss = VGGLoss(weights=self.vgg_weights).to(self.device)
+        self.vgg_loss = self._perceptual_loss().to(self.device)
+
+    def _perceptual_loss(self):
+        """The content term's module (``train --perceptual``): here the reference's single-layer ``VGGLoss`` only."""
+        if self.perceptual != 'single':
+            raise RuntimeError(f'perceptual loss "{self.perceptual}" is not available with this model: the SRGAN trainer keeps '
+                               'the reference\'s single-layer VGG loss')
+        return VGGLoss(weights=self.vgg_weights)
 
     def _initialize_optimizers(self) -> None:
         """trainer.py:167-196: three Adam states, two StepLR (epochs // 8, gamma 0.6)."""

@@ -130,6 +130,12 @@ def parse_args(argv=None) -> Namespace:
                             'loss (one logit per crop).  unet: Real-ESRGAN\'s UNetDiscriminatorSN -- a U-Net with spectral '
                             'normalisation and no BatchNorm that returns a logit per pixel -- trained with the plain GAN loss, '
                             'adversarial weight 0.1; --model esrgan and --model compact, one GPU')
+    train.add_argument('--perceptual', type=str, default='single', choices=('single', 'realesrgan'),
+                       help='the content term of the GAN phase.  single: the reference\'s L1 on VGG19 relu5_4 of the raw images.  '
+                            'realesrgan: Real-ESRGAN\'s perceptual loss -- L1 on conv1_2, conv2_2, conv3_4, conv4_4 and conv5_4 '
+                            'before their ReLU, weighted 0.1, 0.1, 1, 1, 1, on ImageNet-normalised images -- as one fused node; '
+                            '--model esrgan and --model compact, with either --discriminator.  The term\'s weight in the '
+                            'generator loss stays 1')
     train.add_argument('--pretrain-epochs', type=int, default=PRE_EPOCHS)
     train.add_argument('--psnr-checkpoint', type=str, default=None)
     train.add_argument('--seed', type=int, default=0)
@@ -214,6 +220,9 @@ def parse_args(argv=None) -> Namespace:
     if args.function == 'train' and args.discriminator == 'unet' and args.model.lower() not in ('esrgan', 'compact'):
         parser.error(f'--discriminator unet trains with --model esrgan or --model compact; --model {args.model} keeps its own '
                      'discriminator')
+    if args.function == 'train' and args.perceptual == 'realesrgan' and args.model.lower() not in ('esrgan', 'compact'):
+        parser.error(f'--perceptual realesrgan trains with --model esrgan or --model compact; --model {args.model} keeps the '
+                     'reference\'s single-layer VGG loss')
     if args.function == 'train' and args.poisson_noise_prob > 0 and not (args.device_data and args.degradation in ('blind', 'blind2')):
         parser.error('--poisson-noise-prob replaces the Gaussian noise of a blind degradation: add --device-data and '
                      '--degradation blind or --degradation blind2')
