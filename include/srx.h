@@ -970,6 +970,14 @@ int srx_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t 
                           float beta2, float eps, float grad_scale, int64_t* step,
                           const srx_grad_guard_t* state, void* stream);
 
+/* Exponential moving average of a flat parameter buffer, in place on `ema` (Real-ESRGAN's
+ * ema_decay):  ema[i] = decay * ema[i] + one_minus_decay * p[i]  for i in [0, n), fp32, two products
+ * and one sum, each rounded once (never contracted into an fma).  The caller forms one_minus_decay in
+ * double and rounds it once.  decay == 0 copies p bit for bit.  One launch, 16-byte accesses.
+ * Refused: null pointers, n <= 0, ema or p not 16-byte aligned, ema == p, a decay outside [0, 1) or
+ * not finite, a one_minus_decay outside (0, 1] or not finite. */
+int srx_ema_update(float* ema, const float* p, int64_t n, float decay, float one_minus_decay, void* stream);
+
 /* Spectral normalisation of a weight W [rows][cols] (a conv's [Cout][Cin * KH * KW]), the semantics of
  * torch.nn.utils.spectral_norm with n_power_iterations = 1 and eps = 1e-12.
  *   train != 0:  v <- W^T u / max(|W^T u|, eps);  u <- W v / max(|W v|, eps)   (u, v updated in place)

@@ -324,6 +324,7 @@ _SIGS = {
     'srx_grad_guard_ws_bytes': (_Z, [_L]),
     'srx_grad_guard': (_I, [_P, _L, _F, _F, _I, _P, _Z, _P, _P]),
     'srx_adam_step_guarded': (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _P, _P, _P]),
+    'srx_ema_update': (_I, [_P, _P, _L, _F, _F, _P]),
     'srx_spectral_norm_ws_floats': (_Z, [_I, _I]),
     'srx_spectral_norm_fwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     'srx_spectral_norm_bwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),

@@ -18,8 +18,29 @@ class CompactTrainer(ESRGANTrainer):
     gen_tail_bucket = f'body.{tail_index(NUM_CONV)}.weight'
 
     def __init__(self, device, args, *rest, **kw) -> None:
-        num_conv = int(getattr(args, 'num_conv', None) or NUM_CONV)
+        self._num_conv_given = getattr(args, 'num_conv', None)  # None: the default, or the depth of --init-generator's file
+        self._set_num_conv(int(self._num_conv_given or NUM_CONV))
+        super().__init__(device, args, *rest, **kw)
+
+    def _set_num_conv(self, num_conv: int) -> None:
         if num_conv != NUM_CONV:  # (instance attributes: the class keeps describing the default network)
             self.generator_cls = functools.partial(Generator, num_conv=num_conv)
             self.gen_tail_bucket = f'body.{tail_index(num_conv)}.weight'
-        super().__init__(device, args, *rest, **kw)
+
+    def _init_generator_state(self, path: str) -> dict:
+        """``train --init-generator``: every SRVGGNetCompact file ``test --weights`` takes; the depth is the file's."""
+        from ..test import compact_num_conv, load_generator_state
+        state = load_generator_state(path)
+        depth = compact_num_conv(state)
+        if self._num_conv_given is not None and int(self._num_conv_given) != depth:
+            raise RuntimeError(num_conv_conflict(int(self._num_conv_given), depth, path))
+        self.__dict__.pop('generator_cls', None)
+        self.__dict__.pop('gen_tail_bucket', None)
+        self._set_num_conv(depth)
+        return state
+
+
+def num_conv_conflict(given: int, depth: int, path: str) -> str:
+    """The message for a ``--num-conv`` that disagrees with ``--init-generator``'s file (the command line and the trainer)."""
+    return (f'--num-conv {given} does not fit --init-generator {path}, which holds {depth} body convs: drop --num-conv (the '
+            f'depth is read off the file) or pass --num-conv {depth}')

@@ -177,7 +177,41 @@ inline int64_t stream_blocks(int64_t n) {
   return blocks;
 }
 
+// ---- generator weight average ---------------------------------------------------------------------------------------------
+// ema = d * ema + (1 - d) * p over a flat parameter buffer, in place on ema (srx_axpby's pointers are __restrict__: it may not
+// run in place).  Two products and one sum, each rounded once -- the intrinsics keep the compiler from contracting them into an
+// fma, so the bits are a function of the operands alone.  Three streams of 4n bytes; shaped like axpby_kernel.
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t n,
+                                                         float d, float omd) {
+  const int64_t n4 = n / 4;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    f32x4 ev = *reinterpret_cast<const f32x4*>(ema + i * 4);
+    const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ev[e] = __fadd_rn(__fmul_rn(d, ev[e]), __fmul_rn(omd, pv[e]));
+    *reinterpret_cast<f32x4*>(ema + i * 4) = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const int64_t i = n4 * 4 + threadIdx.x;
+    ema[i] = __fadd_rn(__fmul_rn(d, ema[i]), __fmul_rn(omd, p[i]));
+  }
+}
+
 }  // namespace
+
+extern "C" int srx_ema_update(float* ema, const float* p, int64_t n, float decay, float one_minus_decay, void* stream) {
+  SRX_REQUIRE(ema && p && n > 0, "ema_update: bad argument (null pointer or n <= 0)");
+  SRX_REQUIRE(((uintptr_t)ema % 16 == 0) && ((uintptr_t)p % 16 == 0), "ema_update: buffers must be 16-byte aligned");
+  SRX_REQUIRE((const float*)ema != p, "ema_update: ema and p are the same buffer (the average is a buffer of its own)");
+  SRX_REQUIRE(isfinite(decay) && decay >= 0.f && decay < 1.f, "ema_update: decay must be in [0, 1), got %g", (double)decay);
+  SRX_REQUIRE(isfinite(one_minus_decay) && one_minus_decay > 0.f && one_minus_decay <= 1.f,
+              "ema_update: one_minus_decay must be in (0, 1], got %g", (double)one_minus_decay);
+  hipStream_t st = srx_stream(stream);
+  SRX_LAUNCH_PROF("ema_update_kernel", 0.0, ema_update_kernel, dim3((unsigned)stream_blocks(n)), dim3(256), 0, st, ema, p, n,
+                  decay, one_minus_decay);
+  SRX_CHECK_LAUNCH("ema_update_kernel");
+  return SRX_OK;
+}
 
 extern "C" int srx_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* lr, float beta1,
                              float beta2, float eps, float grad_scale, int64_t* step, void* stream) {

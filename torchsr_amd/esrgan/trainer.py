@@ -12,6 +12,8 @@ flat Adam, bucketed RCCL gradient exchange); differences follow the reference:
   the discriminator and VGG19 all multiply bf16-rounded operands with fp32 accumulation in both
   phases (``amp_phases``; BASELINE config 4).  ``--disable-amp`` gives exact fp32.
 """
+import functools
+
 import torch
 
 from .. import functional as F
@@ -30,6 +32,21 @@ class ESRGANTrainer(SRGANTrainer):
     discriminator_cls = Discriminator
     amp_phases = ('psnr', 'gan')          # esrgan/trainer.py:384 and :446,461
     gen_tail_bucket = 'upsample1.weight'  # data parallel: upsample1/2, conv3, conv4 gradients complete first
+    finetune = True
+
+    def _init_generator_state(self, path: str) -> dict:
+        """``train --init-generator``: every RRDBNet file ``test --weights`` takes, in either published naming or this package's;
+        the generator is built at the file's depth (23 blocks, or 6 for the anime model).  An x2 file is refused."""
+        from ..rrdbnet import rrdbnet_geometry, rrdbnet_to_generator_state
+        from ..test import load_generator_state
+        state = rrdbnet_to_generator_state(load_generator_state(path))
+        num_blocks, scale = rrdbnet_geometry(state)
+        if scale != 4:
+            raise RuntimeError(f'--init-generator {path}: an x{scale} RRDBNet file; x{scale} is inference-only here '
+                               '(test --weights runs it), the training path is x4')
+        cls = self.generator_cls  # (instance attribute: the class keeps describing the default network)
+        self.generator_cls = functools.partial(getattr(cls, 'func', cls), num_rrdb_blocks=num_blocks)
+        return state
 
     def _initialize_loss(self) -> None:
         """esrgan/trainer.py:159-165."""
@@ -79,7 +96,7 @@ class ESRGANTrainer(SRGANTrainer):
         # :466 -- the 4th NHWC channel is zero on both sides: the mean runs over the 3 real ones
         pixel = self.l1_loss(self._super_res, self._high4, count=self._high4.numel() // 4 * 3)
         content = self.vgg_loss.forward_nhwc(self._super_res, self._high4)       # :467
-        self._content = F.axpby(pixel, content, 0.01, 1.0)
+        self._content = F.axpby(pixel, content, self.pixel_weight, 1.0)  # train --pixel-weight: 0.01 (:469), Real-ESRGAN 1.0
         self._losses['gan/pixel-loss'] = pixel.detach()
         self._losses['gan/content-loss'] = content.detach()
 

@@ -158,6 +158,78 @@ class FlatAdam:
         self.set_lr(sd['lr'])
 
 
+class FlatEMA:
+    """Exponential moving average of a :class:`FlatParams` buffer (Real-ESRGAN's ``ema_decay``): ``update()`` is one launch,
+    ``ema <- decay * ema + (1 - decay) * p`` in fp32 over the whole flat buffer (``srx_ema_update``).  The alignment gaps are 0
+    in both buffers and stay 0.  ``data`` is allocated once, here: a captured graph holds its address.  ``1 - decay`` is formed
+    in double and rounded once, on its way into the call.
+
+    ``pack_epoch`` is the staleness counter of a module whose parameters are views into ``data`` (``shadow``): nothing bumps it
+    per step -- whoever evaluates that module bumps it first (``refresh``)."""
+
+    def __init__(self, flat: FlatParams, decay: float):
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:  # (also NaN)
+            raise ValueError(f'FlatEMA: decay must be in [0, 1), got {decay}')
+        self.flat, self.decay, self.one_minus_decay = flat, decay, 1.0 - decay
+        self.data = flat.data.clone()
+        self.pack_epoch = [0]
+
+    @torch.no_grad()
+    def reset(self) -> None:
+        """Start the average again from the weights as they are now."""
+        self.data.copy_(self.flat.data)
+        self.pack_epoch[0] += 1
+
+    @torch.no_grad()
+    def update(self) -> None:
+        call('srx_ema_update', self.data.data_ptr(), self.flat.data.data_ptr(), self.flat.numel, self.decay,
+             self.one_minus_decay, torch.cuda.current_stream().cuda_stream)
+
+    def refresh(self) -> None:
+        """Before an evaluation of ``shadow``'s module: its packed weights are as old as the last one."""
+        self.pack_epoch[0] += 1
+
+    def shadow(self, module: nn.Module) -> nn.Module:
+        """A never-trained copy of ``module`` (the one ``flat`` was built from) whose parameters are views into the average, in
+        eval mode; its convs follow ``pack_epoch``, not the optimiser's counter."""
+        import copy
+        twin = copy.deepcopy(module).to(self.data.device)  # (a conv's __deepcopy__ builds its copy on the host)
+        twin.__dict__.pop('_folded', None)  # (inference caches of the original point at the original's layers)
+        params = [p for p in twin.parameters() if p.requires_grad]
+        if [p.shape for p in params] != [p.shape for p in self.flat.params]:
+            raise RuntimeError('FlatEMA.shadow: the module is not the one this buffer was built from')
+        for p, o in zip(params, self.flat.offsets):
+            p.data = self.data[o:o + p.numel()].view(p.shape)
+        for m in twin.modules():
+            st = getattr(m, '_st', None)
+            if isinstance(st, F.ConvState):
+                st.model_epoch = self.pack_epoch
+        return twin.eval()
+
+    def state_dict(self, module: nn.Module) -> dict:
+        """The averaged weights under ``module``'s own key names, on the CPU (a buffer, which has no average, as it is)."""
+        where = self.flat.offsets_by_name(module)
+        out = {}
+        for k, v in module.state_dict().items():
+            src = self.data[where[k]:where[k] + v.numel()].view(v.shape) if k in where else v
+            out[k] = src.detach().clone().cpu()
+        return out
+
+    @torch.no_grad()
+    def load_state_dict(self, module: nn.Module, sd) -> None:
+        where = self.flat.offsets_by_name(module)
+        shapes = {k: v.shape for k, v in module.named_parameters()}
+        missing = sorted(set(where) - set(sd))
+        if missing:
+            raise RuntimeError(f'FlatEMA.load_state_dict: the averaged weights lack {missing[:4]} ...')
+        for k, o in where.items():
+            if tuple(sd[k].shape) != tuple(shapes[k]):
+                raise RuntimeError(f'FlatEMA.load_state_dict: {k} has shape {tuple(sd[k].shape)}, expected {tuple(shapes[k])}')
+            self.data[o:o + sd[k].numel()].copy_(sd[k].reshape(-1))
+        self.pack_epoch[0] += 1
+
+
 class StepLR:
     """torch.optim.lr_scheduler.StepLR(step_size, gamma) as used at torchsr/srgan/trainer.py:186-195.
 

@@ -37,7 +37,7 @@ from .. import _dev
 from .. import functional as F
 from ..ddp import BackwardCuts, GradBuckets, broadcast_module
 from ..layers import no_weight_grad, set_conv_precision
-from ..optim import FlatAdam, FlatParams, StepLR
+from ..optim import FlatAdam, FlatEMA, FlatParams, StepLR
 from .discriminator import Discriminator
 from .generator import Generator
 from .loss import VGGLoss
@@ -53,6 +53,41 @@ def save_image(tensor: Tensor, path: str) -> None:
     from PIL import Image
     img = tensor.detach()[0].clamp(0, 1).mul(255).add(0.5).clamp(0, 255).permute(1, 2, 0).to('cpu', torch.uint8)
     Image.fromarray(img.numpy()).save(path)
+
+
+def check_discriminator_keys(discriminator, state, source: str, advice) -> None:
+    """``state`` must hold exactly ``discriminator``'s keys.  A U-Net state for the VGG-style critic, or the reverse, is refused
+    with both kinds named; ``source`` says where the state came from and ``advice(kind of the state)`` what to do about it."""
+    have, want = set(state), set(discriminator.state_dict())
+    if have == want:
+        return
+    kind = lambda keys: 'unet' if any(k.endswith('.weight_orig') for k in keys) else 'vgg'  # noqa: E731
+    raise RuntimeError(f'{source} holds a "{kind(have)}" discriminator, this run trains a "{kind(want)}" one: {advice(kind(have))}'
+                       if kind(have) != kind(want) else
+                       f'{source}\'s discriminator does not fit this run\'s: keys {sorted(have ^ want)[:4]} ... differ')
+
+
+def load_discriminator_init(discriminator, path: str) -> None:
+    """``train --init-discriminator``: a bare state_dict, Real-ESRGAN's ``{"params": ...}`` / ``{"params_ema": ...}`` (the
+    published ``*_netD.pth`` files) or the ``resume.discriminator`` entry of one of this package's checkpoints, loaded
+    strictly (every key, ``weight_u`` / ``weight_v`` included; DDP's ``module.`` prefix is dropped)."""
+    ckpt = torch.load(path, map_location='cpu')
+    state = ckpt
+    if isinstance(ckpt, dict):
+        if isinstance(ckpt.get('resume'), dict) and isinstance(ckpt['resume'].get('discriminator'), dict):
+            state = ckpt['resume']['discriminator']
+        else:
+            for key in ('params', 'params_ema'):
+                if isinstance(ckpt.get(key), dict):
+                    state = ckpt[key]
+                    break
+    if not isinstance(state, dict) or not all(torch.is_tensor(v) for v in state.values()):
+        raise RuntimeError(f'--init-discriminator {path}: no discriminator state_dict in it (a bare state_dict, {{"params": ...}}, '
+                           f'{{"params_ema": ...}} or one of this package\'s checkpoints with a "resume" entry)')
+    state = {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in state.items()}
+    check_discriminator_keys(discriminator, state, f'the --init-discriminator file {path}',
+                             lambda kind: f'train with --discriminator {kind} (or give a "{"vgg" if kind == "unet" else "unet"}" file)')
+    discriminator.load_state_dict(state, strict=True)
 
 
 class LossRing:
@@ -131,9 +166,12 @@ class SRGANTrainer:
     epochs, gan_checkpoint, local_rank, pretrain_epochs, psnr_checkpoint, skip_image_save,
     world_size, rank``.  Optional extras: ``use_graphs`` (default True), ``vgg_weights``, ``clip_grad_norm`` (float or
     None) and ``skip_nonfinite_steps`` (bool): the gradient guard of all three optimisers (``optim.FlatAdam``), off by default.
+    The ESRGAN and compact trainers also read ``init_generator`` / ``init_discriminator`` (paths), ``ema_decay`` (float in
+    [0, 1) or None) and ``pixel_weight`` (float or None: 0.01) -- fine-tuning, DESIGN.md section 3 "Fine-tuning and EMA".
     """
 
     phase_prefix = 'srgan'
+    finetune = False  # --init-generator / --init-discriminator / --ema-decay / --pixel-weight: the ESRGAN and compact trainers
     # single-graph GAN step: the perceptual loss's BACKWARD on the side stream too (``_gan_all``).  Exact here -- two gradients meet
     # at the generator's output and a two-term sum has one rounding whatever its order
     deep_overlap = True
@@ -178,6 +216,17 @@ class SRGANTrainer:
         # (ddp.configure_comm decides; 0 at world size 1) and an optional rehearsal hook around those windows
         self.comm_reserved_cus = int(getattr(args, 'comm_reserved_cus', 0) or 0)
         self.comm_window_hook = getattr(args, 'comm_window_hook', None)
+        # fine-tuning (ESRGAN and compact trainers; all off by default): files the models start from, the decay of the
+        # generator's weight average, and the weight of the GAN phase's L1 term
+        self.init_generator = getattr(args, 'init_generator', None)
+        self.init_discriminator = getattr(args, 'init_discriminator', None)
+        self.ema_decay = getattr(args, 'ema_decay', None)
+        pixel_weight = getattr(args, 'pixel_weight', None)
+        self.pixel_weight = 0.01 if pixel_weight is None else float(pixel_weight)
+        if not self.finetune and (self.init_generator or self.init_discriminator or self.ema_decay is not None
+                                  or pixel_weight is not None):
+            raise RuntimeError('--init-generator, --init-discriminator, --ema-decay and --pixel-weight train with --model esrgan '
+                               'or --model compact; the SRGAN generator has BatchNorm buffers, which have no average defined')
         if self.device.type != 'cuda':
             raise RuntimeError('torchsr_amd trains on an MI355X (device "cuda"); there is no CPU path')
         if self.device.index is None:
@@ -198,6 +247,8 @@ class SRGANTrainer:
         self._ring = LossRing(self.device, self.wandb_flush_every) \
             if (wandb and self.main_process and getattr(wandb, 'run', None) is not None) else None
         F.direct_grads[0] = True  # parameter gradients accumulate straight into the flat .grad views
+        # read (and checked) before anything is built: the generator takes its depth from its file
+        self._init_gen_state = self._init_generator_state(self.init_generator) if self.init_generator else None
         self._initialize_trainer()
         self._create_test_image()
 
@@ -229,11 +280,24 @@ class SRGANTrainer:
         """trainer.py:136-157.  DDP wrapping is replaced by flat buffers + explicit all-reduce."""
         self.generator = self.generator_cls().to(self.device)
         self.discriminator = self.discriminator_cls().to(self.device)
+        if self._init_gen_state is not None:
+            self.generator.load_state_dict(self._init_gen_state)
+            self._init_gen_state = None
+        if self.init_discriminator:
+            load_discriminator_init(self.discriminator, self.init_discriminator)
         if self.distributed:
             broadcast_module(self.generator)
             broadcast_module(self.discriminator)
         self.gen_flat = FlatParams(self.generator)
         self.disc_flat = FlatParams(self.discriminator)
+        if self.init_generator or self.init_discriminator:
+            F.bump_pack_epoch()
+        # the generator's weight average and the copy of the generator that validates it: allocated here, once, before any
+        # capture; (re)started from the weights or a checkpoint's average wherever a phase loads one (_restore_ema)
+        self.gen_ema = self.ema_generator = None
+        if self.ema_decay is not None:
+            self.gen_ema = FlatEMA(self.gen_flat, self.ema_decay)
+            self.ema_generator = self.gen_ema.shadow(self.generator)
         # gradient buckets in parameter order: [0] = the body (complete LAST in the backward pass), [1] = the slice
         # autograd completes first (the generator's sub-pixel tail, the discriminator's classifier)
         force = self.force_collectives
@@ -328,28 +392,29 @@ class SRGANTrainer:
         keys are written here (the reference loads these files unchanged) plus a ``resume`` entry with
         everything else a run needs to continue where it stopped."""
         cpu = lambda sd: {k: (v.detach().clone().cpu() if torch.is_tensor(v) else v) for k, v in sd.items()}  # noqa: E731
-        return {'epoch': epoch, 'phase': phase, 'state': cpu(self.generator.state_dict()),
-                'resume': {'discriminator': cpu(self.discriminator.state_dict()),
-                           'psnr_optimizer': cpu(self.psnr_optimizer.state_dict()),
-                           'gen_optimizer': cpu(self.gen_optimizer.state_dict()),
-                           'disc_optimizer': cpu(self.disc_optimizer.state_dict()),
-                           'gen_scheduler': self.gen_scheduler.state_dict(),
-                           'disc_scheduler': self.disc_scheduler.state_dict(),
-                           'best_psnr': self.best_psnr,
-                           'rng': torch.get_rng_state(), 'cuda_rng': torch.cuda.get_rng_state(self.device)}}
+        state = {'epoch': epoch, 'phase': phase, 'state': cpu(self.generator.state_dict()),
+                 'resume': {'discriminator': cpu(self.discriminator.state_dict()),
+                            'psnr_optimizer': cpu(self.psnr_optimizer.state_dict()),
+                            'gen_optimizer': cpu(self.gen_optimizer.state_dict()),
+                            'disc_optimizer': cpu(self.disc_optimizer.state_dict()),
+                            'gen_scheduler': self.gen_scheduler.state_dict(),
+                            'disc_scheduler': self.disc_scheduler.state_dict(),
+                            'best_psnr': self.best_psnr,
+                            'rng': torch.get_rng_state(), 'cuda_rng': torch.cuda.get_rng_state(self.device)}}
+        if self.gen_ema is not None:
+            # the averaged weights under the generator's key names (what Real-ESRGAN publishes; ``test --ema`` and a resumed
+            # run read them); 'state' stays the live weights.  Without --ema-decay the file's keys are the four above
+            state['params_ema'] = self.gen_ema.state_dict(self.generator)
+        return state
 
     def _restore_resume_state(self, checkpoint: Optional[dict]) -> bool:
         """Everything beyond the generator, when the checkpoint was written by this package."""
+        self._restore_ema(checkpoint)  # (the generator's weights were loaded before this call)
         extra = (checkpoint or {}).get('resume')
         if not extra:
             return False
-        have, want = set(extra['discriminator']), set(self.discriminator.state_dict())
-        if have != want:
-            kind = lambda keys: 'unet' if any(k.endswith('.weight_orig') for k in keys) else 'vgg'  # noqa: E731
-            raise RuntimeError(f'the checkpoint holds a "{kind(have)}" discriminator, this run trains a "{kind(want)}" one: resume '
-                               f'with --discriminator {kind(have)} (or without the checkpoint)'
-                               if kind(have) != kind(want) else
-                               f'the checkpoint\'s discriminator does not fit this run\'s: keys {sorted(have ^ want)[:4]} ... differ')
+        check_discriminator_keys(self.discriminator, extra['discriminator'], 'the checkpoint',
+                                 lambda kind: f'resume with --discriminator {kind} (or without the checkpoint)')
         self.discriminator.load_state_dict(extra['discriminator'])
         for name in ('psnr_optimizer', 'gen_optimizer', 'disc_optimizer', 'gen_scheduler', 'disc_scheduler'):
             getattr(self, name).load_state_dict(extra[name])
@@ -368,6 +433,36 @@ class SRGANTrainer:
             ckpt['state'] = {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in state.items()}
             return ckpt
         return None
+
+    def _init_generator_state(self, path: str) -> dict:
+        """``train --init-generator``: the file's state in the generator's key names, read through ``test --weights``'s
+        functions; a trainer that fine-tunes sets ``generator_cls`` to the file's depth here.  Not this trainer."""
+        raise RuntimeError('--init-generator trains with --model esrgan or --model compact')
+
+    def _restore_ema(self, checkpoint: Optional[dict]) -> None:
+        """After a checkpoint's weights were loaded: its average when it holds one, else the average starts at the weights."""
+        if self.gen_ema is None:
+            return
+        average = (checkpoint or {}).get('params_ema')
+        if average:
+            self.gen_ema.load_state_dict(self.generator, {(k[len('module.'):] if k.startswith('module.') else k): v
+                                                          for k, v in average.items()})
+        else:
+            self.gen_ema.reset()
+
+    def _init_unused(self, path: str) -> None:
+        """One line when a phase resumes from a checkpoint of its own although init files were given."""
+        given = [f'{flag} {value}' for flag, value in (('--init-generator', self.init_generator),
+                                                       ('--init-discriminator', self.init_discriminator)) if value]
+        if given:
+            self._log(f'Resuming from {path}: {" and ".join(given)} not used')
+
+    def _gen_step(self, optimizer: FlatAdam) -> None:
+        """A generator update: the Adam step and, with --ema-decay, the one launch that moves the average (also on a step the
+        gradient guard skipped: the launch sequence of a captured step stays static, and the weights did not move)."""
+        optimizer.step()
+        if self.gen_ema is not None:
+            self.gen_ema.update()
 
     def _exec(self, key: str, fn: Callable[[], None]) -> None:
         """Run ``fn`` eagerly (first two calls: warm-up) and from then on as a replayed hipGraph."""
@@ -491,7 +586,7 @@ class SRGANTrainer:
                 self._exec('psnr.body', lambda: self._resume('g.tail'))       # residual tower backward
                 self.gen_sync.launch(0)
                 self.gen_sync.wait()
-                self._exec('psnr.opt', lambda: (self.psnr_optimizer.step(), self._push_loss('psnr/train-loss')))
+                self._exec('psnr.opt', lambda: (self._gen_step(self.psnr_optimizer), self._push_loss('psnr/train-loss')))
             except BaseException:
                 self.gen_sync.abort()  # a bucket may be on the wire with compute units reserved for it: give them back
                 raise
@@ -499,7 +594,7 @@ class SRGANTrainer:
                 F.cut_hook[0] = None
                 self._cuts.clear()
         else:
-            self._exec('psnr.all', lambda: (self._pretrain_body(), self.psnr_optimizer.step(),
+            self._exec('psnr.all', lambda: (self._pretrain_body(), self._gen_step(self.psnr_optimizer),
                                             self._push_loss('psnr/train-loss')))
         self._end_step()
         if self._ring is not None:
@@ -512,8 +607,10 @@ class SRGANTrainer:
         self._log('Starting pre-training')
         epoch = 1
         path = self.psnr_checkpoint or f'{self.phase_prefix}-psnr-latest.pth'
-        checkpoint = self._load_checkpoint(path)
+        # (a run that starts from --init-generator and pre-trains for no epoch has no pre-training phase to resume)
+        checkpoint = None if (self.init_generator and self.pre_epochs < 1) else self._load_checkpoint(path)
         if checkpoint:
+            self._init_unused(path)
             self.generator.load_state_dict(checkpoint['state'])
             F.bump_pack_epoch()
             epoch = checkpoint['epoch']
@@ -592,7 +689,7 @@ class SRGANTrainer:
             self._phase_disc()
             self._phase_content()
             self._phase_gen()
-            self.gen_optimizer.step()                                        # :469
+            self._gen_step(self.gen_optimizer)                                # :469
             self._push_loss('gan/train-loss')
             return
         # Two branches of ONE captured graph.  The perceptual loss (trainer.py:455) needs the generator's output and the
@@ -636,7 +733,7 @@ class SRGANTrainer:
             sr_v.grad.record_stream(main)
             with F.deferred_weight_grads():
                 sr.backward(sr_d.grad + sr_v.grad)
-        self.gen_optimizer.step()                                            # :469
+        self._gen_step(self.gen_optimizer)                                    # :469
         self._push_loss('gan/train-loss')
 
     def _side_stream(self):
@@ -670,7 +767,7 @@ class SRGANTrainer:
                 self._exec('gan.gen.body', self._phase_gen_body)
                 self.gen_sync.launch(0)
                 self.gen_sync.wait()
-                self._exec('gan.gopt', lambda: (self.gen_optimizer.step(), self._push_loss('gan/train-loss')))
+                self._exec('gan.gopt', lambda: (self._gen_step(self.gen_optimizer), self._push_loss('gan/train-loss')))
             except BaseException:
                 # (OOM, an error in user code inside a segment) buckets may be on the wire and compute units reserved for
                 # RCCL's channels: without this every later plan and captured graph would be cut for a smaller chip
@@ -699,17 +796,22 @@ class SRGANTrainer:
         self._log('Starting training loop')
         epoch = 1
         self.best_psnr = -1.0
-        checkpoint = self._load_checkpoint(self.gan_checkpoint or f'{self.phase_prefix}-gan-latest.pth')
+        path = self.gan_checkpoint or f'{self.phase_prefix}-gan-latest.pth'
+        checkpoint = self._load_checkpoint(path)
         if checkpoint:
+            self._init_unused(path)
             self.generator.load_state_dict(checkpoint['state'])
             epoch = checkpoint['epoch']
             if self._restore_resume_state(checkpoint):
                 epoch += 1  # the checkpoint is written AFTER its epoch: continue with the next one
                             # (the reference re-runs the saved epoch, trainer.py:483-497)
-        else:
+        elif not (self.init_generator and self.pre_epochs < 1):
+            # (with --init-generator and no pre-training epoch the generator IS the init file: a -psnr-latest.pth that lies
+            # around belongs to another run)
             checkpoint = self._load_checkpoint(f'{self.phase_prefix}-psnr-latest.pth')
             if checkpoint:
                 self.generator.load_state_dict(checkpoint['state'])
+                self._restore_ema(checkpoint)  # this run's own pre-training wrote its average there: it continues
         F.bump_pack_epoch()
         step = 0
         for epoch in range(epoch, self.epochs + 1):
@@ -739,6 +841,13 @@ class SRGANTrainer:
         checkpoints, monitor image."""
         self._enter_phase('test')
         self.generator.eval()
+        generator = self.generator
+        if self.gen_ema is not None:
+            # with --ema-decay the averaged weights are what is validated, kept as best / latest and shown, as in Real-ESRGAN:
+            # a copy of the generator whose parameters are views into the average (eval mode, this phase's fp32); its packed
+            # weights are as old as the last evaluation
+            self.gen_ema.refresh()
+            generator = self.ema_generator
         self._log(f'Testing results after epoch {epoch}')
         with torch.no_grad():
             loss, psnr, batches = 0.0, 0.0, 0
@@ -746,7 +855,7 @@ class SRGANTrainer:
             for low_res, _, high_res in self.test_loader:
                 low_res = low_res.to(self.device)
                 high_res = high_res.to(self.device)
-                super_res = self.generator(low_res)
+                super_res = generator(low_res)
                 mse = self.mse_loss(super_res, high_res).item()
                 psnr += 10 * log10(1 / mse)                                   # :296
                 loss += mse
@@ -769,7 +878,7 @@ class SRGANTrainer:
             if self.main_process:
                 torch.save(self._model_state(epoch, phase), f'{phase}-latest.pth')
             if self.save_image and self.main_process:
-                super_res = self.generator(self.test_image)
+                super_res = generator(self.test_image)
                 save_image(super_res, f'output/SR_epoch{epoch}.png')
                 if wandb and getattr(wandb, 'run', None) is not None:        # :337-343, at 1/4 size
                     _, _, height, width = super_res.shape

@@ -29,12 +29,18 @@ MAX_TILE_PIXELS = 600 * 1000  # LR pixels per tile (x16 HR pixels must stay < 2^
 TRUNK_MAX_PIXELS = 8 * 1000 * 1000  # LR pixels the staged path runs untiled (x256 floats of the sub-pixel conv < 2^31)
 
 
-def load_generator_state(path: str) -> OrderedDict:
+def load_generator_state(path: str, ema: bool = False) -> OrderedDict:
     """The generator's state_dict from a checkpoint: this package's ``{"epoch", "phase", "state"}``, Real-ESRGAN's
-    ``{"params_ema": ...}`` (preferred) or ``{"params": ...}``, or a bare state_dict; DDP's ``module.`` prefix is dropped."""
+    ``{"params_ema": ...}`` (preferred) or ``{"params": ...}``, or a bare state_dict; DDP's ``module.`` prefix is dropped.
+    ``ema`` (``test --ema``): the averaged weights ``params_ema`` -- which a checkpoint of ``train --ema-decay`` holds next to
+    its live ``state`` -- or a ``RuntimeError`` that names the file's keys when it has none."""
     ckpt = torch.load(path, map_location='cpu')
     state = ckpt
-    for key in ('state', 'params_ema', 'params'):
+    if ema and not (isinstance(ckpt, dict) and isinstance(ckpt.get('params_ema'), dict)):
+        keys = sorted(map(str, ckpt))[:6] if isinstance(ckpt, dict) else type(ckpt).__name__
+        raise RuntimeError(f'{path} holds no averaged weights ("params_ema"): its keys are {keys}; train with --ema-decay to '
+                           'write them, or drop --ema')
+    for key in (('params_ema',) if ema else ('state', 'params_ema', 'params')):
         if isinstance(ckpt, dict) and isinstance(ckpt.get(key), dict):
             state = ckpt[key]
             break
@@ -240,7 +246,13 @@ def test(args: Namespace, model: object, device) -> None:
     import numpy as np
     from PIL import Image
     from .srgan.trainer import save_image
-    state = load_generator_state(getattr(args, 'weights', None) or f'{args.model.lower()}-gan-best.pth')
+    path = getattr(args, 'weights', None) or f'{args.model.lower()}-gan-best.pth'
+    try:
+        state = load_generator_state(path, ema=bool(getattr(args, 'ema', False)))
+    except RuntimeError as exc:
+        if not getattr(args, 'ema', False):
+            raise
+        raise SystemExit(f'torchsr test: {exc}')
     scale = 4
     if args.model.lower() == 'compact':  # a 16-conv and a 32-conv file both load: the depth is the file's
         generator = model(num_conv=compact_num_conv(state)).to(device)

@@ -56,6 +56,26 @@ def probability(value: str) -> float:
     return float_value
 
 
+def ema_decay(value: str) -> float:
+    try:
+        float_value = float(value)
+    except (TypeError, ValueError):
+        raise ArgumentTypeError(f'invalid float value: \'{value}\'')
+    if not 0.0 <= float_value < 1.0:  # (also NaN)
+        raise ArgumentTypeError('value must be a decay in [0, 1)!')
+    return float_value
+
+
+def non_negative_float(value: str) -> float:
+    try:
+        float_value = float(value)
+    except (TypeError, ValueError):
+        raise ArgumentTypeError(f'invalid float value: \'{value}\'')
+    if not 0.0 <= float_value < float('inf'):  # (also NaN)
+        raise ArgumentTypeError('value must be a finite non-negative number!')
+    return float_value
+
+
 def non_negative_integer(value: str) -> int:
     try:
         int_value = int(value)
@@ -183,6 +203,26 @@ def parse_args(argv=None) -> Namespace:
     train.add_argument('--skip-nonfinite-steps', action='store_true',
                        help='skip an optimiser step whose gradient holds an inf or a NaN (what the reference\'s GradScaler '
                             'does); the skipped steps are counted and logged per epoch')
+    train.add_argument('--init-generator', type=str, default=None, metavar='PATH',
+                       help='fine-tune: start the generator from this file -- every format test --weights takes, the published '
+                            'RealESRGAN_x4plus / realesr-general-x4v3 files included, in any of their key namings.  The number of '
+                            'blocks (--model esrgan) or body convs (--model compact) is read off the file; an x2 file is refused.  '
+                            'Optimiser states start at zero.  A phase that finds a checkpoint of its own (--psnr-checkpoint, '
+                            '--gan-checkpoint, <model>-{psnr,gan}-latest.pth) resumes from that instead and says so; with '
+                            '--pretrain-epochs 0 the GAN phase starts from this file.  --model esrgan and --model compact')
+    train.add_argument('--init-discriminator', type=str, default=None, metavar='PATH',
+                       help='fine-tune: start the discriminator from this file, loaded strictly: a bare state_dict, '
+                            'Real-ESRGAN\'s {"params": ...} (the published *_netD.pth files, with --discriminator unet) or a '
+                            'checkpoint of this package (its resume.discriminator entry).  --model esrgan and --model compact')
+    train.add_argument('--ema-decay', type=ema_decay, default=None, metavar='FLOAT',
+                       help='keep an exponential moving average of the generator\'s weights, ema = FLOAT * ema + (1 - FLOAT) * '
+                            'weights after every generator update of both phases, one launch inside the captured step '
+                            '(Real-ESRGAN: 0.999).  The averaged weights are what the per-epoch test evaluates, keeps as best / '
+                            'latest and shows; every checkpoint gains them as "params_ema" (test --ema runs them).  0 <= FLOAT < 1; '
+                            'default: off.  --model esrgan and --model compact')
+    train.add_argument('--pixel-weight', type=non_negative_float, default=None, metavar='FLOAT',
+                       help='the weight of the L1 term in the GAN phase\'s generator loss (default 0.01, the reference\'s; '
+                            'Real-ESRGAN: 1.0).  --model esrgan and --model compact')
     test = commands.add_parser('test', help='Generate a super resolution image from a trained model.')
     test.add_argument('image', type=str)
     test.add_argument('--model', type=str, default=MODEL, choices=model_names())
@@ -193,6 +233,9 @@ def parse_args(argv=None) -> Namespace:
                            'RRDBNet file -- RealESRGAN_x4plus, ESRGAN_SRx4_DF2KOST_official, RealESRGAN_x4plus_anime_6B, '
                            'RealESRGAN_x2plus -- in BasicSR / Real-ESRGAN or xinntao/ESRGAN key names as well as this '
                            'package\'s own: the number of blocks and the scale (x4, or x2) are read off the file')
+    test.add_argument('--ema', action='store_true',
+                      help='run the averaged weights ("params_ema") of a checkpoint written by train --ema-decay instead of its '
+                           'live "state"; a file without them is refused')
     test.add_argument('--precision', type=str, default='fp32', choices=('fp32', 'bf16', 'fp16'),
                       help='conv arithmetic of the generator forward: exact fp32 (the reference runs no autocast here), '
                            'bf16 products with fp32 accumulation, or fp16 products and fp16-stored activations with fp32 '
@@ -215,6 +258,27 @@ def parse_args(argv=None) -> Namespace:
     if args.function == 'train':
         if args.num_conv is not None and args.model.lower() != 'compact':
             parser.error(f'--num-conv sets the depth of --model compact; --model {args.model} has none')
+        finetune = args.model.lower() in ('esrgan', 'compact')
+        for flag, value, why in (('--init-generator', args.init_generator, 'keeps no file format of a published model'),
+                                 ('--init-discriminator', args.init_discriminator, 'keeps no file format of a published model'),
+                                 ('--ema-decay', args.ema_decay, 'has BatchNorm buffers, which have no average defined'),
+                                 ('--pixel-weight', args.pixel_weight, 'has no L1 term in its generator loss')):
+            if value is not None and not finetune:
+                parser.error(f'{flag} trains with --model esrgan or --model compact; --model {args.model} {why}')
+        for flag, value in (('--init-generator', args.init_generator), ('--init-discriminator', args.init_discriminator)):
+            if value is not None and not os.path.isfile(value):
+                parser.error(f'{flag}: no such file: {value}')
+        if args.init_generator is not None and args.model.lower() == 'compact':
+            # the file's depth: it sets --num-conv when that was not given, and a --num-conv that differs is an error
+            from torchsr_amd.compact.trainer import num_conv_conflict
+            from torchsr_amd.test import compact_num_conv, load_generator_state
+            try:
+                depth = compact_num_conv(load_generator_state(args.init_generator))
+            except Exception as exc:  # (an unreadable file, or not a compact state_dict)
+                parser.error(f'--init-generator {args.init_generator}: {exc}')
+            if args.num_conv is not None and args.num_conv != depth:
+                parser.error(num_conv_conflict(args.num_conv, depth, args.init_generator))
+            args.num_conv = depth
         if args.num_conv is None:
             args.num_conv = 32
     if args.function == 'train' and args.discriminator == 'unet' and args.model.lower() not in ('esrgan', 'compact'):
