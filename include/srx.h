@@ -764,10 +764,19 @@ int srx_bn_act_bwd(const float* dout, const float* y, const float* mean, const f
  *   fwd:      y = act(conv(x) + bias)
  *   bwd_data: dx = conv^T(dy), multiplied by the ReLU mask (relu_out > 0, laid out like dx; NULL: none) of the layer below -- the
  *             fold srx_conv2d_bwd_data_act does for the direct kernel
- * ws: srx_wino_ws_floats(d, which) floats (which: 0 forward, 1 data gradient; non-zero when the planner splits the input
- * channels over several workgroups, or cuts the tiles of the last, partly filled round of the chip along them).  x != y.
- * srx_wino_plan: out[6] = {BN, channel splits of every tile, workgroups, tile blocks, chunks per workgroup, parts per tile of the
- * last round (1: none)} (host only). */
+ * ws: srx_wino_ws_floats(d, which) floats; non-zero when the planner splits the input channels over several workgroups, or cuts
+ * the tiles of the last, partly filled round of the chip along them.  x != y.  `which` names the launch, as the launch itself plans:
+ *   0  srx_wino_fwd (bias, ReLU): any plan;
+ *   1  srx_wino_bwd_data: any plan, Cin and Cout swapped;
+ *   2  srx_wino_fwd_stats: no split of every tile (statistics come from whole outputs); the last round's tiles may be cut;
+ *   3  srx_wino_fwd_act with a LeakyReLU, an addend or a PixelShuffle store (the only `which` a shuffle layer's plan can be asked
+ *      with): neither split nor cut tiles -- the fix-up passes know none of the three -- so the workspace is 0 floats and may be
+ *      NULL.  (A srx_wino_fwd_act call with none of the three plans as which = 0; a shuffle layer plans as 3 under any forward which.)
+ * srx_wino_plan(d, which, out): out[6] = {BN, channel splits of every tile, workgroups, tile blocks, chunks per workgroup, parts per
+ * tile of the last round (1: none)} of that launch (host only); any other `which` is refused.
+ * Launch records: wino_kernel<BN> under srx_prof_start; the passes behind it -- "wino_fixup_kernel" (sums a channel split) and
+ * "wino_tail_fixup_kernel<32>" / "<64>" (finishes the cut tiles) -- only under srx_prof_start_aux, as the weight gradient's reduce
+ * kernels. */
 int srx_wino_applicable(const srx_conv2d_t* d);
 size_t srx_wino_packed_floats(const srx_conv2d_t* d);
 size_t srx_wino_ws_floats(const srx_conv2d_t* d, int which);

@@ -293,15 +293,20 @@ def bf16_round(t):
     return t.to(torch.bfloat16).to(t.dtype)
 
 
-def conv_refs(what, a, b, x_shape, w_shape, stride, pad, up=0, bias=None, rounded=False, u=U32):
+def conv_refs(what, a, b, x_shape, w_shape, stride, pad, up=0, bias=None, rounded=False, u=U32, wino=False):
     """One product of the layer ``x_shape`` (N, Cin, H, W: the conv's input BEFORE the nearest x2 upsampling ``up = 2`` fuses
     into its gather) * ``w_shape`` (Cout, Cin, k, k): ``what`` = 'y' (a = x, b = W, + the fp32 bias), 'dx' (a = dy, b = W) or 'dW'
     (a = x, b = dy), three ways: (float64 value, torch fp32 value, the elementwise bound gamma_K (|a| conv |b|), K the reduction
     length).  ``rounded``: bf16 products -- BOTH factors are rounded to bf16 first (test_conv2d_bf16_products,
     oracle.srgan.bf16_products(exact_sums=True)); a bf16 x bf16 product is exact in fp32, so the float64 value differs from the
-    kernel's by the K-term fp32 accumulation alone and the same bound holds, on the rounded operands."""
+    kernel's by the K-term fp32 accumulation alone and the same bound holds, on the rounded operands.  ``wino`` ('y' and 'dx' of a
+    3 x 3 / stride 1 / pad 1 fp32 layer): a fourth value, the elementwise bound of the Winograd form (wino_bound below)."""
     import torch
     import torch.nn.functional as TF
+    if wino:
+        assert what in ('y', 'dx') and tuple(w_shape[2:]) == (3, 3) and (stride, pad, up) == (1, 1, 0) and not rounded
+        w_eff = b if what == 'y' else b.transpose(0, 1).flip(2, 3)
+        return conv_refs(what, a, b, x_shape, w_shape, stride, pad, up, bias, rounded, u) + (wino_bound(a, w_eff, bias, u=u),)
     if rounded:
         a, b = bf16_round(a), bf16_round(b)
     cout, cin, k, _ = w_shape
@@ -326,6 +331,60 @@ def conv_refs(what, a, b, x_shape, w_shape, stride, pad, up=0, bias=None, rounde
         m = b[:, 0].numel()
         return f(a.double(), b.double()), f(a, b), gamma(m, u) * f(a.double().abs(), b.double().abs())
     raise KeyError(what)
+
+
+# Winograd F(2x2, 3x3) (wino.hip): Y = A^T [ sum_ci (G g G^T) (.) (B^T d B) ] A.  The bound of one output element is NOT that of
+# the direct form: the transforms cancel, so an error is relative to the sum of the ABSOLUTE transformed terms,
+#     |y - y64| <= gamma_k ( |A^T| [ sum_ci (|G| |g| |G^T|) (.) (|B^T| |d| |B|) ] |A| + |bias| ),
+# k = wino_k(...): the longest chain of roundings between an operand and the output, counted from the code.
+WINO_BT = ((1, 0, -1, 0), (0, 1, 1, 0), (0, -1, 1, 0), (0, 1, 0, -1))
+WINO_G = ((1, 0, 0), (.5, .5, .5), (.5, -.5, .5), (0, 0, 1))
+WINO_AT = ((1, 1, 1, 0), (0, 1, -1, -1))
+WINO_MAX_PARTS = 16   # srx_wino_force_plan's and the planner's limit: 16 splits of every tile (8 parts of a tile of the last round)
+
+
+def wino_k(cin, parts=1, bias=False, extra=0):
+    """Roundings between an operand and one output element of wino.hip, each next to where the code makes it."""
+    return (4                       # filter transform, srx_wino_pack_one: G g is two additions per entry (the halving is exact), (G g) G^T two more
+            + 2                     # input transform, stage_patch: B^T d is one addition per entry, (B^T d) B one more
+            + 1                     # the product U V (counted apart from its accumulation: right for a fused MFMA step too)
+            + cin                   # the MFMA chain over the input channels, the first step's addition to C = 0 included
+            + (parts - 1)           # wino_fixup_kernel / wino_tail_fixup_kernel: the splits or parts, added in order onto the first
+            + 4                     # output transform, the epilogue: A^T M is two additions per entry, (A^T M) A two more
+            + (1 if bias else 0)    # + bias
+            + extra)                # the caller's: LeakyReLU's multiplication, the addend's addition
+
+
+def wino_bound(a, w_eff, bias=None, parts=WINO_MAX_PARTS, extra=0, u=U32):
+    """gamma_k (wino_abs + |bias|) of the forward problem a * w_eff; ``parts``: the splits or parts of the launch's plan -- the
+    planner's limit where the caller does not know the plan (a layer class chose it)."""
+    mag = wino_abs(a, w_eff)
+    if bias is not None:
+        mag = mag + bias.double().abs().view(1, -1, 1, 1)
+    return gamma(wino_k(w_eff.shape[1], parts, bias is not None, extra), u) * mag
+
+
+def wino_abs(a, w_eff, tiles_per_pass=8192):
+    """|A^T| [ sum_ci (|G| |g| |G^T|) (.) (|B^T| |d| |B|) ] |A| of the forward problem ``a`` (N, Cin, H, W; H, W even) * ``w_eff``
+    (Cout, Cin, 3, 3) in float64, shaped like the output (N, Cout, H, W).  A data gradient is the forward problem of dy and
+    ``w.transpose(0, 1).flip(2, 3)``.  Images are taken a few at a time: the transformed patches of a step-sized layer are GBs."""
+    import torch
+    import torch.nn.functional as TF
+    bt, g, at = (torch.tensor(m, dtype=torch.float64).abs() for m in (WINO_BT, WINO_G, WINO_AT))
+    n, cin, h, w = a.shape
+    cout = w_eff.shape[0]
+    th, tw = h // 2, w // 2
+    uabs = torch.einsum('ip,ocpq,jq->ijco', g, w_eff.double().abs(), g).reshape(16, cin, cout)
+    out = torch.empty((n, cout, h, w), dtype=torch.float64)
+    step = max(1, tiles_per_pass // (th * tw))
+    for n0 in range(0, n, step):
+        ap = TF.pad(a[n0:n0 + step].double().abs(), (1, 1, 1, 1))
+        m = ap.shape[0]
+        patches = ap.unfold(2, 4, 2).unfold(3, 4, 2)                                  # (m, Cin, TH, TW, 4, 4)
+        vabs = torch.einsum('ip,ncyxpq,jq->ijnyxc', bt, patches, bt).reshape(16, m * th * tw, cin)
+        mabs = torch.bmm(vabs, uabs).reshape(4, 4, m, th, tw, cout)
+        out[n0:n0 + step] = torch.einsum('ui,vj,ijnyxo->noyuxv', at, at, mabs).reshape(m, cout, h, w)
+    return out
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # The non-convolution launches of the steps: BatchNorm, losses, pools, activations' backward, layout, Adam (norm.hip, loss.hip,

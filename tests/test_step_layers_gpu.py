@@ -12,7 +12,9 @@ the same fp32 operands the kernel read.  Checks per output:
 * statistical: relL2(kernel, fp64) <= F * relL2(torch CPU fp32, fp64) + 1e-7, F = 1.5 for direct forms, 3.0 for Winograd;
 * elementwise, direct forms: |out - ref64| <= gamma_K * (|x| conv |W|), gamma_K = K u / (1 - K u), u = 2^-24, K the form's
   reduction length -- the worst case of any summation order, nothing fitted;
-* elementwise, Winograd forms: max |out - ref64| <= 2e-5 max |ref64| (the figure of test_wino_gpu.py).
+* elementwise, Winograd forms: max |out - ref64| <= 2e-5 max |ref64| (the figure of test_wino_gpu.py), and per element
+  |out - ref64| <= gamma_k (|A^T| [sum_ci (|G||g||G^T|) (.) (|B^T||d||B|)] |A| + |bias|), k the rounding chain of wino.hip
+  (step_layers.wino_k, with the most splits a plan can have: the layer class chose the plan) -- as derived as the direct forms'.
 
 Fused activations are continuous in the forward; in the backward the reference takes the activation's decisions from the kernel's
 own output (the gradient at the conv output is gy * act'(y_kernel)), so that a pre-activation within rounding of zero does not
@@ -24,7 +26,7 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-from step_layers import STEP_CONVS, conv_refs, gamma, prof_launches
+from step_layers import STEP_CONVS, conv_refs, gamma, prof_launches, wino_bound
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
@@ -80,8 +82,9 @@ def budget(what, mine, theirs, f, report):
         assert mine <= f * theirs + 1e-7, (what, mine, theirs)
 
 
-def check(what, got, ref64, ref32, bound, wino, report):
-    """got / ref32: the kernel's and torch's fp32 results, ref64 the float64 value; bound: the elementwise bound (direct forms)."""
+def check(what, got, ref64, ref32, bound, wino, report, wbound=None):
+    """got / ref32: the kernel's and torch's fp32 results, ref64 the float64 value; bound: the elementwise bound (direct forms);
+    wbound: the elementwise bound of a Winograd form (step_layers.wino_bound), which every Winograd output must come with."""
     got, ref32 = got.double(), ref32.double()
     mine, theirs = rel_l2(got, ref64), rel_l2(ref32, ref64)
     f = F_WINO if wino else F_DIRECT
@@ -90,6 +93,10 @@ def check(what, got, ref64, ref32, bound, wino, report):
     err = (got - ref64).abs()
     if wino:
         assert err.max().item() <= 2e-5 * ref64.abs().max().item(), (what, err.max().item(), ref64.abs().max().item())
+        assert wbound is not None and wbound.shape == err.shape, (what, 'a Winograd output without its elementwise bound')
+        print(f'  {what:44s} max err/bound {(err / wbound.clamp_min(1e-300)).max().item():.3f}  (wino)')
+        outside = int((err > wbound).sum())
+        assert outside == 0, (what, f'{outside} of {err.numel()} elements outside the Winograd bound')
     else:
         worst = (err - bound).max().item()
         print(f'  {what:44s} max err/bound {(err / bound.clamp_min(1e-300)).max().item():.3f}')
@@ -152,11 +159,12 @@ def run_conv_case(case, dev, report, precision='fp32', u=U, prefill=0.0):
     wino = conv._st.wino_fwd is not None
     tag = case['id']
 
-    pre64, pre32, by = conv_refs('y', x, wt, x.shape, wt.shape, s, p, up, b, rounded['y'], u)
+    pre64, pre32, by, *wby = conv_refs('y', x, wt, x.shape, wt.shape, s, p, up, b, rounded['y'], u, wino=wino)
     post = lambda t: (torch.relu(t) if act == 1 else TF.leaky_relu(t, slope) if act == 2 else t)  # noqa: E731
     shuf = lambda t: TF.pixel_shuffle(t, 2) if shuffle else t  # noqa: E731
     got_y = nchw(yg.detach().cpu(), cl)
-    check(f'{tag} y', got_y, shuf(post(pre64)), shuf(post(pre32)), shuf(by), wino, report)
+    # (ReLU moves no two values further apart, so the pre-activation's Winograd bound holds behind it)
+    check(f'{tag} y', got_y, shuf(post(pre64)), shuf(post(pre32)), shuf(by), wino, report, shuf(wby[0]) if wino else None)
     if stats:
         m = pre64[:, 0].numel()
         s1 = part[:, :, 0].double().sum(0).cpu()
@@ -182,13 +190,14 @@ def run_conv_case(case, dev, report, precision='fp32', u=U, prefill=0.0):
     else:
         g_pre = g_post
     if dx_on:
-        dx64, dx32, bdx = conv_refs('dx', g_pre, wt, x.shape, wt.shape, s, p, up, None, rounded['dx'], u)
+        wino_dx = conv._st.wino_bwd is not None  # (a forward-only Winograd layer takes the direct data gradient)
+        dx64, dx32, bdx, *wbdx = conv_refs('dx', g_pre, wt, x.shape, wt.shape, s, p, up, None, rounded['dx'], u, wino=wino_dx)
         if in_act:
             mask = (x > 0).double() if in_act == 'relu' else torch.where(x > 0, 1.0, 0.2).double()
             dx64, dx32, bdx = dx64 * mask, dx32 * mask.float(), bdx * mask
+            wbdx = [t * mask for t in wbdx]   # (Winograd: the ReLU mask alone, 0 or 1 -- no rounding)
         got_dx = nchw(xg.grad.cpu(), cin)
-        wino_dx = conv._st.wino_bwd is not None  # (a forward-only Winograd layer takes the direct data gradient)
-        check(f'{tag} dx', got_dx, dx64, dx32, bdx, wino_dx, report)
+        check(f'{tag} dx', got_dx, dx64, dx32, bdx, wino_dx, report, wbdx[0] if wino_dx else None)
     if dw_on:
         m = g_pre[:, 0].numel()
         dw64, dw32, bdw = conv_refs('dW', x, g_pre, x.shape, wt.shape, s, p, up, None, rounded['dW'], u)
@@ -304,12 +313,15 @@ def run_stack_case(case, dev, report):
     pre64, pre32 = TF.conv2d(x.double(), wt.double(), b.double(), 1, 1), TF.conv2d(x, wt, b, 1, 1)
     got_y = torch.cat([nchw(fs.detach().cpu(), cout), nchw(ft.cpu(), cout)])
     absconv = TF.conv2d(x.double().abs(), wt.double().abs(), b.double().abs(), 1, 1)
-    check(f"{case['id']} y", got_y, torch.relu(pre64), torch.relu(pre32), gamma(cin * 9 + 1) * absconv, wino, report)
+    check(f"{case['id']} y", got_y, torch.relu(pre64), torch.relu(pre32), gamma(cin * 9 + 1) * absconv, wino, report,
+          wino_bound(x, wt, b) if wino else None)
     g_pre = gy * (got_y[:n] > 0)
     dx64 = torch.nn.grad.conv2d_input((n, cin, h, w), wt.double(), g_pre.double(), 1, 1)
     dx32 = torch.nn.grad.conv2d_input((n, cin, h, w), wt, g_pre, 1, 1)
     absdx = torch.nn.grad.conv2d_input((n, cin, h, w), wt.double().abs(), g_pre.double().abs(), 1, 1)
-    check(f"{case['id']} dx", nchw(src.grad.cpu(), cin), dx64, dx32, gamma(cout * 9) * absdx, conv._st.wino_bwd is not None, report)
+    wino_dx = conv._st.wino_bwd is not None
+    check(f"{case['id']} dx", nchw(src.grad.cpu(), cin), dx64, dx32, gamma(cout * 9) * absdx, wino_dx, report,
+          wino_bound(g_pre, wt.transpose(0, 1).flip(2, 3)) if wino_dx else None)
 
 
 def run_case(case, dev, report):

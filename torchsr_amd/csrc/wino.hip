@@ -645,13 +645,22 @@ extern "C" int srx_wino_pack(const srx_conv2d_t* d, const float* w, float* upk, 
   return SRX_OK;
 }
 
-// workspace (floats) of a forward (which = 0) or data-gradient (which = 1) call: the partial outputs of a channel split
+// The plan of a launch as wino_run makes it.  which: 0 a plain forward (srx_wino_fwd), 1 the data gradient, 2 the forward with
+// BatchNorm statistics (whole outputs per tile: no split of every tile; the last round's may be cut), 3 a forward with a LeakyReLU,
+// an addend or a PixelShuffle store (the fix-up passes know none of them: neither split nor tail)
+static bool wino_launch_plan(const srx_conv2d_t* d, int which, WinoPlan& p, int& T, int& cin, int& cout) {
+  if (!d || which < 0 || which > 3 || !wino_shape_ok(d, which == 3 || (which != 1 && d->shuffle != 0))) return false;
+  cin = which == 1 ? d->Cout : d->Cin; cout = which == 1 ? d->Cin : d->Cout;
+  T = d->N * (d->H / 2) * (d->W / 2);
+  const bool act = which == 3 || d->shuffle != 0;
+  p = wino_plan(T, cin, cout, act || which == 2, act);
+  return true;
+}
+
+// workspace (floats) of a call (which: see wino_launch_plan): the partial outputs of a channel split, or of the last round's parts
 extern "C" size_t srx_wino_ws_floats(const srx_conv2d_t* d, int which) {
-  if (!d || !wino_shape_ok(d, which != 1)) return 0;
-  const int cin = which == 1 ? d->Cout : d->Cin, cout = which == 1 ? d->Cin : d->Cout;
-  const int T = d->N * (d->H / 2) * (d->W / 2);
-  // (which = 2: the forward with BatchNorm statistics -- whole outputs per tile, so no split of every tile; the last round's may be cut)
-  const WinoPlan p = wino_plan(T, cin, cout, d->shuffle != 0 || which == 2, d->shuffle != 0);
+  WinoPlan p; int T, cin, cout;
+  if (!wino_launch_plan(d, which, p, T, cin, cout)) return 0;
   if (p.tsplit > 1) {
     const int64_t wgs = srx_cdiv(T, WT) * (cout / p.bn);
     return (size_t)(wgs % srx_plan_cus()) * p.tsplit * WT * 4 * p.bn;
@@ -659,12 +668,10 @@ extern "C" size_t srx_wino_ws_floats(const srx_conv2d_t* d, int which) {
   return p.zsplit > 1 ? (size_t)p.zsplit * d->N * d->H * d->W * cout : 0;
 }
 
-// out[6] = {BN, channel splits, workgroups, tile blocks, chunks per workgroup (max), 0}
+// out[6] = {BN, channel splits, workgroups, tile blocks, chunks per workgroup (max), parts per tile of the last round}
 extern "C" int srx_wino_plan(const srx_conv2d_t* d, int which, int* out) {
-  SRX_REQUIRE(d && out && wino_shape_ok(d), "wino_plan: not a Winograd layer");
-  const int cin = which ? d->Cout : d->Cin, cout = which ? d->Cin : d->Cout;
-  const int T = d->N * (d->H / 2) * (d->W / 2);
-  const WinoPlan p = wino_plan(T, cin, cout);
+  WinoPlan p; int T, cin, cout;
+  SRX_REQUIRE(out && wino_launch_plan(d, which, p, T, cin, cout) && (which == 3 || !d->shuffle), "wino_plan: not a Winograd layer (or which not in 0..3)");
   out[0] = p.bn; out[1] = p.zsplit; out[3] = (int)srx_cdiv(T, WT); out[2] = out[3] * (cout / p.bn) * p.zsplit;
   out[4] = (int)srx_cdiv(cin / WKC, p.zsplit); out[5] = p.tsplit;
   if (p.tsplit > 1) { const int tail = out[2] % srx_plan_cus(); out[2] += tail * (p.tsplit - 1); }
@@ -730,12 +737,12 @@ static int wino_run(const srx_conv2d_t* d, int which, const float* x, const floa
   if (p.zsplit > 1) {
     const size_t n4 = a.out_elems / 4;
     const unsigned blocks = (unsigned)std::min<size_t>(srx_cdiv((int64_t)n4, 256), 4096);
-    hipLaunchKernelGGL(wino_fixup_kernel, dim3(blocks), dim3(256), 0, st, ws, p.zsplit, n4, a.out_elems, bias, mask, y, a.Cout / 4, relu);
+    SRX_LAUNCH_PROF_AUX("wino_fixup_kernel", wino_fixup_kernel, dim3(blocks), dim3(256), 0, st, ws, p.zsplit, n4, a.out_elems, bias, mask, y, a.Cout / 4, relu);
     SRX_CHECK_LAUNCH("wino_fixup_kernel");
   }
   if (tail > 0) {
-    if (p.bn == 64) hipLaunchKernelGGL(wino_tail_fixup_kernel<64>, dim3((unsigned)tail), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL(wino_tail_fixup_kernel<32>, dim3((unsigned)tail), dim3(256), 0, st, a);
+    if (p.bn == 64) SRX_LAUNCH_PROF_AUX("wino_tail_fixup_kernel<64>", wino_tail_fixup_kernel<64>, dim3((unsigned)tail), dim3(512), 0, st, a);
+    else SRX_LAUNCH_PROF_AUX("wino_tail_fixup_kernel<32>", wino_tail_fixup_kernel<32>, dim3((unsigned)tail), dim3(256), 0, st, a);
     SRX_CHECK_LAUNCH("wino_tail_fixup_kernel");
   }
   return SRX_OK;
