@@ -267,6 +267,24 @@ int srx_unshuffle2_conv_fwd(int N, int H, int W, const float* x, const float* wp
                             void* stream);
 int srx_unshuffle2_conv_plan(int N, int H, int W, int* out);
 
+/* Weight gradient of that layer (unshuffle.hip; training RRDBNet at x2).  x: the image the forward read, dy: fp32
+ * [N][Hp / 2][Wp / 2][64], dw_oihw: the module's [64][12][3][3]; accumulate != 0 adds to it.  dV[o][c][ty][tx] = sum over
+ * (n, Y, X) of dy[n][Y][X][o] * x[n][r(2 Y - 2 + ty)][q(2 X - 2 + tx)][c] with the forward's gather (zero outside [0, Hp),
+ * index H -> H - 2; columns alike) and dw[o][4 c + 2 (ty & 1) + (tx & 1)][ty >> 1][tx >> 1] = dV[o][c][ty][tx].  Exact fp32
+ * MFMAs whatever the layer's precision.  There is no data gradient: the input is the image.  The bias gradient is the column
+ * sum of dy (srx_colsum).
+ *   ws_floats: the workspace the call needs for this shape (slabs x 4 x 36 x 64), 0 for a shape the call refuses.
+ *   plan: host only, by the function the launch plans with (under srx_set_reserved_cus): out[5] = {segments of 16 output pixels
+ *         of one output row, wave ranges that hold a segment, segments per range, slabs the reduction sums = workgroups per group,
+ *         groups of tap rows}; the launch has groups x slabs workgroups of four wave ranges, ranges past the second entry are
+ *         empty.
+ * Refused, nothing launched: SRX_E_BADARG for a null x / dy / dw / ws and for the shapes the forward refuses; SRX_E_WORKSPACE for
+ * ws_floats below srx_unshuffle2_conv_wgrad_ws_floats(N, H, W). */
+size_t srx_unshuffle2_conv_wgrad_ws_floats(int N, int H, int W);
+int srx_unshuffle2_conv_wgrad_plan(int N, int H, int W, int* out);
+int srx_unshuffle2_conv_bwd_weight(int N, int H, int W, const float* x, const float* dy, float* dw_oihw, int accumulate, float* ws,
+                                   size_t ws_floats, void* stream);
+
 /* Launch plan of nn.Linear (linear.hip), computed by the function the launches themselves plan with; host code only.  which = 0
  * forward, 1 data gradient: out[6] = {splits launched (slabs of partial sums), contraction elements per split (k / j), launches
  * of up to 64 rows, 16-row blocks NB of the last launch, form of the first launch (1 plain, 2 fast), form of the last launch}.

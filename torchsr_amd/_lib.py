@@ -179,6 +179,9 @@ _SIGS = {
     'srx_unshuffle2_conv_pack': (_I, [_P, _P, _P]),
     'srx_unshuffle2_conv_fwd': (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P]),
     'srx_unshuffle2_conv_plan': (_I, [_I, _I, _I, C.POINTER(C.c_int)]),
+    'srx_unshuffle2_conv_wgrad_ws_floats': (_Z, [_I, _I, _I]),
+    'srx_unshuffle2_conv_wgrad_plan': (_I, [_I, _I, _I, C.POINTER(C.c_int)]),
+    'srx_unshuffle2_conv_bwd_weight': (_I, [_I, _I, _I, _P, _P, _P, _I, _P, _Z, _P]),
     'srx_conv2d_force_s2': (_I, [_I, _I, _I]),
     'srx_wgrad_force': (_I, [_I, _I]),
     'srx_wgrad_force_kernels': (_I, [_I, _I, _I]),

@@ -7,7 +7,7 @@ sets the number of body convs.
 """
 import functools
 
-from ..esrgan.trainer import ESRGANTrainer
+from ..esrgan.trainer import ESRGANTrainer, read_scale, scale_conflict
 from .generator import NUM_CONV, Generator, tail_index
 
 
@@ -19,19 +19,34 @@ class CompactTrainer(ESRGANTrainer):
 
     def __init__(self, device, args, *rest, **kw) -> None:
         self._num_conv_given = getattr(args, 'num_conv', None)  # None: the default, or the depth of --init-generator's file
+        self.scale = read_scale(args)
         self._set_num_conv(int(self._num_conv_given or NUM_CONV))
         super().__init__(device, args, *rest, **kw)
 
     def _set_num_conv(self, num_conv: int) -> None:
-        if num_conv != NUM_CONV:  # (instance attributes: the class keeps describing the default network)
-            self.generator_cls = functools.partial(Generator, num_conv=num_conv)
+        if num_conv != NUM_CONV or self.scale != 4:  # (instance attributes: the class keeps describing the default network)
+            self.generator_cls = functools.partial(Generator, scale_factor=self.scale, num_conv=num_conv)
             self.gen_tail_bucket = f'body.{tail_index(num_conv)}.weight'
 
+    def _set_scale(self) -> None:
+        pass  # (``_set_num_conv`` builds the generator class from the depth and the scale)
+
+    def _state_scale(self, state: dict):
+        from ..test import compact_scale
+        try:
+            return compact_scale(state)
+        except RuntimeError:
+            return None
+
     def _init_generator_state(self, path: str) -> dict:
-        """``train --init-generator``: every SRVGGNetCompact file ``test --weights`` takes; the depth is the file's."""
-        from ..test import compact_num_conv, load_generator_state
+        """``train --init-generator``: every SRVGGNetCompact file ``test --weights`` takes; the depth is the file's, and the
+        scale (read off the last conv's output channels) must be the run's."""
+        from ..test import compact_num_conv, compact_scale, load_generator_state
         state = load_generator_state(path)
         depth = compact_num_conv(state)
+        scale = compact_scale(state, path)
+        if scale != self.scale:
+            raise RuntimeError(scale_conflict(f'--init-generator {path}', 'SRVGGNetCompact', scale, self.scale))
         if self._num_conv_given is not None and int(self._num_conv_given) != depth:
             raise RuntimeError(num_conv_conflict(int(self._num_conv_given), depth, path))
         self.__dict__.pop('generator_cls', None)

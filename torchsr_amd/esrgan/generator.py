@@ -22,23 +22,25 @@ class Generator(nn.Module):
     takes 12 channels at half the resolution (``weight`` [64, 12, 3, 3], RRDBNet's own shape) and the two x2 stages end at
     ``[N,3,2h,2w]``.  The unshuffle is the gather of ``conv1``'s kernel (``layers.Unshuffle2Conv2d``); an odd h or w (at least 3)
     is padded there by one reflected row / column at the bottom / right, as ``RealESRGANer.pre_process`` pads, and the result is
-    cropped back to ``[2h, 2w]``.  x2 is inference-only: a training-mode or autograd-enabled forward raises ``RuntimeError``.
+    cropped back to ``[2h, 2w]``.  By default x2 is inference-only: a training-mode or autograd-enabled forward raises
+    ``RuntimeError``.  ``trainable=True`` builds ``conv1`` with its weight gradient (``Unshuffle2Conv2d(trainable=True)``) and
+    lifts that refusal; at ``scale_factor=4`` the flag is accepted and changes nothing.
     """
 
     # tiled inference (torchsr_amd/test.py): the true receptive field radius is ~350 low-resolution pixels, more than a
     # tile can carry, so ESRGAN tiling is approximate near tile borders
     halo = 64
 
-    def __init__(self, num_rrdb_blocks: int = NUM_RESIDUAL, scale_factor: int = 4) -> None:
+    def __init__(self, num_rrdb_blocks: int = NUM_RESIDUAL, scale_factor: int = 4, trainable: bool = False) -> None:
         super().__init__()
         if scale_factor not in (2, 4):
             raise ValueError(f'esrgan.Generator: scale_factor must be 4 or 2 (RRDBNet behind pixel_unshuffle(2)), got {scale_factor!r}')
-        self.scale_factor = scale_factor
+        self.scale_factor, self.trainable = scale_factor, bool(trainable)
         if scale_factor == 2:
             # tiles of the image: the trunk's 64 pixels of halo are 128 of the image's, and even tile origins keep a tile's
             # unshuffle phase the whole image's (test.upscale rounds tile sizes and the halo up to multiples of tile_align)
             self.halo, self.tile_align = 128, 2
-            self.conv1 = Unshuffle2Conv2d()
+            self.conv1 = Unshuffle2Conv2d(self.trainable)
         else:
             self.conv1 = Conv2d(3, 64, kernel_size=3, stride=1, padding=1)
         self.blocks = nn.Sequential(*[ResidualInResidualDenseBlock(channels=64, growth_channels=32, scale_ratio=0.2)
@@ -66,9 +68,9 @@ class Generator(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         if self.scale_factor == 2:
-            if not F.inference_mode(self):
-                raise RuntimeError('esrgan.Generator(scale_factor=2) is inference-only (eval mode, no autograd); the training '
-                                   'path is x4')
+            if not self.trainable and not F.inference_mode(self):
+                raise RuntimeError('esrgan.Generator(scale_factor=2) is inference-only (eval mode, no autograd) unless it is built '
+                                   'with trainable=True; the default training path is x4')
             h, w = int(x.shape[-2]), int(x.shape[-1])
             if (h & 1 and h < 3) or (w & 1 and w < 3):
                 raise RuntimeError(f'esrgan.Generator(scale_factor=2): an odd height or width is padded by reflection and must be '

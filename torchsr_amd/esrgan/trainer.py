@@ -34,19 +34,42 @@ class ESRGANTrainer(SRGANTrainer):
     gen_tail_bucket = 'upsample1.weight'  # data parallel: upsample1/2, conv3, conv4 gradients complete first
     finetune = True
 
+    def __init__(self, device, args, *rest, **kw) -> None:
+        self.scale = read_scale(args)  # train --scale: 4, or 2 (RRDBNet behind pixel_unshuffle(2); the compact net with 12 outputs)
+        self._set_scale()
+        super().__init__(device, args, *rest, **kw)
+
+    def _set_scale(self) -> None:
+        if self.scale != 4:  # (instance attribute: the class keeps describing the default network)
+            cls = self.generator_cls
+            self.generator_cls = functools.partial(getattr(cls, 'func', cls), **{**getattr(cls, 'keywords', {}),
+                                                                                'scale_factor': self.scale, 'trainable': True})
+
     def _init_generator_state(self, path: str) -> dict:
         """``train --init-generator``: every RRDBNet file ``test --weights`` takes, in either published naming or this package's;
-        the generator is built at the file's depth (23 blocks, or 6 for the anime model).  An x2 file is refused."""
+        the generator is built at the file's depth (23 blocks, or 6 for the anime model).  The file's scale must be the run's."""
         from ..rrdbnet import rrdbnet_geometry, rrdbnet_to_generator_state
         from ..test import load_generator_state
         state = rrdbnet_to_generator_state(load_generator_state(path))
         num_blocks, scale = rrdbnet_geometry(state)
-        if scale != 4:
-            raise RuntimeError(f'--init-generator {path}: an x{scale} RRDBNet file; x{scale} is inference-only here '
-                               '(test --weights runs it), the training path is x4')
+        if scale != self.scale:
+            raise RuntimeError(scale_conflict(f'--init-generator {path}', 'RRDBNet', scale, self.scale))
         cls = self.generator_cls  # (instance attribute: the class keeps describing the default network)
-        self.generator_cls = functools.partial(getattr(cls, 'func', cls), num_rrdb_blocks=num_blocks)
+        self.generator_cls = functools.partial(getattr(cls, 'func', cls), **{**getattr(cls, 'keywords', {}),
+                                                                            'num_rrdb_blocks': num_blocks})
         return state
+
+    def _state_scale(self, state: dict):
+        """The scale a generator state_dict was trained at (``None``: not readable off it)."""
+        w = state.get('conv1.weight')
+        return {3: 4, 12: 2}.get(int(w.shape[1])) if w is not None and w.dim() == 4 else None
+
+    def _load_generator_state(self, state: dict, path: str) -> None:
+        """A checkpoint's generator: one clear error when it was trained at the other scale."""
+        scale = self._state_scale(state)
+        if scale is not None and scale != self.scale:
+            raise RuntimeError(scale_conflict(f'checkpoint {path}', 'generator', scale, self.scale))
+        super()._load_generator_state(state, path)
 
     def _initialize_loss(self) -> None:
         """esrgan/trainer.py:159-165."""
@@ -112,3 +135,18 @@ class ESRGANTrainer(SRGANTrainer):
         self._losses['gan/adversarial-loss'] = aux[1]
         self._losses['gan/train-loss'] = gen_loss.detach()
         self._super_res = self._content = self._high4 = None
+
+
+def read_scale(args) -> int:
+    scale = int(getattr(args, 'scale', None) or 4)
+    if scale not in (2, 4):
+        raise RuntimeError(f'--scale {scale}: the trainers run at x4 and x2')
+    return scale
+
+
+def scale_conflict(what: str, kind: str, scale: int, run_scale: int) -> str:
+    """The message for a file whose scale is not the run's (``--init-generator`` and resumed checkpoints)."""
+    if scale == 2:
+        return (f'{what}: an x2 {kind} file in a run at x{run_scale}; x2 is inference-only unless the run is started with '
+                f'--scale 2 (test --weights runs the file as it is)')
+    return f'{what}: an x{scale} {kind} file in a run started with --scale {run_scale}; start the run with --scale {scale}'

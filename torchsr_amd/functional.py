@@ -1103,6 +1103,9 @@ class ConvState:
         # the slots' buffers under the names their readers use: aliases, set again after every ``ensure`` of the slot
         self.wpk_fwd = self.wpk_bwd = self.wino_fwd = self.wino_bwd = self.bf16s_fwd = self.bf16s_bwd = None
         self.fused_only = False  # set while the layer runs inside a fused multi-conv kernel that has its own weight stream
+        # not False: the layer packs its own weights on every autograd forward (a trainable Unshuffle2Conv2d; then the buffer,
+        # once it exists) and no pack table carries it
+        self.own_pack = False
 
     def desc(self, n, h, w) -> Conv2dDesc:
         _chk_f16_inference(self, 'conv2d')
@@ -1211,7 +1214,9 @@ class PackTable:
 
     def _build(self) -> bool:
         # (convs whose packed fp32 copies nothing reads -- dense blocks running as fused bf16 launches, RDBPack -- are left out)
-        every = [(c._st, c.weight) for c in self.convs if c.weight.requires_grad and not c._st.fused_only]
+        # ... and so is a layer that packs on every forward (a trainable Unshuffle2Conv2d: ``ConvState.own_pack``)
+        every = [(c._st, c.weight) for c in self.convs
+                 if c.weight.requires_grad and not c._st.fused_only and c._st.own_pack is False]
         # a layer is ready once it has run: it then has its direct packs (gconv / thin / row-tile kernels), its Winograd-domain
         # copies (wino.hip: such a layer needs no direct pack at all), or both (it took both paths at different sizes)
         direct = [(st, wt) for st, wt in every if st.direct.fwd is not None]
@@ -1378,13 +1383,7 @@ def conv2d(x: Tensor, weight: Tensor, bias: Optional[Tensor], st: ConvState, wan
     return _Conv2d.apply(x, weight, bias, st, want_stats, weight if master is None else master, in_act, act_bwd_folded)
 
 
-def unshuffle2_conv(x4: Tensor, weight: Tensor, bias: Optional[Tensor], st: ConvState) -> Tensor:
-    """RRDBNet's x2 input layer, ``conv2d(pixel_unshuffle(pad(x), 2), weight, bias, padding=1)``, as one launch on the NHWC-4
-    image (csrc/unshuffle.hip): ``x4`` [N,H,W,4], ``weight`` OIHW [64,12,3,3] -> [N,Hp/2,Wp/2,64] with an odd H / W padded by
-    one reflected row / column inside the gather.  Inference only (no autograd node); ``st.precision`` 0 or 1.  The weights
-    are packed once through ``st.direct`` (``WeightPack.ensure``, keyed like every other layer's)."""
-    if torch.is_grad_enabled():
-        raise RuntimeError('unshuffle2_conv: the x2 input layer is inference-only; run it under torch.no_grad() on an eval-mode model')
+def _unshuffle2_check(x4: Tensor, weight: Tensor, st: ConvState) -> Tensor:
     if st.precision not in (0, 1):
         raise RuntimeError(f"unshuffle2_conv: precision {st.precision} has no kernel ('fp32' and 'bf16' do)")
     x4 = _chk(x4, 'unshuffle2_conv.input')
@@ -1394,6 +1393,75 @@ def unshuffle2_conv(x4: Tensor, weight: Tensor, bias: Optional[Tensor], st: Conv
                            f'{tuple(weight.shape)}')
     if (h & 1 and h < 3) or (w & 1 and w < 3):
         raise RuntimeError(f'unshuffle2_conv: an odd height or width is padded by reflection and must be at least 3, got {h} x {w}')
+    return x4
+
+
+def _unshuffle2_wgrad(x4: Tensor, dy: Tensor, out: Tensor, accumulate: int, s) -> None:
+    """The x2 input layer's weight gradient (``srx_unshuffle2_conv_bwd_weight``), written or accumulated into OIHW ``out``."""
+    n, h, w, _ = x4.shape
+    nws = _lib.lib().srx_unshuffle2_conv_wgrad_ws_floats(n, h, w)
+    call('srx_unshuffle2_conv_bwd_weight', n, h, w, _p(x4), _p(dy), _p(out), accumulate, _p(_ws(nws, x4)), nws, s)
+
+
+class _Unshuffle2Conv(Function):
+    """``unshuffle2_conv`` of a trainable layer.  The packed weights are rebuilt by every forward -- one 6912-float launch, a node
+    of a captured step like any other -- into the layer's one persistent buffer, never served from the ``WeightPack`` cache: a
+    replayed step must not read a pack from before its Adam update, and no pack table refreshes this layout.  Backward: the
+    weight gradient (fp32 whatever ``st.precision``) and the column sum of ``dy``; the input is the image and takes none."""
+
+    @staticmethod
+    def forward(ctx, x4: Tensor, weight: Tensor, bias: Optional[Tensor], st: ConvState):
+        ctx.set_materialize_grads(False)
+        n, h, w, _ = x4.shape
+        wpk = st.own_pack
+        if not isinstance(wpk, Tensor) or wpk.device != x4.device:
+            wpk = st.own_pack = torch.empty(_lib.lib().srx_unshuffle2_conv_packed_floats(), dtype=torch.float32, device=x4.device)
+        s = _stream()
+        call('srx_unshuffle2_conv_pack', _p(_chk(weight.detach(), 'unshuffle2_conv.weight')), _p(wpk), s)
+        b = None if bias is None else _chk(bias.detach(), 'unshuffle2_conv.bias')
+        y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, 64), dtype=torch.float32, device=x4.device)
+        call('srx_unshuffle2_conv_fwd', n, h, w, _p(x4), _p(wpk), _p(b), _p(y), st.precision, s)
+        ctx.params = (weight, bias)
+        ctx.save_for_backward(x4)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        x4, = ctx.saved_tensors
+        wparam, bparam = ctx.params
+        dy = _chk(dy, 'unshuffle2_conv.grad')
+        s = _stream()
+        dw = db = None
+        if ctx.needs_input_grad[1]:
+            sink = _sink(wparam)
+            if sink is None:
+                dw = torch.empty((64, 12, 3, 3), dtype=torch.float32, device=dy.device)
+            _unshuffle2_wgrad(x4, dy, dw if sink is None else sink, 0 if sink is None else 1, s)
+        if bparam is not None and ctx.needs_input_grad[2]:
+            sink = _sink(bparam)
+            if sink is None:
+                db = torch.empty(64, dtype=torch.float32, device=dy.device)
+            _colsum(_p(dy), dy.numel() // 64, 64, 64, db if sink is None else sink, 0 if sink is None else 1, dy, s)
+        return None, dw, db, None
+
+
+def unshuffle2_conv(x4: Tensor, weight: Tensor, bias: Optional[Tensor], st: ConvState, trainable: bool = False) -> Tensor:
+    """RRDBNet's x2 input layer, ``conv2d(pixel_unshuffle(pad(x), 2), weight, bias, padding=1)``, as one launch on the NHWC-4
+    image (csrc/unshuffle.hip): ``x4`` [N,H,W,4], ``weight`` OIHW [64,12,3,3] -> [N,Hp/2,Wp/2,64] with an odd H / W padded by
+    one reflected row / column inside the gather; ``st.precision`` 0 or 1.  Without autograd the weights are packed once through
+    ``st.direct`` (``WeightPack.ensure``, keyed like every other layer's).  With autograd on, a ``trainable`` layer runs as an
+    autograd node (``_Unshuffle2Conv``: weight and bias gradients, no input gradient -- an image that requires one is refused);
+    any other layer is inference-only there."""
+    if torch.is_grad_enabled():
+        if not trainable:
+            raise RuntimeError('unshuffle2_conv: the x2 input layer is inference-only; run it under torch.no_grad() on an eval-mode '
+                               'model (or build the layer with trainable=True)')
+        if x4.requires_grad:
+            raise RuntimeError('unshuffle2_conv: the x2 input layer has no input gradient (its input is the image); got an image '
+                               'that requires grad')
+        return _Unshuffle2Conv.apply(_unshuffle2_check(x4, weight, st), weight, bias, st)
+    x4 = _unshuffle2_check(x4, weight, st)
+    n, h, w, _ = x4.shape
     st.direct.ensure(st.pack_key(weight), weight.device, False,
                      lambda: (_lib.lib().srx_unshuffle2_conv_packed_floats(), 0, torch.float32),
                      lambda fwd, bwd, _: call('srx_unshuffle2_conv_pack', _p(_chk(weight.detach(), 'unshuffle2_conv.weight')), _p(fwd),

@@ -75,19 +75,24 @@ class Unshuffle2Conv2d(Conv2d):
     """RRDBNet's input layer at x2: ``nn.Conv2d(12, 64, 3, 1, 1)`` behind ``pixel_unshuffle(x, 2)``, with that module's
     ``weight`` [64, 12, 3, 3] and ``bias`` -- a published x2 state_dict loads key for key.  ``forward`` takes the NHWC-4 IMAGE
     [N,H,W,4] and returns [N,Hp/2,Wp/2,64] from one launch that gathers the unshuffled (and, for an odd H / W, reflect-padded)
-    pixels itself (``functional.unshuffle2_conv``).  Inference only: training mode or autograd raises."""
+    pixels itself (``functional.unshuffle2_conv``).  By default inference only: training mode or autograd raises.
+    ``trainable=True`` asks for the training path: with autograd on the layer is an autograd node with a weight and a bias
+    gradient (``srx_unshuffle2_conv_bwd_weight``) and no input gradient -- the input is the image."""
 
-    def __init__(self):
+    def __init__(self, trainable: bool = False):
         super().__init__(12, 64, kernel_size=3, stride=1, padding=1)
+        self.trainable = bool(trainable)
+        if self.trainable:
+            self._st.own_pack = None  # packs on every autograd forward; pack tables leave it out (functional.PackTable)
 
     def forward(self, x4: Tensor) -> Tensor:
-        if not F.inference_mode(self):
-            raise RuntimeError('Unshuffle2Conv2d: the x2 input layer is inference-only (eval mode, no autograd); '
-                               'the training path is x4')
-        return F.unshuffle2_conv(x4, self.weight, self.bias, self._st)
+        if not self.trainable and not F.inference_mode(self):
+            raise RuntimeError('Unshuffle2Conv2d: the x2 input layer is inference-only (eval mode, no autograd) unless it is built '
+                               'with trainable=True; the default training path is x4')
+        return F.unshuffle2_conv(x4, _w(self.weight), _w(self.bias), self._st, self.trainable)
 
     def __deepcopy__(self, memo):
-        new = Unshuffle2Conv2d()
+        new = Unshuffle2Conv2d(self.trainable)
         new.load_state_dict(self.state_dict())
         return new
 

@@ -434,6 +434,10 @@ class SRGANTrainer:
             return ckpt
         return None
 
+    def _load_generator_state(self, state: dict, path: str) -> None:
+        """A checkpoint's generator weights (a trainer with more than one generator geometry checks the file's first)."""
+        self.generator.load_state_dict(state)
+
     def _init_generator_state(self, path: str) -> dict:
         """``train --init-generator``: the file's state in the generator's key names, read through ``test --weights``'s
         functions; a trainer that fine-tunes sets ``generator_cls`` to the file's depth here.  Not this trainer."""
@@ -611,7 +615,7 @@ class SRGANTrainer:
         checkpoint = None if (self.init_generator and self.pre_epochs < 1) else self._load_checkpoint(path)
         if checkpoint:
             self._init_unused(path)
-            self.generator.load_state_dict(checkpoint['state'])
+            self._load_generator_state(checkpoint['state'], path)
             F.bump_pack_epoch()
             epoch = checkpoint['epoch']
             if self._restore_resume_state(checkpoint):
@@ -800,7 +804,7 @@ class SRGANTrainer:
         checkpoint = self._load_checkpoint(path)
         if checkpoint:
             self._init_unused(path)
-            self.generator.load_state_dict(checkpoint['state'])
+            self._load_generator_state(checkpoint['state'], path)
             epoch = checkpoint['epoch']
             if self._restore_resume_state(checkpoint):
                 epoch += 1  # the checkpoint is written AFTER its epoch: continue with the next one
@@ -810,7 +814,7 @@ class SRGANTrainer:
             # around belongs to another run)
             checkpoint = self._load_checkpoint(f'{self.phase_prefix}-psnr-latest.pth')
             if checkpoint:
-                self.generator.load_state_dict(checkpoint['state'])
+                self._load_generator_state(checkpoint['state'], f'{self.phase_prefix}-psnr-latest.pth')
                 self._restore_ema(checkpoint)  # this run's own pre-training wrote its average there: it continues
         F.bump_pack_epoch()
         step = 0

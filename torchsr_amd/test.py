@@ -55,6 +55,17 @@ def compact_num_conv(state) -> int:
     return (max(idx) - 2) // 2
 
 
+def compact_scale(state, path: str = 'the file') -> int:
+    """The scale of an SRVGGNetCompact state_dict, read off its last conv's output channels 3 s^2: 12 is x2, 48 is x4 (27, x3,
+    is refused: untested here)."""
+    cout = int(state[f'body.{2 * compact_num_conv(state) + 2}.weight'].shape[0])
+    scale = {12: 2, 48: 4}.get(cout)
+    if scale is None:
+        raise RuntimeError(f'{path}: a compact (SRVGGNetCompact) state_dict whose last conv has {cout} output channels; 12 (x2) '
+                           'and 48 (x4) run here' + (' (27 is x3, which is untested here)' if cout == 27 else ''))
+    return scale
+
+
 @torch.no_grad()
 def upscale(generator: torch.nn.Module, low_res: Tensor, halo: int = None,
             max_tile_pixels: int = MAX_TILE_PIXELS, scale: int = 4, precision: str = None, staged: bool = True,
@@ -255,7 +266,8 @@ def test(args: Namespace, model: object, device) -> None:
         raise SystemExit(f'torchsr test: {exc}')
     scale = 4
     if args.model.lower() == 'compact':  # a 16-conv and a 32-conv file both load: the depth is the file's
-        generator = model(num_conv=compact_num_conv(state)).to(device)
+        scale = compact_scale(state, path)  # ... and so is the scale: 12 output channels are x2, 48 are x4
+        generator = model(scale_factor=scale, num_conv=compact_num_conv(state)).to(device)
     elif args.model.lower() == 'esrgan':
         # a published RRDBNet file (BasicSR / Real-ESRGAN or xinntao/ESRGAN key names) or one of this package's: the number
         # of blocks (23, or 6 for the anime model) and the scale (x4, or x2 behind pixel_unshuffle) are the file's

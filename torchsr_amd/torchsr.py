@@ -156,6 +156,11 @@ def parse_args(argv=None) -> Namespace:
                             'before their ReLU, weighted 0.1, 0.1, 1, 1, 1, on ImageNet-normalised images -- as one fused node; '
                             '--model esrgan and --model compact, with either --discriminator.  The term\'s weight in the '
                             'generator loss stays 1')
+    train.add_argument('--scale', type=int, default=4, choices=(2, 4),
+                       help='the factor the generator enlarges by (default 4).  2: RRDBNet behind pixel_unshuffle(2) '
+                            '(RealESRGAN_x2plus; --model esrgan) or SRVGGNetCompact with 12 output channels (--model compact); the '
+                            'low-resolution side of every training pair is then the crop at 1/2.  --init-generator takes a file '
+                            'of this scale only')
     train.add_argument('--pretrain-epochs', type=int, default=PRE_EPOCHS)
     train.add_argument('--psnr-checkpoint', type=str, default=None)
     train.add_argument('--seed', type=int, default=0)
@@ -206,7 +211,7 @@ def parse_args(argv=None) -> Namespace:
     train.add_argument('--init-generator', type=str, default=None, metavar='PATH',
                        help='fine-tune: start the generator from this file -- every format test --weights takes, the published '
                             'RealESRGAN_x4plus / realesr-general-x4v3 files included, in any of their key namings.  The number of '
-                            'blocks (--model esrgan) or body convs (--model compact) is read off the file; an x2 file is refused.  '
+                            'blocks (--model esrgan) or body convs (--model compact) is read off the file; its scale must be --scale.  '
                             'Optimiser states start at zero.  A phase that finds a checkpoint of its own (--psnr-checkpoint, '
                             '--gan-checkpoint, <model>-{psnr,gan}-latest.pth) resumes from that instead and says so; with '
                             '--pretrain-epochs 0 the GAN phase starts from this file.  --model esrgan and --model compact')
@@ -259,6 +264,9 @@ def parse_args(argv=None) -> Namespace:
         if args.num_conv is not None and args.model.lower() != 'compact':
             parser.error(f'--num-conv sets the depth of --model compact; --model {args.model} has none')
         finetune = args.model.lower() in ('esrgan', 'compact')
+        if args.scale != 4 and not finetune:
+            parser.error(f'--scale {args.scale} trains with --model esrgan or --model compact; --model {args.model} is the '
+                         'reference\'s x4 network, whose two sub-pixel stages have no x2 form')
         for flag, value, why in (('--init-generator', args.init_generator, 'keeps no file format of a published model'),
                                  ('--init-discriminator', args.init_discriminator, 'keeps no file format of a published model'),
                                  ('--ema-decay', args.ema_decay, 'has BatchNorm buffers, which have no average defined'),
@@ -273,12 +281,21 @@ def parse_args(argv=None) -> Namespace:
             from torchsr_amd.compact.trainer import num_conv_conflict
             from torchsr_amd.test import compact_num_conv, load_generator_state
             try:
-                depth = compact_num_conv(load_generator_state(args.init_generator))
+                init_state = load_generator_state(args.init_generator)
+                depth = compact_num_conv(init_state)
             except Exception as exc:  # (an unreadable file, or not a compact state_dict)
                 parser.error(f'--init-generator {args.init_generator}: {exc}')
             if args.num_conv is not None and args.num_conv != depth:
                 parser.error(num_conv_conflict(args.num_conv, depth, args.init_generator))
             args.num_conv = depth
+            from torchsr_amd.esrgan.trainer import scale_conflict
+            from torchsr_amd.test import compact_scale
+            try:
+                file_scale = compact_scale(init_state, args.init_generator)
+            except RuntimeError as exc:
+                parser.error(f'--init-generator {exc}')
+            if file_scale != args.scale:
+                parser.error(scale_conflict(f'--init-generator {args.init_generator}', 'SRVGGNetCompact', file_scale, args.scale))
         if args.num_conv is None:
             args.num_conv = 32
     if args.function == 'train' and args.discriminator == 'unet' and args.model.lower() not in ('esrgan', 'compact'):
@@ -351,18 +368,18 @@ def main(argv=None) -> None:
     from torchsr_amd.dataset import initialize_datasets, initialize_device_datasets
     if args.device_data:
         train_loader, test_loader, train_len, test_len = initialize_device_datasets(
-            args.train_dir, device, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=4,
+            args.train_dir, device, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=args.scale,
             dataset_multiplier=args.dataset_multiplier, distributed=distributed, seed=args.seed,
             rank=max(int(args.rank), 0) if distributed else 0, world_size=int(args.world_size) if distributed else 1,
             degradation=args.degradation, gt_usm=args.gt_usm, poisson_prob=args.poisson_noise_prob, pair_pool=args.pair_pool,
             jpeg420_prob=args.jpeg_420_prob)
         if args.pair_pool and args.rank in [-1, 0]:
-            per_pair = 4 * 3 * (crop_size * crop_size + (crop_size // 4) ** 2)
+            per_pair = 4 * 3 * (crop_size * crop_size + (crop_size // args.scale) ** 2)
             print(f'training pair pool: {args.pair_pool} pairs per process, {args.pair_pool * per_pair / 1e6:.1f} MB of HBM; the first '
                   f'{args.pair_pool // args.batch_size} steps fill it')
     else:
         train_loader, test_loader, train_len, test_len = initialize_datasets(
-            args.train_dir, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=4,
+            args.train_dir, batch_size=args.batch_size, crop_size=crop_size, upscale_factor=args.scale,
             dataset_multiplier=args.dataset_multiplier, workers=args.data_workers, distributed=distributed,
             seed=args.seed)
     trainer = model_class(device, args, train_loader, test_loader, train_len, test_len, distributed)
