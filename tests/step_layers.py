@@ -232,11 +232,14 @@ for _c in ESRGAN_STEP_CONVS:
     _c['kernels'] = {_p: _EK[_c['id']][_p] for _p in _c['precisions']}
 
 # Conv-family launches of the ESRGAN step that have no row: the fused dense block (bf16) and the pack launches, and the tests that
-# hold them at 16 x 32 x 32
+# hold them at 16 x 32 x 32, and (the dense block) the tests of its every calling form: exact on integers, bounded element by element
 CONV_LAUNCHES_TESTED_ELSEWHERE = {
-    'rdb_kernel<0>': 'test_ops_gpu.py::test_fused_dense_block_forward[16-32-32]',
-    'rdb_kernel<1>': 'test_ops_gpu.py::test_fused_dense_block_backward[16-32-32]',
-    'rdb_pack_kernel': 'test_ops_gpu.py::test_fused_dense_block_forward[16-32-32]',
+    'rdb_kernel<0>': 'test_ops_gpu.py::test_fused_dense_block_forward[16-32-32], test_rdb_forms_gpu.py::test_forward_is_exact_on_integers_in_every_form, '
+                     '::test_forward_chain_of_three_blocks_out_of_one_pack, ::test_forward_within_the_derived_bound_of_fp64',
+    'rdb_kernel<1>': 'test_ops_gpu.py::test_fused_dense_block_backward[16-32-32], test_rdb_forms_gpu.py::test_backward_is_exact_on_integers_in_every_form, '
+                     '::test_backward_chain_of_three_blocks_out_of_one_pack, ::test_backward_within_the_derived_bound_of_fp64',
+    'rdb_pack_kernel': 'test_ops_gpu.py::test_fused_dense_block_forward[16-32-32], test_rdb_forms_gpu.py::test_forward_chain_of_three_blocks_out_of_one_pack, '
+                       '::test_backward_chain_of_three_blocks_out_of_one_pack (three blocks out of one launch)',
     'pack_table_kernel': 'test_pack_table_gpu.py::test_one_table_for_every_layer',
 }
 
