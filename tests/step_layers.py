@@ -108,8 +108,8 @@ for _id, _hw, _ci, _co, _s in _ED:
     for _tag, _n, _dw in (('pair', 32, True), ('adv', 16, False)):
         ESRGAN_STEP_CONVS.append(_ecase(f'{_id}.{_tag}', (_n, _hw, _hw, _ci, _co, 3, _s, 1), stats=True, in_act='lrelu' if _id == 'd2' else None, dw=_dw))
 # VGG19 features[:36] (srgan/loss.py): source + target forward at N = 32, the source's data gradient at N = 16.  Exact fp32:
-# layer by layer as in STEP_CONVS; bf16: the frozen stack keeps its inner activations as bf16 (functional._FrozenConvStack.
-# _forward_bf16s) -- bf16s = (H = W, Cin, Cout), out16: the forms of the forward output at this shape (0: fp32, in front of a
+# layer by layer as in STEP_CONVS; bf16: the frozen stack keeps its inner activations as bf16 (functional.
+# _stack_conv_fwd) -- bf16s = (H = W, Cin, Cout), out16: the forms of the forward output at this shape (0: fp32, in front of a
 # pool and at the end; 1: bf16), dx16: the data gradient's (fp32 only for the layer behind the 3 -> 64 one), masked: the layer's
 # input is a conv's ReLU output whose backward the data gradient applies (behind a pool the pool's backward has it)
 ESRGAN_STEP_CONVS += [

@@ -224,7 +224,7 @@ def run_dense_wgrad_case(case, dev, report, precision, u):
 
 # ------------------------------------------------------------------------------------- VGG19 under bf16: bf16-stored activations
 def run_bf16s_case(case, dev, report, precision, u):
-    """One VGG19 layer of the perceptual loss under autocast, as ``_FrozenConvStack._forward_bf16s`` / ``_backward_bf16s`` call
+    """One VGG19 layer of the perceptual loss under autocast, as ``functional._stack_conv_fwd`` / ``_stack_conv_dgrad`` call
     it: source + target forward as one batch of 32 on bf16-stored input, output fp32 (in front of a pool, the last layer) or
     bf16 (``out16``, every form the step uses at this shape); the source's data gradient at batch 16 from a bf16-stored gradient,
     masked by the layer's own (ReLU) input where a conv made it, written as bf16 (fp32 for the layer behind the 3 -> 64 one)."""

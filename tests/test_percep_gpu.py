@@ -262,8 +262,8 @@ def test_loss_against_the_reference(dev, percep, shape, seed, precision):
     try:
         layers, taps = percep._stack()
         for side in (16, 32):
-            assert F._bf16_tap_stack_ok(layers, taps, (4, side, side, 4)) == bf16
-        assert F._bf16_tap_stack_ok(layers, taps, (2 * shape[0], shape[2], shape[3], 4)) == bf16
+            assert F._bf16_stack_ok(layers, (4, side, side, 4), taps) == bf16
+        assert F._bf16_stack_ok(layers, (2 * shape[0], shape[2], shape[3], 4), taps) == bf16
         src, tgt = _images(shape, seed)
         got = percep(src.to(dev), tgt.to(dev)).item()
     finally:

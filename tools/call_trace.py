@@ -10,11 +10,13 @@ Each case runs eagerly (no hipGraph), from one seed, at the smallest sizes the s
 their golden inputs): three SRGAN steps, three ESRGAN steps in fp32 and three under autocast (bf16-storage VGG stack, fused dense
 blocks) -- the first packs lazily per layer, the later ones after the pack tables took over --, the VGG loss forward and backward
 alone, and Generator inference in fp32, bf16 and fp16: a first call, a second (every pack current) and a third after an in-place
-update of one weight that changes no value (that layer's repack and nothing else).  The digest of the library's sources is the
-first line.  Sizing calls made on the library handle directly (``*_ws_floats``) are not traced; the sizes they return are
+update of one weight that changes no value (that layer's repack and nothing else); then every calling form of the two
+perceptual-loss nodes (``frozen_stack_cases``), each followed by a ``=`` line with digests of its results.  The digest of the
+library's sources is the first line.  Sizing calls made on the library handle directly (``*_ws_floats``) are not traced; the sizes they return are
 (``nws`` arguments).  A swapped pair of non-null pointers is invisible here: the numerical tests cover that.
 """
 import ctypes as C
+import hashlib
 import os
 import sys
 from argparse import Namespace
@@ -81,6 +83,86 @@ def trainer(cls, dev, tag, disable_amp):
     return t
 
 
+def sha(t) -> str:
+    return hashlib.sha256(t.detach().cpu().reshape(-1).view(torch.uint8).numpy().tobytes()).hexdigest()[:16]
+
+
+def frozen_stack_cases(out, dev, vgg, src, tgt) -> None:
+    """Every path through the frozen-stack walk behind ``VGGLoss`` and ``PerceptualLoss`` (functional.frozen_conv_stack /
+    frozen_tap_stack): fp32 and bf16 storage, [source; target] and source alone, stack prefixes, the general LeakyReLU stack; each
+    once more on the direct kernels (``_dev.NO_WINO``) and, where bf16, on fp32 storage (``_dev.NO_BF16S``).  Behind each case a
+    ``=`` line with the sha256 of the result's and the input gradient's bytes: two trees must agree on those too."""
+    from torchsr_amd import _dev
+    from torchsr_amd import functional as F
+    from torchsr_amd._lib import ACT_LRELU
+    from torchsr_amd.layers import Conv2d, set_conv_precision
+    from torchsr_amd.realesrgan.loss import PerceptualLoss
+    percep = PerceptualLoss(weights='random').to(dev)
+    src4, tgt4 = F.to_nhwc(src, 4), F.to_nhwc(tgt, 4)
+    g = torch.Generator().manual_seed(5)
+    convs = [Conv2d(3, 16, 3, 1, 1, act=ACT_LRELU, slope=0.2), Conv2d(16, 32, 3, 1, 1, act=ACT_LRELU, slope=0.2)]
+    for m in convs:
+        with torch.no_grad():
+            m.weight.copy_(torch.randn(m.weight.shape, generator=g) * 0.2)
+            m.bias.copy_(torch.randn(m.bias.shape, generator=g) * 0.1)
+        m.to(dev).requires_grad_(False)
+    lrelu = [('conv', convs[0]), ('pool', None), ('conv', convs[1])]
+    small = torch.rand(2, 8, 12, 4, generator=g).to(dev)
+    small[..., 3] = 0
+    small_t = small.flip(0).contiguous()
+
+    def case(tag, fn, x=None):
+        """``fn(x)`` -> a loss (differentiated when ``x`` is given) or a list of tensors"""
+        res = []
+
+        def run():
+            leaf = None if x is None else x.clone().requires_grad_(True)
+            y = fn(leaf)
+            if leaf is not None:
+                y.backward()
+                res.extend([y, leaf.grad])
+            else:
+                res.extend(y)
+        traced(out, tag, run)
+        out.append('= ' + ' '.join(sha(t) for t in res))
+
+    def features_sum(layers, x, t):
+        fs, _ = F.frozen_conv_stack(x, t, layers)
+        return fs.sum()
+
+    def cases(precision, switch):
+        tag = precision + ('' if switch is None else ', ' + switch)
+        stack = vgg._stack()
+        with torch.no_grad():
+            tf_vgg = vgg.target_features(tgt)
+        case('VGG loss, source + target, ' + tag, lambda x: vgg.forward_nhwc(x, tgt4), src4)
+        case('VGG loss, source + target_features, ' + tag, lambda x: vgg.forward_nhwc(x, None, target_features=tf_vgg), src4)
+        if precision == 'bf16':
+            for k in (2, 4, 5):
+                case('frozen_conv_stack, layers[:%d], %s' % (k, tag), lambda x: features_sum(stack[:k], x, None), src4)
+        case('perceptual loss, target_features() alone, ' + tag, lambda _: percep.target_features(tgt))
+        tf_p = percep.target_features(tgt)
+        case('perceptual loss, source + target, ' + tag, lambda x: percep.forward_nhwc(x, tgt4), src4)
+        case('perceptual loss, source + target_features, ' + tag, lambda x: percep.forward_nhwc(x, None, target_features=tf_p), src4)
+        if precision == 'fp32':
+            case('LeakyReLU stack, source alone, ' + tag, lambda x: features_sum(lrelu, x, None), small)
+            case('LeakyReLU stack, source + target, ' + tag, lambda x: features_sum(lrelu, x, small_t), small)
+
+    for precision in ('fp32', 'bf16'):
+        set_conv_precision(vgg, precision)
+        set_conv_precision(percep, precision)
+        for switch in (None, 'NO_WINO') + (('NO_BF16S',) if precision == 'bf16' else ()):
+            was = None if switch is None else getattr(_dev, switch)
+            if switch is not None:
+                setattr(_dev, switch, True)
+            try:
+                cases(precision, switch)
+            finally:
+                if switch is not None:
+                    setattr(_dev, switch, was)
+    set_conv_precision(vgg, 'fp32')
+
+
 def main():
     from torchsr_amd.esrgan.trainer import ESRGANTrainer
     from torchsr_amd.srgan.generator import Generator
@@ -117,9 +199,11 @@ def main():
         traced(out, 'Generator inference, %s, after an in-place update of conv1' % precision,
                lambda: upscale(gen, low, precision=precision))
 
+    frozen_stack_cases(out, dev, vgg, src.detach(), tgt)
+
     with open(sys.argv[1], 'w') as f:
         f.write('\n'.join(out) + '\n')
-    print('%d calls in %d cases written to %s' % (sum(not ln.startswith('#') for ln in out), sum(ln.startswith('#') for ln in out) - 1,
+    print('%d calls in %d cases written to %s' % (sum(ln[0] not in '#=' for ln in out), sum(ln.startswith('#') for ln in out) - 1,
                                                   sys.argv[1]))
 
 

@@ -1990,216 +1990,16 @@ def maxpool2x2(x: Tensor) -> Tensor:
     return _MaxPool.apply(x)
 
 
-class _FrozenConvStack(Function):
-    """A frozen stack of ``conv3x3 + ReLU`` and ``MaxPool2d(2)`` layers as ONE autograd node: the VGG19 feature
-    extractor of the perceptual loss (srgan/loss.py:30-34,52-53: pretrained, ``requires_grad = False``, eval).
-
-    Forward: ``source`` and ``target`` (loss.py:52 and :53) go through the stack TOGETHER as one batch of 2N -- same
-    weights, twice the rows per launch (the 6x6 and 12x12 layers alone fill a quarter of the chip).  Backward: only
-    the source half is differentiated (the target is ``high_res.detach()``, srgan/trainer.py:455), weights take no
-    gradient, and every ReLU backward rides in the epilogue of the data gradient above it
-    (``srx_conv2d_bwd_data_act``) or in the max-pool backward (``srx_maxpool2x2_relu_bwd``): 16 data-gradient
-    launches and 4 pool launches, no elementwise passes besides the topmost ReLU.
-    """
-
-    @staticmethod
-    def forward(ctx, source: Tensor, target: Optional[Tensor], layers, *weights):
-        ctx.set_materialize_grads(False)
-        source = _chk(source, 'conv_stack.source')
-        n_src = source.shape[0]
-        x = source if target is None else torch.cat([source, _chk(target, 'conv_stack.target')], dim=0)
-        s = _stream()
-        ctx.bf16s = _bf16_stack_ok(layers, x.shape)
-        if ctx.bf16s:
-            return _FrozenConvStack._forward_bf16s(ctx, x, n_src, target is None, layers)
-        saved, plan = [x], []
-        for kind, conv in layers:
-            n, h, w, c = x.shape
-            if kind == 'pool':
-                y = torch.empty((n, h // 2, w // 2, c), dtype=torch.float32, device=x.device)
-                call('srx_maxpool2x2_fwd', _p(x), _p(y), n, h, w, c, s)
-                plan.append(('pool', None, None))
-            else:
-                st = conv._st
-                if st.act not in (ACT_RELU, ACT_LRELU) or st.stride != 1 or st.shuffle:
-                    raise RuntimeError('conv_stack: stride-1 conv + ReLU / LeakyReLU layers only')
-                d = st.desc(n, h, w)
-                y = torch.empty(st.out_shape(n, h, w), dtype=torch.float32, device=x.device)
-                b = None if conv.bias is None else _chk(conv.bias.detach(), 'conv_stack.bias')
-                # wide 3x3 layers: Winograd F(2x2, 3x3), 2.25x fewer fp32 multiplications (csrc/wino.hip)
-                wino = wino_layer_ok(st, d)
-                if wino:
-                    st.pack_wino(conv.weight, d, need_bwd=ctx.needs_input_grad[0])
-                    _wino_fwd(d, x, st.wino_fwd, b, y, None, s)
-                    plan.append(('conv', st, ('wino', st.wino_bwd)))
-                else:
-                    st.pack(conv.weight, d)
-                    _conv_fwd(d, _p(x), _p(st.wpk_fwd), _p(b), _p(y), x, s)
-                    plan.append(('conv', st, st.wpk_bwd))
-            saved.append(y)
-            x = y
-        ctx.plan, ctx.n_src = plan, n_src
-        ctx.masters = [conv.weight if kind == 'conv' else None for kind, conv in layers]
-        ctx.save_for_backward(*saved)
-        if target is None:
-            return x, None
-        fs, ft = x[:n_src], x[n_src:]
-        ctx.mark_non_differentiable(ft)
-        return fs, ft
-
-    @staticmethod
-    def _forward_bf16s(ctx, x: Tensor, n_src: int, single: bool, layers):
-        """Under autocast (``precision = 1`` on every layer; esrgan/trainer.py:461-467) the activations BETWEEN the convs are
-        stored as bf16 (csrc/gconv.hip "bf16 STORAGE"): the same bf16 products as before -- an operand is rounded once, by
-        its producer -- at half the bytes and without the loaders' fp32 -> bf16 conversion.  A conv in front of a pool and
-        the last conv write fp32: the pool compares fp32 values (as the recipe does), the features go to the fp32 MSE."""
-        L, s = _lib.lib(), _stream()
-        saved, plan = [x], []
-        need_bwd = ctx.needs_input_grad[0]
-        for i, (kind, conv) in enumerate(layers):
-            n, h, w, c = x.shape
-            to_f32 = i + 1 == len(layers) or layers[i + 1][0] == 'pool'
-            if kind == 'pool':
-                y = torch.empty((n, h // 2, w // 2, c), dtype=torch.bfloat16, device=x.device)
-                call('srx_maxpool2x2_fwd_to_bf16', _p(x), _p(y), n, h, w, c, s)
-                plan.append(('pool', None))
-            else:
-                st = conv._st
-                d = st.desc(n, h, w)
-                dref = C.byref(d)
-                y = torch.empty(st.out_shape(n, h, w), dtype=torch.float32 if to_f32 else torch.bfloat16, device=x.device)
-                b = None if conv.bias is None else _chk(conv.bias.detach(), 'conv_stack.bias')
-                if i == 0:   # the 3 -> 64 first layer: fp32 image in, its own kernel
-                    st.pack(conv.weight, d)
-                    call('srx_conv2d_fwd_first3_to_bf16', dref, _p(x), _p(st.wpk_fwd), _p(b), _p(y), s)
-                else:
-                    st.pack_bf16s(conv.weight, d, need_bwd)
-                    nws = L.srx_conv3x3_bf16s_ws_floats(dref, 0)
-                    ws = _ws(nws, x) if nws else None
-                    call('srx_conv3x3_bf16s_fwd', dref, _p(x), _p(st.bf16s_fwd), _p(b), 1, _p(y), 0 if to_f32 else 1, _p(ws), nws, s)
-                plan.append(('conv', st))
-            saved.append(y)
-            x = y
-        ctx.plan, ctx.n_src = plan, n_src
-        ctx.save_for_backward(*saved)
-        if single:
-            return x, None
-        fs, ft = x[:n_src], x[n_src:]
-        ctx.mark_non_differentiable(ft)
-        return fs, ft
-
-    @staticmethod
-    def _backward_bf16s(ctx, dfs: Tensor):
-        saved, plan, n = ctx.saved_tensors, ctx.plan, ctx.n_src
-        L, s = _lib.lib(), _stream()
-        g32 = _chk(dfs, 'conv_stack.grad')
-        top = saved[-1][:n]
-        g = torch.empty(g32.shape, dtype=torch.bfloat16, device=g32.device)
-        call('srx_act_bwd_from_out_to_bf16', _p(g32), _p(top), _p(g), g32.numel(), ACT_RELU, 0.0, s)
-        for i in range(len(plan) - 1, 0, -1):
-            kind, st = plan[i]
-            x = saved[i][:n]                      # this layer's input (source half)
-            if kind == 'pool':                    # x: the fp32 output of the conv + ReLU below
-                _, h, w, c = x.shape
-                dx = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-                call('srx_maxpool2x2_relu_bwd_bf16', _p(g), _p(x), _p(dx), n, h, w, c, s)
-                g = dx
-                continue
-            _, h, w, _c = x.shape
-            d = st.desc(n, h, w)
-            dref = C.byref(d)
-            fold = plan[i - 1][0] == 'conv'       # x = relu(conv below): that ReLU's backward on the way out
-            to_f32 = i == 1                       # the first layer's data gradient (3-channel kernel) reads fp32
-            dx = torch.empty(x.shape, dtype=torch.float32 if to_f32 else torch.bfloat16, device=x.device)
-            nws = L.srx_conv3x3_bf16s_ws_floats(dref, 1)
-            ws = _ws(nws, dx) if nws else None
-            call('srx_conv3x3_bf16s_bwd_data', dref, _p(g), _p(st.bf16s_bwd), _p(x) if fold else None, _p(dx), 0 if to_f32 else 1,
-                 _p(ws), nws, s)
-            g = dx
-        st = plan[0][1]
-        x = saved[0][:n]
-        _, h, w, _c = x.shape
-        dx = torch.empty_like(x)
-        _conv_dgrad(st.desc(n, h, w), _p(g), _p(st.wpk_bwd), _p(dx), x, s)
-        return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
-
-    @staticmethod
-    def backward(ctx, dfs: Tensor, _dft=None):
-        saved, plan, n = ctx.saved_tensors, ctx.plan, ctx.n_src
-        if dfs is None or not ctx.needs_input_grad[0]:
-            return (None,) * len(ctx.needs_input_grad)
-        if ctx.bf16s:
-            return _FrozenConvStack._backward_bf16s(ctx, dfs)
-        s = _stream()
-        g = _chk(dfs, 'conv_stack.grad')
-        # the topmost activation's backward is the only elementwise pass
-        top = saved[-1][:n]
-        kind, st, _ = plan[-1]
-        if kind == 'conv':
-            g2 = torch.empty_like(g)
-            call('srx_act_bwd_from_out', _p(g), _p(top), _p(g2), g.numel(), st.act, st.slope, s)
-            g = g2
-        for i in range(len(plan) - 1, -1, -1):
-            kind, st, wpk_bwd = plan[i]
-            x = saved[i][:n]                      # this layer's input (source half: batch-major, so a prefix)
-            below = plan[i - 1] if i > 0 else None
-            if kind == 'pool':
-                _, h, w, c = x.shape
-                dx = torch.empty_like(x)
-                # the pool's input is always a ReLU output in cfg 'E'; a pool fed by something else keeps the plain form
-                fn = 'srx_maxpool2x2_relu_bwd' if (below is not None and below[0] == 'conv' and below[1].act == ACT_RELU) \
-                    else 'srx_maxpool2x2_bwd'
-                call(fn, _p(g), _p(x), _p(dx), n, h, w, c, s)
-                if fn == 'srx_maxpool2x2_bwd' and below is not None and below[0] == 'conv':
-                    g2 = torch.empty_like(dx)
-                    call('srx_act_bwd_from_out', _p(dx), _p(x), _p(g2), dx.numel(), below[1].act, below[1].slope, s)
-                    dx = g2
-                g = dx
-                continue
-            _, h, w, _c = x.shape
-            fold = below is not None and below[0] == 'conv'   # x = act(conv below): fold that activation's backward in
-            wino = isinstance(wpk_bwd, tuple)
-            g, _ = _layer_dgrad(st, st.desc(n, h, w), ctx.masters[i], wino, wpk_bwd[1] if wino else None, None if wino else wpk_bwd,
-                                g, x, below[1] if fold else None, s)
-        return (g, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
-
-
-def _bf16_stack_ok(layers, shape) -> bool:
-    """May this frozen stack keep its inner activations as bf16 (``_FrozenConvStack._forward_bf16s``)?  Every conv multiplies
-    bf16 products (autocast), starts with the 3 -> 64 layer, every other conv is a 3x3 / stride 1 / pad 1 + ReLU layer with
-    channel counts that are multiples of 64, pools sit between convs and the stack ends with a conv."""
-    if _dev.NO_BF16S or len(layers) < 2 or layers[0][0] != 'conv' or layers[-1][0] != 'conv' or layers[1][0] != 'conv':
-        return False
-    L = _lib.lib()
-    n, h, w, _c = shape
-    for i, (kind, conv) in enumerate(layers):
-        if kind == 'pool':
-            if layers[i - 1][0] != 'conv' or layers[i + 1][0] != 'conv' or h % 2 or w % 2:
-                return False
-            h, w = h // 2, w // 2
-            continue
-        st = conv._st
-        if st.precision != 1 or st.act != ACT_RELU or st.stride != 1 or st.shuffle or st.k != 3 or st.pad != 1:
-            return False
-        if i == 0:
-            if st.cin > 4 or st.cout != 64:
-                return False
-        elif L.srx_conv3x3_bf16s_applicable(C.byref(st.desc(n, h, w))) != 1:
-            return False
-    return True
-
-
-def frozen_conv_stack(source: Tensor, target: Optional[Tensor], layers):
-    """``layers``: [('conv', layers.Conv2d) | ('pool', None)].  Returns ``(features(source), features(target))``."""
-    weights = [p for _, m in layers if m is not None for p in (m.weight, m.bias) if p is not None]
-    if any(p.requires_grad for p in weights):
-        raise RuntimeError('frozen_conv_stack: the stack must be frozen (requires_grad = False on every parameter)')
-    return _FrozenConvStack.apply(source, target, layers, *weights)
-
-
-def _bf16_tap_stack_ok(layers, taps, shape) -> bool:
-    """``_bf16_stack_ok`` for a stack whose tap convs carry no activation of their own (``_FrozenTapStack``): the same
-    conditions on the same descriptors, a tap's ReLU being the pool's."""
+# --------------------------------------------------------------------------- frozen conv stacks (the perceptual losses)
+# ONE walk over a frozen ``[('conv', layers.Conv2d) | ('pool', None)]`` stack behind both perceptual-loss nodes: per conv the
+# choice between the bf16-storage kernels, Winograd and the direct kernel, the rule for which layer writes fp32, and the
+# data-gradient chain with the activation backwards folded in.  What differs between the nodes -- the pools, the entry into the
+# backward, the loss -- stays in ``_FrozenConvStack`` / ``_FrozenTapStack`` and is passed in.
+def _bf16_stack_ok(layers, shape, taps=()) -> bool:
+    """May this frozen stack keep its inner activations as bf16 (``_stack_conv_fwd``)?  Every conv multiplies bf16 products
+    (autocast), the stack starts with the 3 -> 64 layer, every other conv is a 3x3 / stride 1 / pad 1 layer with channel counts that
+    are multiples of 64, pools sit between convs and the stack ends with a conv.  Every conv carries a fused ReLU, except the
+    convs at the positions ``taps`` (``_FrozenTapStack``), which carry none: a tap's ReLU is the pool's."""
     if _dev.NO_BF16S or len(layers) < 2 or layers[0][0] != 'conv' or layers[-1][0] != 'conv' or layers[1][0] != 'conv':
         return False
     L = _lib.lib()
@@ -2221,6 +2021,197 @@ def _bf16_tap_stack_ok(layers, taps, shape) -> bool:
     return True
 
 
+def _stack_writes_f32(layers, i: int) -> bool:
+    """THE rule for a conv's output under bf16 storage: the last conv and a conv in front of a pool write fp32 -- the features go
+    to an fp32 loss, a pool compares fp32 values (as the recipe does) --, every other conv writes bf16.  In a tap stack these are
+    exactly the taps (``_tap_stack_check``)."""
+    return i + 1 == len(layers) or layers[i + 1][0] == 'pool'
+
+
+def _bf16s_ws(dref, backward: int, like: Tensor):
+    """``(workspace pointer, its size)`` of a bf16-storage conv's forward (0) or data gradient (1)."""
+    nws = _lib.lib().srx_conv3x3_bf16s_ws_floats(dref, backward)
+    return (_p(_ws(nws, like)) if nws else None), nws
+
+
+def _stack_conv_fwd(layers, i: int, x: Tensor, relu: bool, to_f32: bool, bf16s: bool, need_bwd: bool, who: str, s):
+    """The conv at position ``i`` of a frozen stack on ``x``: pack, choose, launch.  ``bf16s`` (``_bf16_stack_ok``): the
+    activations BETWEEN the convs are stored as bf16 (csrc/gconv.hip "bf16 STORAGE") -- the same bf16 products as with fp32
+    storage, an operand being rounded once, by its producer, at half the bytes and without the loaders' fp32 -> bf16 conversion;
+    ``relu``: the ReLU is fused (there the epilogue is an argument; elsewhere it is the layer's own ``act``); ``to_f32``: what the
+    conv writes.  Returns the output and the layer's plan entry ``('conv', state, packed weights of the data gradient)``: the
+    fp32 paths capture them now (``('wino', U)`` or the direct pack), the bf16-storage path reads its own at backward time (None)."""
+    conv = layers[i][1]
+    st = conv._st
+    n, h, w, _c = x.shape
+    d = st.desc(n, h, w)
+    dref = C.byref(d)
+    y = torch.empty(st.out_shape(n, h, w), dtype=torch.float32 if to_f32 else torch.bfloat16, device=x.device)
+    b = None if conv.bias is None else _chk(conv.bias.detach(), who + '.bias')
+    if bf16s and i == 0:   # the 3 -> 64 first layer: fp32 image in, its own kernel
+        st.pack(conv.weight, d)
+        call('srx_conv2d_fwd_first3_to_bf16', dref, _p(x), _p(st.wpk_fwd), _p(b), _p(y), s)
+        return y, ('conv', st, None)
+    if bf16s:
+        st.pack_bf16s(conv.weight, d, need_bwd)
+        ws, nws = _bf16s_ws(dref, 0, x)
+        call('srx_conv3x3_bf16s_fwd', dref, _p(x), _p(st.bf16s_fwd), _p(b), 1 if relu else 0, _p(y), 0 if to_f32 else 1, ws, nws, s)
+        return y, ('conv', st, None)
+    if wino_layer_ok(st, d):   # wide 3x3 layers: Winograd F(2x2, 3x3), 2.25x fewer fp32 multiplications (csrc/wino.hip)
+        st.pack_wino(conv.weight, d, need_bwd=need_bwd)
+        _wino_fwd(d, x, st.wino_fwd, b, y, None, s)
+        return y, ('conv', st, ('wino', st.wino_bwd))
+    st.pack(conv.weight, d)
+    _conv_fwd(d, _p(x), _p(st.wpk_fwd), _p(b), _p(y), x, s)
+    return y, ('conv', st, st.wpk_bwd)
+
+
+def _stack_conv_dgrad(plan, i: int, g: Tensor, x: Tensor, master: Tensor, bf16s: bool, s) -> Tensor:
+    """The data gradient of the conv at position ``i`` from the plan of ``_stack_conv_fwd``; ``x``: the conv's input (source
+    half).  A conv right below made ``x = act(conv)``: that activation's backward is folded in on the way out."""
+    _, st, wpk_bwd = plan[i]
+    n, h, w, _c = x.shape
+    d = st.desc(n, h, w)
+    below = plan[i - 1][1] if i > 0 and plan[i - 1][0] == 'conv' else None
+    if not bf16s:
+        wino = isinstance(wpk_bwd, tuple)
+        return _layer_dgrad(st, d, master, wino, wpk_bwd[1] if wino else None, None if wino else wpk_bwd, g, x, below, s)[0]
+    if i == 0:   # the 3 -> 64 first layer: the direct kernel on an fp32 gradient
+        dx = torch.empty_like(x)
+        _conv_dgrad(d, _p(g), _p(st.wpk_bwd), _p(dx), x, s)
+        return dx
+    dref = C.byref(d)
+    to_f32 = i == 1   # ... which layer 1 therefore writes as fp32
+    dx = torch.empty(x.shape, dtype=torch.float32 if to_f32 else torch.bfloat16, device=x.device)
+    ws, nws = _bf16s_ws(dref, 1, dx)
+    call('srx_conv3x3_bf16s_bwd_data', dref, _p(g), _p(st.bf16s_bwd), _p(x) if below is not None else None, _p(dx), 0 if to_f32 else 1,
+         ws, nws, s)
+    return dx
+
+
+def _stack_forward(x: Tensor, layers, taps, bf16s: bool, need_bwd: bool, pool, who: str, s):
+    """Every layer of a frozen stack on ``x``; ``pool(i, x) -> y`` launches the node's own pool at position ``i``; the convs at
+    the positions ``taps`` write their pre-activation.  Returns ``(saved, plan)``: every layer's input and the last output, and
+    one entry per layer for ``_stack_backward``."""
+    saved, plan = [x], []
+    for i, (kind, _conv) in enumerate(layers):
+        if kind == 'pool':
+            x = pool(i, x)
+            plan.append(('pool', None, None))
+        else:
+            x, entry = _stack_conv_fwd(layers, i, x, i not in taps, not bf16s or _stack_writes_f32(layers, i), bf16s, need_bwd, who, s)
+            plan.append(entry)
+        saved.append(x)
+    return saved, plan
+
+
+def _stack_backward(g: Tensor, saved, plan, masters, n: int, bf16s: bool, pool_bwd, s) -> Tensor:
+    """The data-gradient chain of the source half (the first ``n`` images: batch-major, so a prefix) from the gradient ``g`` of
+    the last conv's output, pre-activation; ``pool_bwd(i, g, x) -> dx`` launches the node's own pool backward on the pool's input."""
+    for i in range(len(plan) - 1, -1, -1):
+        x = saved[i][:n]
+        g = pool_bwd(i, g, x) if plan[i][0] == 'pool' else _stack_conv_dgrad(plan, i, g, x, masters[i], bf16s, s)
+    return g
+
+
+def _stack_weights(layers, who: str):
+    weights = [p for _, m in layers if m is not None for p in (m.weight, m.bias) if p is not None]
+    if any(p.requires_grad for p in weights):
+        raise RuntimeError(who + ': the stack must be frozen (requires_grad = False on every parameter)')
+    return weights
+
+
+class _FrozenConvStack(Function):
+    """A frozen stack of ``conv3x3 + ReLU`` and ``MaxPool2d(2)`` layers as ONE autograd node: the VGG19 feature
+    extractor of the perceptual loss (srgan/loss.py:30-34,52-53: pretrained, ``requires_grad = False``, eval).
+
+    Forward: ``source`` and ``target`` (loss.py:52 and :53) go through the stack TOGETHER as one batch of 2N -- same
+    weights, twice the rows per launch (the 6x6 and 12x12 layers alone fill a quarter of the chip).  Backward: only
+    the source half is differentiated (the target is ``high_res.detach()``, srgan/trainer.py:455), weights take no
+    gradient, and every ReLU backward rides in the epilogue of the data gradient above it or in the max-pool backward: 16
+    data-gradient launches and 4 pool launches, no elementwise passes besides the topmost ReLU.
+
+    The convs and their data gradients are the shared walk's (``_stack_forward`` / ``_stack_backward``), under autocast on bf16
+    storage (``_bf16_stack_ok``).  This node's own: the ``(fs, ft)`` views it returns, the plain pools, the topmost
+    activation's backward, and in fp32 the general stack -- LeakyReLU convs, a pool whose input is no ReLU output.
+    """
+
+    @staticmethod
+    def forward(ctx, source: Tensor, target: Optional[Tensor], layers, *weights):
+        ctx.set_materialize_grads(False)
+        source = _chk(source, 'conv_stack.source')
+        n_src = source.shape[0]
+        x = source if target is None else torch.cat([source, _chk(target, 'conv_stack.target')], dim=0)
+        s = _stream()
+        ctx.bf16s = bf16s = _bf16_stack_ok(layers, x.shape)
+        for kind, conv in layers:
+            if kind == 'conv' and (conv._st.act not in (ACT_RELU, ACT_LRELU) or conv._st.stride != 1 or conv._st.shuffle):
+                raise RuntimeError('conv_stack: stride-1 conv + ReLU / LeakyReLU layers only')
+
+        def pool(i: int, x: Tensor) -> Tensor:
+            n, h, w, c = x.shape
+            y = torch.empty((n, h // 2, w // 2, c), dtype=torch.bfloat16 if bf16s else torch.float32, device=x.device)
+            call('srx_maxpool2x2_fwd_to_bf16' if bf16s else 'srx_maxpool2x2_fwd', _p(x), _p(y), n, h, w, c, s)
+            return y
+
+        saved, ctx.plan = _stack_forward(x, layers, (), bf16s, ctx.needs_input_grad[0], pool, 'conv_stack', s)
+        ctx.n_src = n_src
+        ctx.masters = [conv.weight if kind == 'conv' else None for kind, conv in layers]
+        ctx.save_for_backward(*saved)
+        x = saved[-1]
+        if target is None:
+            return x, None
+        fs, ft = x[:n_src], x[n_src:]
+        ctx.mark_non_differentiable(ft)
+        return fs, ft
+
+    @staticmethod
+    def backward(ctx, dfs: Tensor, _dft=None):
+        saved, plan, n, bf16s = ctx.saved_tensors, ctx.plan, ctx.n_src, ctx.bf16s
+        if dfs is None or not ctx.needs_input_grad[0]:
+            return (None,) * len(ctx.needs_input_grad)
+        s = _stream()
+        g = _chk(dfs, 'conv_stack.grad')
+        # the topmost activation's backward is the only elementwise pass
+        top = saved[-1][:n]
+        kind, st, _ = plan[-1]
+        if bf16s:
+            g2 = torch.empty(g.shape, dtype=torch.bfloat16, device=g.device)
+            call('srx_act_bwd_from_out_to_bf16', _p(g), _p(top), _p(g2), g.numel(), ACT_RELU, 0.0, s)
+            g = g2
+        elif kind == 'conv':
+            g2 = torch.empty_like(g)
+            call('srx_act_bwd_from_out', _p(g), _p(top), _p(g2), g.numel(), st.act, st.slope, s)
+            g = g2
+
+        def pool_bwd(i: int, g: Tensor, x: Tensor) -> Tensor:
+            _, h, w, c = x.shape
+            if bf16s:                             # x: the fp32 output of the conv + ReLU below
+                dx = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+                call('srx_maxpool2x2_relu_bwd_bf16', _p(g), _p(x), _p(dx), n, h, w, c, s)
+                return dx
+            below = plan[i - 1][1] if i > 0 and plan[i - 1][0] == 'conv' else None
+            dx = torch.empty_like(x)
+            # the pool's input is always a ReLU output in cfg 'E'; a pool fed by something else keeps the plain form
+            if below is not None and below.act == ACT_RELU:
+                call('srx_maxpool2x2_relu_bwd', _p(g), _p(x), _p(dx), n, h, w, c, s)
+                return dx
+            call('srx_maxpool2x2_bwd', _p(g), _p(x), _p(dx), n, h, w, c, s)
+            if below is None:
+                return dx
+            g2 = torch.empty_like(dx)
+            call('srx_act_bwd_from_out', _p(dx), _p(x), _p(g2), dx.numel(), below.act, below.slope, s)
+            return g2
+
+        g = _stack_backward(g, saved, plan, ctx.masters, n, bf16s, pool_bwd, s)
+        return (g, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
+
+
+def frozen_conv_stack(source: Tensor, target: Optional[Tensor], layers):
+    """``layers``: [('conv', layers.Conv2d) | ('pool', None)].  Returns ``(features(source), features(target))``."""
+    return _FrozenConvStack.apply(source, target, layers, *_stack_weights(layers, 'frozen_conv_stack'))
+
+
 def _tap_stack_check(layers, taps) -> None:
     """The shape ``_FrozenTapStack`` is built for (VGG19 cfg 'E' with Real-ESRGAN's taps): 3x3 / stride 1 convs with a fused ReLU,
     except the taps, which write their pre-activation and are the last layer or sit in front of a pool; every pool behind a tap."""
@@ -2237,18 +2228,19 @@ def _tap_stack_check(layers, taps) -> None:
             raise RuntimeError('tap_stack: stride-1 convs, act NONE at the taps and a fused ReLU everywhere else')
         if i in taps and i != last and layers[i + 1][0] != 'pool':
             raise RuntimeError('tap_stack: a tap is the last layer or sits in front of a pool')
+    # hence the taps are the convs that write fp32 under bf16 storage: the walk states that rule once, for both nodes
+    assert all((i in taps) == _stack_writes_f32(layers, i) for i, (kind, _) in enumerate(layers) if kind == 'conv')
 
 
 def _tap_stack_run(x: Tensor, n_src: int, layers, taps, tfeats, loss: Optional[Tensor], need_bwd: bool):
     """The forward launches of ``_FrozenTapStack`` on the normalised batch ``x`` (``[source; target]`` when it holds
-    ``2 * n_src`` images).  ``loss`` given: every tap's ``weight * mean|fs - ft|`` is accumulated into it, ``ft`` being the target
-    half or ``tfeats[k]``.  Returns ``(saved, plan, bf16s)``: every layer's input and the last output, as ``_FrozenConvStack``."""
+    ``2 * n_src`` images): the shared walk with this node's pools.  ``loss`` given: every tap's ``weight * mean|fs - ft|`` is
+    accumulated into it, ``ft`` being the target half or ``tfeats[k]``.  Returns ``(saved, plan, bf16s)``, as ``_stack_forward``."""
     L, s = _lib.lib(), _stream()
     pair = x.shape[0] == 2 * n_src
-    bf16s = _bf16_tap_stack_ok(layers, taps, x.shape)
-    act16 = torch.bfloat16 if bf16s else torch.float32
+    bf16s = _bf16_stack_ok(layers, x.shape, taps)
     ws = _ws(1024, x) if loss is not None else None
-    saved, plan, k, first = [x], [], 0, 1
+    k, first = 0, 1
 
     def tap_l1(a: Tensor, b: Tensor, weight: float) -> None:
         nonlocal first
@@ -2257,50 +2249,24 @@ def _tap_stack_run(x: Tensor, n_src: int, layers, taps, tfeats, loss: Optional[T
         call('srx_tap_l1_fwd', _p(a), _p(b), a.numel(), weight, _p(loss), 0 if first else 1, _p(ws), s)
         first = 0
 
-    for i, (kind, conv) in enumerate(layers):
+    def pool(i: int, x: Tensor) -> Tensor:                  # x: the fp32 pre-activation of the tap conv below
+        nonlocal k, first
         n, h, w, c = x.shape
-        if kind == 'pool':                                  # x: the fp32 pre-activation of the tap conv below
-            y = torch.empty((n, h // 2, w // 2, c), dtype=act16, device=x.device)
-            fused = loss is not None and pair
-            call('srx_maxpool2x2_relu_fwd_tap', _p(x), _p(y), 1 if bf16s else 0, n_src, n, h, w, c, _p(ws) if fused else None, s)
-            if fused:
-                call('srx_tap_l1_finalize', _p(ws), L.srx_tap_blocks(n_src, h, w, c), taps[i - 1] / float(n_src * h * w * c), _p(loss),
-                     0 if first else 1, s)
-                first = 0
-            elif loss is not None:
-                tap_l1(x[:n_src], tfeats[k], taps[i - 1])
-            k += 1
-            plan.append(('pool', None, None))
-        else:
-            st = conv._st
-            d = st.desc(n, h, w)
-            dref = C.byref(d)
-            tap = i in taps
-            to_f32 = tap or not bf16s
-            y = torch.empty(st.out_shape(n, h, w), dtype=torch.float32 if to_f32 else torch.bfloat16, device=x.device)
-            b = None if conv.bias is None else _chk(conv.bias.detach(), 'tap_stack.bias')
-            if bf16s and i == 0:   # the 3 -> 64 first layer: fp32 image in, its own kernel
-                st.pack(conv.weight, d)
-                call('srx_conv2d_fwd_first3_to_bf16', dref, _p(x), _p(st.wpk_fwd), _p(b), _p(y), s)
-                plan.append(('conv', st, None))
-            elif bf16s:
-                st.pack_bf16s(conv.weight, d, need_bwd)
-                nws = L.srx_conv3x3_bf16s_ws_floats(dref, 0)
-                cws = _ws(nws, x) if nws else None
-                call('srx_conv3x3_bf16s_fwd', dref, _p(x), _p(st.bf16s_fwd), _p(b), 0 if tap else 1, _p(y), 0 if to_f32 else 1, _p(cws),
-                     nws, s)
-                plan.append(('conv', st, None))
-            elif wino_layer_ok(st, d):
-                st.pack_wino(conv.weight, d, need_bwd=need_bwd)
-                _wino_fwd(d, x, st.wino_fwd, b, y, None, s)
-                plan.append(('conv', st, ('wino', st.wino_bwd)))
-            else:
-                st.pack(conv.weight, d)
-                _conv_fwd(d, _p(x), _p(st.wpk_fwd), _p(b), _p(y), x, s)
-                plan.append(('conv', st, st.wpk_bwd))
-        saved.append(y)
-        x = y
+        y = torch.empty((n, h // 2, w // 2, c), dtype=torch.bfloat16 if bf16s else torch.float32, device=x.device)
+        fused = loss is not None and pair
+        call('srx_maxpool2x2_relu_fwd_tap', _p(x), _p(y), 1 if bf16s else 0, n_src, n, h, w, c, _p(ws) if fused else None, s)
+        if fused:
+            call('srx_tap_l1_finalize', _p(ws), L.srx_tap_blocks(n_src, h, w, c), taps[i - 1] / float(n_src * h * w * c), _p(loss),
+                 0 if first else 1, s)
+            first = 0
+        elif loss is not None:
+            tap_l1(x[:n_src], tfeats[k], taps[i - 1])
+        k += 1
+        return y
+
+    saved, plan = _stack_forward(x, layers, taps, bf16s, need_bwd, pool, 'tap_stack', s)
     if loss is not None:
+        x = saved[-1]
         tap_l1(x[:n_src], x[n_src:] if pair else tfeats[k], taps[len(layers) - 1])
     return saved, plan, bf16s
 
@@ -2312,12 +2278,12 @@ class _FrozenTapStack(Function):
     In cfg 'E' the taps are the last conv in front of each pool plus the last conv, and ``maxpool(relu(x)) == relu(maxpool(x))``
     bit for bit: a tap conv writes its pre-activation (epilogue act NONE), the pool behind it applies the ReLU after the maximum
     and sums ``|fs - ft|`` over the windows it has loaded anyway (``srx_maxpool2x2_relu_fwd_tap``); the other convs keep their
-    fused ReLU.  The convs, their plans and the choice between the fp32 path (Winograd where ``wino_layer_ok``) and the
-    bf16-storage path are ``_FrozenConvStack``'s; there the tap layers are exactly the ones that write fp32.
+    fused ReLU.  The convs, their plans and the choice between Winograd, the direct kernel and the bf16-storage path are the
+    shared walk's (``_stack_forward`` / ``_stack_backward``); under bf16 storage the taps are exactly the layers that write fp32.
 
-    Backward, source half only: the loss gradient enters at the last tap (``srx_tap_l1_bwd_top``), descends through the same
-    data-gradient calls with the non-tap ReLUs folded, and every pool backward adds its tap's L1 gradient in the same pass
-    (``srx_maxpool2x2_relu_bwd_tap``)."""
+    This node's own: the normalisation in front, the tap pools with the L1 terms, and the backward, source half only: the loss
+    gradient enters at the last tap (``srx_tap_l1_bwd_top``), descends through the walk's data-gradient calls with the non-tap
+    ReLUs folded, and every pool backward adds its tap's L1 gradient in the same pass (``srx_maxpool2x2_relu_bwd_tap``)."""
 
     @staticmethod
     def forward(ctx, source: Tensor, target: Optional[Tensor], layers, taps, mean, inv_std, tfeats, *weights):
@@ -2346,7 +2312,7 @@ class _FrozenTapStack(Function):
         plan, n, taps, bf16s = ctx.plan, ctx.n_src, ctx.taps, ctx.bf16s
         saved = ctx.saved_tensors[:len(plan) + 1]
         tfeats = ctx.saved_tensors[len(plan) + 1:]
-        L, s = _lib.lib(), _stream()
+        s = _stream()
         gscale = _chk(g, 'tap_stack.grad')
         k = len(taps) - 1                          # the tap whose L1 term enters next, topmost first
 
@@ -2358,45 +2324,25 @@ class _FrozenTapStack(Function):
         g = torch.empty(fs.shape, dtype=torch.bfloat16 if bf16s else torch.float32, device=fs.device)
         call('srx_tap_l1_bwd_top', _p(fs), _p(target_of(top)), _p(g), 1 if bf16s else 0, taps[len(plan) - 1] / float(fs.numel()),
              _p(gscale), fs.numel(), s)
-        for i in range(len(plan) - 1, -1, -1):
-            kind, st, wpk_bwd = plan[i]
-            x = saved[i][:n]                       # this layer's input (source half: batch-major, so a prefix)
+
+        def pool_bwd(i: int, g: Tensor, x: Tensor) -> Tensor:   # x: the fp32 pre-activation of tap i - 1
+            nonlocal k
+            k -= 1
             _, h, w, c = x.shape
-            if kind == 'pool':                     # x: the fp32 pre-activation of tap i - 1
-                k -= 1
-                dx = torch.empty(x.shape, dtype=g.dtype, device=x.device)
-                call('srx_maxpool2x2_relu_bwd_tap', _p(g), 1 if bf16s else 0, _p(x), _p(target_of(saved[i])), _p(dx), 1 if bf16s else 0,
-                     taps[i - 1] / float(x.numel()), _p(gscale), n, h, w, c, s)
-                g = dx
-                continue
-            d = st.desc(n, h, w)
-            fold = i > 0 and plan[i - 1][0] == 'conv'   # x = relu(conv below), never a tap: fold that ReLU's backward in
-            if not bf16s:
-                wino = isinstance(wpk_bwd, tuple)
-                g, _ = _layer_dgrad(st, d, ctx.masters[i], wino, wpk_bwd[1] if wino else None, None if wino else wpk_bwd, g, x,
-                                    plan[i - 1][1] if fold else None, s)
-            elif i == 0:
-                dx = torch.empty_like(x)
-                _conv_dgrad(d, _p(g), _p(st.wpk_bwd), _p(dx), x, s)
-                g = dx
-            else:
-                dref = C.byref(d)
-                to_f32 = i == 1                    # the first layer's data gradient (3-channel kernel) reads fp32
-                dx = torch.empty(x.shape, dtype=torch.float32 if to_f32 else torch.bfloat16, device=x.device)
-                nws = L.srx_conv3x3_bf16s_ws_floats(dref, 1)
-                ws = _ws(nws, dx) if nws else None
-                call('srx_conv3x3_bf16s_bwd_data', dref, _p(g), _p(st.bf16s_bwd), _p(x) if fold else None, _p(dx), 0 if to_f32 else 1,
-                     _p(ws), nws, s)
-                g = dx
+            dx = torch.empty(x.shape, dtype=g.dtype, device=x.device)
+            call('srx_maxpool2x2_relu_bwd_tap', _p(g), 1 if bf16s else 0, _p(x), _p(target_of(saved[i])), _p(dx), 1 if bf16s else 0,
+                 taps[i - 1] / float(x.numel()), _p(gscale), n, h, w, c, s)
+            return dx
+
+        # (a conv below a conv is never a tap: the activation the walk folds into a data gradient is always a ReLU)
+        g = _stack_backward(g, saved, plan, ctx.masters, n, bf16s, pool_bwd, s)
         dsrc = torch.empty_like(g)
         call('srx_normalize_nhwc4_bwd', _p(g), _p(dsrc), n, g.shape[1], g.shape[2], ctx.inv_std, s)
         return (dsrc,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
 def _tap_stack_args(layers, taps, mean, std):
-    weights = [p for _, m in layers if m is not None for p in (m.weight, m.bias) if p is not None]
-    if any(p.requires_grad for p in weights):
-        raise RuntimeError('frozen_tap_stack: the stack must be frozen (requires_grad = False on every parameter)')
+    weights = _stack_weights(layers, 'frozen_tap_stack')
     taps = {int(i): float(wt) for i, wt in taps.items()}
     _tap_stack_check(layers, taps)
     f3 = C.c_float * 3

@@ -11,13 +11,13 @@ the ``train`` command line refuses to start unless ``--vgg-weights random`` asks
 """
 import os
 import warnings
-from typing import Optional
+from typing import List, Optional
 
 import torch
 from torch import nn, Tensor
 
 from .. import functional as F
-from ..layers import ACT_RELU, Conv2d, Marker
+from ..layers import ACT_NONE, ACT_RELU, Conv2d, Marker
 
 # torchvision.models.vgg cfgs['E']
 VGG19_CFG = [64, 64, 'M', 128, 128, 'M', 256, 256, 256, 256, 'M', 512, 512, 512, 512, 'M', 512, 512, 512, 512, 'M']
@@ -29,16 +29,36 @@ class MaxPool2x2(nn.Module):
         return F.maxpool2x2(x)
 
 
-def make_vgg19_features(feature_layer: int = 36) -> nn.Sequential:
-    """``vgg19().features[:feature_layer]`` with the same child indices (conv at 0,2,5,...)."""
-    layers, cin = [], 3
+def vgg19_conv_names() -> List[str]:
+    """``conv1_1 .. conv5_4`` in cfg 'E' order."""
+    names, block, k = [], 1, 0
+    for v in VGG19_CFG:
+        if v == 'M':
+            block, k = block + 1, 0
+        else:
+            k += 1
+            names.append(f'conv{block}_{k}')
+    return names
+
+
+def vgg19_layers(taps=()) -> list:
+    """The children of ``vgg19().features`` with the same indices (conv at 0, 2, 5, ...).  A conv named in ``taps`` writes its
+    pre-activation (act NONE; the ``Marker`` behind it stands for the ReLU the pool applies), every other conv has the ReLU fused."""
+    names, layers, cin = iter(vgg19_conv_names()), [], 3
     for v in VGG19_CFG:
         if v == 'M':
             layers.append(MaxPool2x2())
         else:
-            layers += [Conv2d(cin, v, kernel_size=3, stride=1, padding=1, act=ACT_RELU), Marker('ReLU (conv epilogue)')]
+            tap = next(names) in taps
+            layers += [Conv2d(cin, v, kernel_size=3, stride=1, padding=1, act=ACT_NONE if tap else ACT_RELU),
+                       Marker('ReLU (in the pool behind a tap)' if tap else 'ReLU (conv epilogue)')]
             cin = v
-    layers = layers[:feature_layer]
+    return layers
+
+
+def make_vgg19_features(feature_layer: int = 36) -> nn.Sequential:
+    """``vgg19().features[:feature_layer]`` with the same child indices (conv at 0,2,5,...)."""
+    layers = vgg19_layers()[:feature_layer]
     if layers and isinstance(layers[-1], Conv2d):
         raise RuntimeError('feature_layer must not cut between a conv and its ReLU')
     return nn.Sequential(*layers)
@@ -53,6 +73,38 @@ def _find_weights(path: Optional[str]) -> Optional[str]:
     return None
 
 
+def load_frozen_vgg19(features: nn.Sequential, weights: Optional[str], seed: int, who: str) -> bool:
+    """Fill ``features`` (children indexed as ``vgg19().features``) from the state_dict at ``weights`` (default:
+    ``$TORCHSR_VGG19_WEIGHTS``, then the torch hub cache), or -- ``'random'``, or no file, then with a warning that names ``who``
+    -- with seeded kaiming-normal weights, and freeze every parameter.  Returns whether the weights are the pretrained ones."""
+    path = None if weights == 'random' else _find_weights(weights)
+    if path is not None:
+        state = torch.load(path, map_location='cpu')
+        own = features.state_dict()
+        picked = {k[len('features.'):]: v for k, v in state.items()
+                  if k.startswith('features.') and k[len('features.'):] in own}
+        features.load_state_dict(picked, strict=True)
+    else:
+        if weights != 'random':  # 'random' is the explicit opt-in of benchmarks, tests and `--vgg-weights random`
+            warnings.warn(f'{VGG19_FILE} not found (pass weights=, or set TORCHSR_VGG19_WEIGHTS): {who} uses '
+                          'seeded random features', stacklevel=3)
+        g = torch.Generator().manual_seed(seed)
+        for m in features:
+            if isinstance(m, Conv2d):
+                fan_out = m.out_channels * m.kernel_size[0] * m.kernel_size[1]
+                with torch.no_grad():
+                    m.weight.copy_(torch.randn(m.weight.shape, generator=g) * (2.0 / fan_out) ** 0.5)
+                    m.bias.zero_()
+    for _, param in features.named_parameters():
+        param.requires_grad = False
+    return path is not None
+
+
+def stack_layers(features: nn.Sequential) -> list:
+    """``features`` as the ``layers`` of ``functional.frozen_conv_stack`` / ``frozen_tap_stack``: no markers."""
+    return [('pool', None) if isinstance(m, MaxPool2x2) else ('conv', m) for m in features if not isinstance(m, Marker)]
+
+
 class VGGLoss(nn.Module):
     """``VGGLoss(feature_layer=36)``; ``forward(source, target) -> 0-dim loss`` (L1 of features).
 
@@ -63,28 +115,7 @@ class VGGLoss(nn.Module):
     def __init__(self, feature_layer: int = 36, weights: Optional[str] = None, seed: int = 1234) -> None:
         super().__init__()
         self.features = make_vgg19_features(feature_layer).eval()
-        path = None if weights == 'random' else _find_weights(weights)
-        if path is not None:
-            state = torch.load(path, map_location='cpu')
-            own = self.features.state_dict()
-            picked = {k[len('features.'):]: v for k, v in state.items()
-                      if k.startswith('features.') and k[len('features.'):] in own}
-            self.features.load_state_dict(picked, strict=True)
-            self.pretrained = True
-        else:
-            if weights != 'random':  # 'random' is the explicit opt-in of benchmarks, tests and `--vgg-weights random`
-                warnings.warn(f'{VGG19_FILE} not found (pass weights=, or set TORCHSR_VGG19_WEIGHTS): VGGLoss uses '
-                              'seeded random features', stacklevel=2)
-            g = torch.Generator().manual_seed(seed)
-            for m in self.features:
-                if isinstance(m, Conv2d):
-                    fan_out = m.out_channels * m.kernel_size[0] * m.kernel_size[1]
-                    with torch.no_grad():
-                        m.weight.copy_(torch.randn(m.weight.shape, generator=g) * (2.0 / fan_out) ** 0.5)
-                        m.bias.zero_()
-            self.pretrained = False
-        for _, param in self.features.named_parameters():
-            param.requires_grad = False
+        self.pretrained = load_frozen_vgg19(self.features, weights, seed, 'VGGLoss')
 
     def features_nhwc(self, x4: Tensor) -> Tensor:
         out = x4
@@ -99,7 +130,7 @@ class VGGLoss(nn.Module):
         return self.features_nhwc(F.to_nhwc(target, 4))
 
     def _stack(self):
-        return [('pool', None) if isinstance(m, MaxPool2x2) else ('conv', m) for m in self.features if not isinstance(m, Marker)]
+        return stack_layers(self.features)
 
     def forward(self, source: Tensor, target: Tensor = None, target_features: Tensor = None) -> Tensor:
         """``l1_loss(features(source), features(target))`` (loss.py:52-54).  Source and target run through the frozen
