@@ -364,7 +364,9 @@ def test_deferred_weight_grads_equal_immediate(dev):
 @pytest.mark.parametrize('case', [(2, 24, 24, 64, 64), (16, 6, 6, 512, 512), (2, 12, 12, 128, 256), (1, 10, 14, 64, 128)])
 def test_dgrad_with_folded_activation_backward(dev, case):
     """srx_conv2d_bwd_data_act: dx = conv_transpose(dy, W) * (x > 0 ? 1 : slope) in one kernel, against the two-step
-    form on the CPU (whole tiles, K-split tail tiles with their fix-up pass, the 144-row tiles' extra rows)."""
+    form on the CPU, on whatever plan the cost model picks for these shapes.  Which tile form runs is not asserted here: whole
+    tiles, K-split tiles with their fix-up pass and the 144-row tiles' extra rows are pinned, each under this epilogue, in
+    test_epilogue_forms_gpu.py."""
     from torchsr_amd import _lib
     from torchsr_amd.layers import Conv2d
     n, h, w, cin, cout = case
@@ -407,7 +409,8 @@ def test_dgrad_with_folded_activation_backward(dev, case):
 def test_dgrad_general_epilogue(dev, case, bf16):
     """srx_conv2d_bwd_data_ex: dx = out_scale * conv_transpose(dy, W) + addend_scale * addend on the leading channels,
     the addend with a row stride of its own, then the activation mask on a channel range -- against the same
-    arithmetic in fp64 on the CPU."""
+    arithmetic in fp64 on the CPU.  The shape comments name what each size is FOR; the plan that runs is the cost model's and is
+    not asserted -- every tile form under this epilogue, whole and K-split, is pinned in test_epilogue_forms_gpu.py."""
     from torchsr_amd import _lib
     from torchsr_amd.layers import Conv2d, set_conv_precision
     n, h, w, cin, cout, ld_dx, ld_add, add_ch = case
